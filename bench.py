@@ -20,7 +20,13 @@ value = segments traced by all ranks in the K timed steps / max-over-ranks wall 
 millions per second; the segment count is the exact count the kernel accumulates (one per
 closest-hit query), so nothing is estimated.
 
-Also reported on rank 0:
+A plain run does what this figure needs and no more: it sets up (the first, untimed call carries
+the item order's estimate), warms up, times the K steps and prints the line.  --dump-outputs DIR
+also writes the last timed step's image, as hipptReadback returns it, to DIR/pixels.npy and
+DIR/accum.npy (float32; dump_outputs below); the scenes are seeded, so the same arguments give
+the same inputs in every run.
+
+With --full, also reported on rank 0 (and config.image_crc32, the image's checksum):
   roofline      FP32 VALU roofline of the mesh kernel (bound "valu": the path is branchy scalar
                 FP32 over a cache-resident scene, neither HBM- nor MFMA-bound): algorithmic
                 FLOP per launch from a counted (untimed) pass of the same step (20 per child-box
@@ -123,6 +129,12 @@ def parse():
                    help="any library option by its hippt.h name without HIPPT_OPT_ (e.g. BVH_QUANT=3); "
                         "recorded in config.options")
     p.add_argument("--pmc", default=None, help="PMC summary JSON for roofline.traffic")
+    p.add_argument("--full", action="store_true",
+                   help="also report what the headline figure does not need: the roofline (a counted pass, the "
+                        "image checksum and the PMC summaries) and the CPU baseline")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps write the last step's image as DIR/pixels.npy and DIR/accum.npy "
+                        "(float32)")
     a = p.parse_args()
     if a.preset:
         for k, v in PRESETS[a.preset].items():
@@ -383,6 +395,36 @@ def make_roofline(args, pmc, traffic, kernel_ms_step, launches, alg_bytes_step, 
     return r
 
 
+DUMP_BUDGET_BYTES = 60_000_000  # --dump-outputs: all files together stay below 64 MB
+DUMP_SEED = 20240
+
+
+def sample_rows(height: int, row_bytes: int, budget: int = DUMP_BUDGET_BYTES) -> np.ndarray:
+    """The image rows --dump-outputs keeps: all of them where height * row_bytes fits the budget,
+    else a seeded sample of whole rows (the same rows for the same image size, in ascending order)."""
+    keep = max(1, budget // max(1, row_bytes))
+    if keep >= height:
+        return np.arange(height)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(height, size=keep, replace=False))
+
+
+def dump_outputs(path: str, pixels: np.ndarray, accum: np.ndarray) -> dict:
+    """Writes the last timed step's image, what hipptReadback hands a caller, as float32 .npy files:
+    pixels.npy (rows, W, 3), the three colour bytes of every packed 32-bit pixel, lowest byte first
+    (the fourth byte is the constant alpha 255), and accum.npy (rows, W, 4), the running-average
+    accumulation the pixels are tonemapped from.  Both hold the same rows (sample_rows)."""
+    h, w = pixels.shape
+    rows = sample_rows(h, w * (3 + 4) * 4)
+    px = np.ascontiguousarray(pixels[rows], dtype=np.uint32)
+    colour = px.view(np.uint8).reshape(len(rows), w, 4)
+    if sys.byteorder != "little":
+        colour = colour[..., ::-1]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "pixels.npy"), colour[..., :3].astype(np.float32))
+    np.save(os.path.join(path, "accum.npy"), np.ascontiguousarray(accum[rows], dtype=np.float32))
+    return {"dir": path, "files": ["pixels.npy", "accum.npy"], "rows": int(len(rows)), "of_rows": int(h)}
+
+
 def free_port() -> int:
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
@@ -496,14 +538,17 @@ def main():
         if not pt._lib.hipptRenderFramesAsync(0, frames, args.depth, None):
             raise SystemExit(hippt.load_library().hipptLastError().decode())
 
-    # counted pass (untimed): traversal counters for the roofline's algorithmic bytes
-    pt.setOption(hippt.OPT_COUNT_TRAVERSAL, 1)
+    # first call (untimed): the item order's estimate; with --full it is also the counted pass, the
+    # traversal counters for the roofline's algorithmic bytes
+    if args.full:
+        pt.setOption(hippt.OPT_COUNT_TRAVERSAL, 1)
     pt.resetStats()
     step()
     device_sync(pt)
-    counted = pt.stats()
+    counted = pt.stats() if args.full else None
     bvh_width = pt._lib.hipptActiveBvhWidth()  # the tree nodeVisits count (2- or 4-wide)
-    pt.setOption(hippt.OPT_COUNT_TRAVERSAL, 0)
+    if args.full:
+        pt.setOption(hippt.OPT_COUNT_TRAVERSAL, 0)
 
     # GPU clock warm-up (untimed, before the W warmup steps): the first ~20 ms of GPU work after an
     # idle period run slow (the whole image's first three launches 7.69 / 7.49 / 7.17 ms, then
@@ -539,37 +584,51 @@ def main():
     samples = hd.sum_over_ranks(st["pixelSamples"], dist)
     value = segments / elapsed_max / 1e6
 
-    # output image of the last step: gathered bands (untimed), checksum on rank 0 (below, with the
-    # PMC summary's check)
-
-    # roofline of the dominant (mesh) kernel, from this rank's counted pass and live events
-    launches = round(st["traceLaunches"] / max(1, args.steps), 3)
-    bytes_node = BYTES_NODE if bvh_width != 4 else BYTES_NODE4
-    flop_node = FLOP_NODE if bvh_width != 4 else 2 * FLOP_NODE
-    alg_bytes_step = (bytes_node * counted["nodeVisits"] + BYTES_TRI * counted["triTests"]
-                      + BYTES_SHADE * (counted["segments"] - counted["pixelSamples"])
-                      + BYTES_SAMPLE * counted["pixelSamples"])
-    flops_step = (flop_node * counted["nodeVisits"] + FLOP_TRI * counted["triTests"]
-                  + FLOP_SHADE * counted["segments"])
-    kernel_ms_step = st["traceMs"] / max(1, args.steps)
-    mean_launch_ms = st["traceMs"] / max(1, st["traceLaunches"])
-    achieved = alg_bytes_step / (kernel_ms_step * 1e-3) / 1e9 if kernel_ms_step > 0 else 0.0
     workload = f"{args.scene} {args.width}x{args.height} {frames}spp depth{args.depth}"
     if args.path_mode == "wavefront":
         workload += " wavefront"
-    pmc = load_pmc(args, workload)
-    px = pt.readback()[0][my_rows]
-    full = (hd.gather_interleaved(px, args.height, dist) if args.split == "interleave"
-            else hd.gather_bands(px, args.height, dist))
-    import zlib
-    image_crc = zlib.crc32(full.tobytes()) & 0xFFFFFFFF if full is not None else None
-    pmc, pmc_refused = check_pmc(pmc, image_crc, lib_sha256(os.environ.get("HIPPT_LIB") or hippt.LIB_PATH), world)
-    traffic = pmc.get("hbm_bytes_per_step") if pmc else None
 
-    roofline = make_roofline(args, pmc, traffic, kernel_ms_step, launches, alg_bytes_step, flops_step,
-                             counted, achieved, mean_launch_ms)
-    if pmc_refused:
-        roofline["pmc_refused"] = pmc_refused
+    # output image of the last step (--full or --dump-outputs): gathered bands (untimed), on rank 0
+    # written out and its checksum taken (below, with the PMC summary's check)
+    image_crc = dumped = None
+    if args.full or args.dump_outputs:
+        def gather(a):
+            return (hd.gather_interleaved(a, args.height, dist) if args.split == "interleave"
+                    else hd.gather_bands(a, args.height, dist))
+
+        px, acc = pt.readback()
+        full = gather(px[my_rows])
+        if args.dump_outputs:
+            full_acc = gather(acc[my_rows])
+            if rank == 0:
+                dumped = dump_outputs(args.dump_outputs, full, full_acc)
+        if args.full and full is not None:
+            import zlib
+            image_crc = zlib.crc32(full.tobytes()) & 0xFFFFFFFF
+
+    roofline = None
+    if args.full:
+        # roofline of the dominant (mesh) kernel, from this rank's counted pass and live events
+        launches = round(st["traceLaunches"] / max(1, args.steps), 3)
+        bytes_node = BYTES_NODE if bvh_width != 4 else BYTES_NODE4
+        flop_node = FLOP_NODE if bvh_width != 4 else 2 * FLOP_NODE
+        alg_bytes_step = (bytes_node * counted["nodeVisits"] + BYTES_TRI * counted["triTests"]
+                          + BYTES_SHADE * (counted["segments"] - counted["pixelSamples"])
+                          + BYTES_SAMPLE * counted["pixelSamples"])
+        flops_step = (flop_node * counted["nodeVisits"] + FLOP_TRI * counted["triTests"]
+                      + FLOP_SHADE * counted["segments"])
+        kernel_ms_step = st["traceMs"] / max(1, args.steps)
+        mean_launch_ms = st["traceMs"] / max(1, st["traceLaunches"])
+        achieved = alg_bytes_step / (kernel_ms_step * 1e-3) / 1e9 if kernel_ms_step > 0 else 0.0
+        pmc = load_pmc(args, workload)
+        pmc, pmc_refused = check_pmc(pmc, image_crc, lib_sha256(os.environ.get("HIPPT_LIB") or hippt.LIB_PATH),
+                                     world)
+        traffic = pmc.get("hbm_bytes_per_step") if pmc else None
+
+        roofline = make_roofline(args, pmc, traffic, kernel_ms_step, launches, alg_bytes_step, flops_step,
+                                 counted, achieved, mean_launch_ms)
+        if pmc_refused:
+            roofline["pmc_refused"] = pmc_refused
 
     k = baseline_config_index(args)
     workload_label = workload
@@ -577,7 +636,7 @@ def main():
         workload_label += (f" (BASELINE configs[{k}])" if world == 1 or args.scaling == "strong"
                            else f" (BASELINE configs[{k}] per GPU)")
     if rank == 0:
-        cpu = cpu_baseline(args, scene) if world == 1 else None
+        cpu = cpu_baseline(args, scene) if args.full and world == 1 else None
         line = {
             "metric": METRIC,
             "value": round(value, 3),
@@ -625,9 +684,12 @@ def main():
                                        "steady state"},
                 **({"options": options} if options else {}),
             },
-            "roofline": roofline,
-            "cpu_baseline": cpu,
         }
+        if dumped:
+            line["outputs"] = dumped
+        if args.full:
+            line["roofline"] = roofline
+            line["cpu_baseline"] = cpu
         if world > 1:
             kms = [r[0] for r in per_rank]
             line["ranks"] = {"trace_ms_per_step": [round(x, 4) for x in kms],

@@ -49,6 +49,34 @@ def test_presets_name_their_baseline_config(bench, preset, k, scene, w, h, spp, 
     assert bench.baseline_config_index(a) is None
 
 
+def test_plain_run_is_the_default_and_full_is_an_option(bench):
+    a = _args(bench, ["--gpus", "1", "--steps", "3", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (3, 2)
+    a = _args(bench, ["--full", "--dump-outputs", "d"])
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_dump_outputs_files_and_row_sample(bench, tmp_path):
+    """--dump-outputs: float32 files of the image's rows; all rows where they fit the budget, else a
+    seeded sample of whole rows, the same on every call, below the budget."""
+    import numpy as np
+    rng = np.random.default_rng(1)
+    px = rng.integers(0, 1 << 32, size=(9, 5), dtype=np.uint64).astype(np.uint32)
+    acc = rng.random((9, 5, 4), dtype=np.float32)
+    info = bench.dump_outputs(str(tmp_path / "o"), px, acc)
+    assert info["rows"] == 9 and info["of_rows"] == 9
+    got_px, got_acc = np.load(tmp_path / "o" / "pixels.npy"), np.load(tmp_path / "o" / "accum.npy")
+    assert got_px.dtype == np.float32 and got_acc.dtype == np.float32
+    assert np.array_equal(got_px, np.stack([(px >> s) & 255 for s in (0, 8, 16)], axis=-1).astype(np.float32))
+    assert got_acc.tobytes() == acc.tobytes()
+    # the default image fits whole; a 4K image is sampled
+    assert len(bench.sample_rows(1080, 1920 * 28)) == 1080
+    rows = bench.sample_rows(2160, 3840 * 28)
+    assert 0 < len(rows) < 2160 and len(rows) * 3840 * 28 <= 64_000_000
+    assert np.all(np.diff(rows) > 0) and rows.min() >= 0 and rows.max() < 2160
+    assert np.array_equal(rows, bench.sample_rows(2160, 3840 * 28))
+
+
 def test_cpu_thread_rule(bench):
     a = _args(bench, [])
     facts = {"nproc": 256, "affinity": 256, "omp_num_threads": 16, "model": "x"}

@@ -1262,14 +1262,14 @@ def test_quantized_tree_tiny_far_nodes(pt):
 
 
 def test_bench_json_contract():
-    """bench.py prints one JSON line with the driver's keys, the roofline and the CPU baseline
+    """bench.py --full prints one JSON line with the driver's keys, the roofline and the CPU baseline
     objects (a short run: 1 step, sampled CPU baseline)."""
     import json
     import os
     import subprocess
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--steps", "1", "--warmup", "0",
+    out = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--full", "--steps", "1", "--warmup", "0",
                           "--width", "320", "--height", "180", "--cpu-seconds", "1", "--cpu-baseline", "port"],
                          capture_output=True, text=True, timeout=300, cwd=repo)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -1288,3 +1288,35 @@ def test_bench_json_contract():
     assert d["config"]["chunk"]["applied"] in (256, 512) and "applied_cap" in d["config"]["chain"]
     cb = d["cpu_baseline"]
     assert cb["kind"] == "port" and cb["value"] > 0 and cb["cores"] >= 1 and cb["unit"] == "Msamples/s"
+
+
+def test_bench_plain_run_dumps_the_last_steps_image(tmp_path):
+    """A plain bench.py run (no --full) reports the headline figure only, neither roofline nor CPU
+    baseline, and --dump-outputs writes the last timed step's image: float32 files, the colour bytes
+    and the accumulation bit-identical to the oracle's frames 0..spp-1."""
+    import json
+    import subprocess
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    w, h, spp = 160, 90, 8
+    out = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "2",
+                          "--warmup", "1", "--width", str(w), "--height", str(h), "--spp", str(spp),
+                          "--dump-outputs", str(tmp_path / "out")],
+                         capture_output=True, text=True, timeout=300, cwd=repo)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, out.stdout
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+        assert k in d, k
+    assert "roofline" not in d and "cpu_baseline" not in d
+    assert d["steps"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert d["config"]["segments_per_step"] > 0 and d["outputs"]["rows"] == h
+    px = np.load(tmp_path / "out" / "pixels.npy")
+    acc = np.load(tmp_path / "out" / "accum.npy")
+    assert px.dtype == np.float32 and px.shape == (h, w, 3)
+    assert acc.dtype == np.float32 and acc.shape == (h, w, 4)
+    ora_px, ora_acc, _, _ = po.MeshScene(scenes.cornell34(), w, h).frames(0, spp, 8)
+    ora_bytes = np.stack([(ora_px >> s) & 255 for s in (0, 8, 16)], axis=-1)
+    assert np.array_equal(px, ora_bytes.astype(np.float32))
+    assert acc.tobytes() == np.ascontiguousarray(ora_acc, dtype=np.float32).tobytes()

@@ -12,5 +12,5 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 OUT=gpurun_out/pmc_$NAME
 mkdir -p "$OUT"
 timeout -s KILL 120 rocprofv3 --pmc $CTRS -T --output-format csv -d "$OUT" -o run -- \
-    python3 bench.py --steps 3 --warmup 1 --cpu-baseline off "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"
+    python3 bench.py --full --steps 3 --warmup 1 --cpu-baseline off "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"
 echo "pmc $NAME done"

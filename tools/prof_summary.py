@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Summarise a tools/profile.sh run into profiles/<tag>_summary.md and profiles/pmc_summary.json.
 
-Launch order of bench.py: a counted pass (mesh_kernel<true>), then the warmup steps and the timed
+Launch order of bench.py --full: a counted pass (mesh_kernel<true>), then the warmup steps and the timed
 steps (mesh_kernel<false>; with chained batches a launch may trace several steps, another only
 combine, and a step may have no launch of its own).  rocprofv3 -T truncates the template instances
 to "mesh_kernel", so the timed launches are the last launches_per_step x steps mesh_kernel
@@ -174,7 +174,7 @@ def main():
     stats_csv = open(os.path.join(root, "kt", "run_kernel_stats.csv")).read()
     with open(os.path.join(prof_dir, f"{name}_summary.md"), "w") as f:
         f.write(f"# rocprofv3 summary `{tag}` — {workload}\n\n")
-        f.write("Command: `bash tools/profile.sh` (bench.py --steps 20 --warmup 5 under rocprofv3 "
+        f.write("Command: `bash tools/profile.sh` (bench.py --full --steps 20 --warmup 5 under rocprofv3 "
                 "--kernel-trace --stats, then separate --pmc passes; figures per step).\n\n")
         f.write("## rocprofv3 --kernel-trace --stats (all dispatches, incl. the counted pass)\n\n```\n")
         f.write(stats_csv)

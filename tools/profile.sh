@@ -13,7 +13,7 @@ export TMPDIR=/tmp
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 OUT=gpurun_out/prof_${TAG}
 mkdir -p "$OUT"
-ARGS=(--steps 20 --warmup 5 --cpu-baseline off "$@")
+ARGS=(--full --steps 20 --warmup 5 --cpu-baseline off "$@")
 sha256sum qt-raytracer_amd/libhippt.so > "$OUT/lib.sha256"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -T --output-format csv -d "$OUT/kt" -o run -- \
     python3 bench.py "${ARGS[@]}" > "$OUT/kt_bench.json" 2> "$OUT/kt_bench.err"

@@ -3,7 +3,7 @@
 set -e
 TAG=${1:?tag}
 mkdir -p gpurun_out/$TAG
-B="timeout -k 10 300 python3 bench.py"
+B="timeout -k 10 300 python3 bench.py --full"
 bash tools/profile.sh $TAG
 bash tools/profile.sh ${TAG}_blob --scene blob70k
 python3 tools/prof_summary.py $TAG > /dev/null
