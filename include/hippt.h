@@ -153,6 +153,30 @@ bool hipptReadback(unsigned int *pixels, float *accum, const char **errorMessage
 /* Zeroes the accumulation buffer (GpuPathTracer::resetAccumulation, GpuPathTracer.cpp:85-95). */
 bool hipptResetAccumulation(const char **errorMessage);
 
+/* ---- ray queries --------------------------------------------------------------------- */
+/* Per-ray answers over the uploaded scene (hipptUploadMesh / hipptUploadScene; after an Init, which
+ * creates the device contexts), by the renderer's contract: every t is computed with the renderer's
+ * arithmetic, and the BVH only culls.  A call runs after the work already queued on its device,
+ * waits for its own work only and leaves pending asynchronous frames, the image and the counters of
+ * hipptGetStats untouched.  A ray with a non-finite origin, direction or tmin, a NaN tmax, an
+ * all-zero direction, tmin < 0 or tmax <= tmin is a miss (tmax may be +inf). */
+enum { HIPPT_RAYS_DEVICE = 1 };   /* flags: every pointer of the call is device memory */
+
+/* rays: numRays x 8 floats: origin xyz, tmin, direction xyz (any length), tmax.
+ * Closest hit over the uploaded scene by the renderer's contract: the lexicographic minimum of
+ * (t, primitive id) over hits with tmin <= t < tmax; ids are the upload's (triangles 0..numTris-1,
+ * then spheres).  t[i] = +inf and prim[i] = -1 on a miss.  t or prim may be null.  Blocking.
+ * Host memory is cut into contiguous shares over the devices of hipptSetDevices and staged in
+ * slices (HIPPT_OPT_QUERY_SLICE); with HIPPT_RAYS_DEVICE the pointers (rays 16-byte aligned) must
+ * be memory of one of those devices, and the whole batch runs there unstaged. */
+bool hipptTraceRays(const float *rays, long long numRays, int flags, float *t, int *prim, const char **errorMessage);
+/* occluded[i] = 1 if any primitive is hit with tmin <= t < tmax, else 0 (stops at the first one found). */
+bool hipptOccluded(const float *rays, long long numRays, int flags, unsigned char *occluded, const char **errorMessage);
+/* The camera ray of sample `frame` of every pixel of the current Init (the ray hipptRenderFrames
+ * starts that sample with: same seed, jitter and lens draw), traced with tmin 0.001, tmax inf:
+ * t and prim hold width*height entries, row 0 = v = 0. */
+bool hipptTraceCamera(int frame, int flags, float *t, int *prim, const char **errorMessage);
+
 /* ---- counters and options ---------------------------------------------------------- */
 typedef struct hipptStats {
     unsigned long long segments;      /* closest-hit queries traced (rays x bounces) */
@@ -272,6 +296,9 @@ enum {
                                        multiple of it), or 64 consecutive pixels of a row (0); -1 (default):
                                        automatic (8 for a band of consecutive rows, 0 for interleaved row
                                        shares).  Same results either way */
+    , HIPPT_OPT_QUERY_SLICE = 33    /* ray queries from host memory: rays per slice staged through a device's
+                                       buffers, 64..2^28; 0 (default): automatic (2^22).  Same results either
+                                       way */
 };
 /* Records of the chained runs closed since the last call (HIPPT_OPT_CHAIN_AUDIT), as 32-bit words:
  * per run a 16-word header  [0] 0xC4A1D17 [1] run id [2] device [3] batch 0's first frame [4] frames

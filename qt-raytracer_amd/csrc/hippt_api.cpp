@@ -31,6 +31,7 @@
 #include "bvh_builder.h"
 #include "mesh_io.h"
 #include "hippt_device.h"
+#include "hippt_query.h"
 #include "hippt_wavefront.h"
 
 struct hipptBvh {
@@ -218,6 +219,18 @@ struct Ctx {
     std::vector<EventPair> freeEv;                       // pairs not in flight
     std::vector<std::pair<int, EventPair>> pending;      // (0 trace / 1 combine, events)
     hipEvent_t presentEv[2] = {nullptr, nullptr};        // band copy into State::present[b] done
+    // Ray queries (hipptTraceRays, hipptOccluded, hipptTraceCamera): the claim counters, a spill area of
+    // their own (a render's may be in use by launches queued before the query, and growing it would
+    // wait for them), the staging buffers of one slice of a host-memory batch (rays in, results out),
+    // and the event a call waits on.  Allocated on first use, freed with the context.
+    unsigned *qCtr = nullptr;
+    int *qSpill = nullptr;
+    size_t qSpillBytes = 0;
+    void *qStage = nullptr;
+    size_t qStageBytes = 0;
+    hipEvent_t qDone = nullptr;
+    long long qOccKey = -1;  // occupancy cached per (scene version, layout, kernel variant)
+    int qBlocksPerCu = 0;
 };
 
 struct SceneHost {
@@ -282,6 +295,7 @@ struct State {
     int pixelTile = -1;    // the item order's runs: tile columns (HIPPT_OPT_PIXEL_TILE; 0 rows, -1 automatic)
     int chainBatches = -1; // batches a chained launch may trace (HIPPT_OPT_CHAIN; 0 off, -1 automatic)
     bool chainAudit = false;            // HIPPT_OPT_CHAIN_AUDIT
+    long long querySlice = 0;           // rays per staged slice of a host-memory query (HIPPT_OPT_QUERY_SLICE; 0 automatic)
     std::vector<unsigned> auditWords;   // closed runs' audit words not yet read (hipptChainAudit)
     std::vector<std::pair<int, uint32_t *>> rngTables;  // per device, built on first use
     // The big work buffers (sample scratch, chain ring, spill area) of the contexts a re-initialization
@@ -521,6 +535,10 @@ void destroy_ctx(Ctx &c, bool keep) {
     drop(c.spill, c.spillBytes);
     c.spill = nullptr;
     c.spillBytes = 0;
+    (void)hipFree(c.qCtr);
+    (void)hipFree(c.qSpill);
+    (void)hipFree(c.qStage);
+    if (c.qDone) (void)hipEventDestroy(c.qDone);
     (void)hipHostFree(c.wfHost);
     for (hipEvent_t e : c.wfPoll)
         if (e) (void)hipEventDestroy(e);
@@ -1813,6 +1831,234 @@ bool render_locked(int frameIndex, int count, int maxDepth, const unsigned int *
     return true;
 }
 
+// ---- ray queries (hippt_query.hip; include/hippt.h hipptTraceRays, hipptOccluded, hipptTraceCamera) ----
+// A query is one or more launches of the query kernel on a context's stream, after whatever the stream
+// already holds, followed by a wait for the query's own event.  It reads the scene buffers only: it
+// does not flush the deferred combine or the chain, launches no held batch, and leaves the stats and
+// the timing events alone, so pending asynchronous frames come out as if it had not been made.
+struct QueryCall {
+    const float *rays = nullptr;  // numRays x 8 floats (camera: null)
+    long long n = 0;
+    int flags = 0;
+    float *t = nullptr;
+    int *prim = nullptr;
+    unsigned char *occ = nullptr;
+    bool any = false, camera = false;
+    int frame = 0;
+};
+
+// The traversal's layout and parameters for the current scene on context c: enqueue_locked's choices
+// (tree width, LDS residency, stack capacity, the top of the tree in LDS) with the wavefront extend
+// kernel's loop exits, over float nodes.
+bool query_setup(Ctx &c, const QueryCall &call, hippt::QueryParams &q, const char **err) {
+    State &s = S();
+    const bool wide = s.scene.numNodes4 > 0 && s.bvhWidth != 2;
+    const int numNodes = wide ? s.scene.numNodes4 : s.scene.numNodes, numTris = s.scene.numTris;
+    const int numMats = int(s.scene.mats.size() / 2);
+    const bool ldsScene = s.ldsScene && hippt::mesh_lds_bytes(0, numNodes, numTris, wide, 0, numMats) <=
+                                            hippt::mesh_lds_scene_limit();
+    const bool topTree = wide && !ldsScene;
+    const int capLimit = s.stackCap > 0 ? s.stackCap
+                         : ldsScene     ? 30
+                         : topTree && s.scene.stackBound4 > kWideStackCap ? kSpillStackCap
+                                                                           : kWideStackCap;
+    const int stackCap = wide ? std::max(1, std::min(s.scene.stackBound4, capLimit)) : 0;
+    const int stackDepth = wide ? stackCap + 2 : std::max(1, s.scene.levels);
+    unsigned topBytes = 0;
+    if (topTree && s.ldsTopNodes != 0) {
+        size_t n = size_t(std::min(numNodes, kTopOrderNodes));
+        if (s.ldsTopNodes > 0) {
+            n = std::min(n, size_t(s.ldsTopNodes));
+        } else {
+            const size_t stackBytes = hippt::mesh_lds_bytes(stackDepth, 0, 0, true);
+            const size_t budget = hippt::mesh_lds_block_budget();
+            n = std::min(n, budget > stackBytes ? (budget - stackBytes) / 128 : 0);
+        }
+        topBytes = unsigned(n * 128);
+    }
+    q = hippt::QueryParams{};
+    q.nodes = wide ? c.nodes4 : c.nodes;
+    q.tris = c.tris;
+    q.stackDepth = stackDepth;
+    q.numNodes = numNodes;
+    q.numTris = numTris;
+    q.ldsScene = ldsScene ? 1 : 0;
+    q.full = s.scene.full ? 1 : 0;
+    q.wide = wide ? 1 : 0;
+    q.stackCap = stackCap;
+    q.spillCap = wide ? s.scene.stackBound4 + 3 : 0;
+    q.topBytes = topBytes;
+    const bool lambertGlobal = !ldsScene && !s.scene.full;
+    q.waveThreshold = s.waveThreshold >= 0 ? s.waveThreshold : ldsScene ? 24 : lambertGlobal ? 40 : 32;
+    q.leafExit = unsigned(s.leafExit >= 0 ? s.leafExit : ldsScene ? 4 : lambertGlobal ? 22 : 17);
+    q.nodeExit = unsigned(s.nodeExit >= 0 ? s.nodeExit : ldsScene ? 8 : lambertGlobal ? 56 : 48);
+    if (call.camera) {
+        hippt::QueryCam &k = q.cam;
+        k.cam = current_camera();
+        k.invW = 1.0f / float(std::max(1, s.width - 1));
+        k.invH = 1.0f / float(std::max(1, s.height - 1));
+        k.width = s.width;
+        k.y0 = 0;
+        k.rowStride = 1;
+        k.firstFrame = call.frame;
+        k.bandPixels = unsigned(s.width) * unsigned(s.height);
+        k.rcpBandPixels = 1.0f / float(k.bandPixels);
+        k.rcpWidth = 1.0f / float(s.width);
+    }
+    HIP_TRY(hipSetDevice(c.device));
+    const long long occKey = ((long long)s.scene.version << 24) ^ ((long long)topBytes << 40) ^ (stackDepth << 8) ^
+                             (ldsScene ? 16 : 0) ^ (wide ? 8 : 0) ^ (s.scene.full ? 4 : 0) ^ (call.any ? 2 : 0) ^
+                             (call.camera ? 1 : 0);
+    if (c.qOccKey != occKey) {
+        c.qBlocksPerCu = hippt::query_blocks_per_cu(q, call.any, call.camera);
+        c.qOccKey = occKey;
+    }
+    if (!c.qCtr) HIP_TRY(hipMalloc(&c.qCtr, hippt::kQueryCtrBytes));
+    if (!c.qDone) HIP_TRY(hipEventCreateWithFlags(&c.qDone, hipEventDisableTiming));
+    if (wide) {
+        const size_t bytes = size_t(c.cus) * size_t(c.qBlocksPerCu) * hippt::kMeshBlock * size_t(q.spillCap) * sizeof(int);
+        if (c.qSpillBytes < bytes) {  // (no query is in flight: every call waits for its own)
+            (void)hipFree(c.qSpill);
+            c.qSpill = nullptr;
+            c.qSpillBytes = 0;
+            HIP_TRY(hipMalloc(&c.qSpill, bytes));
+            c.qSpillBytes = bytes;
+        }
+        q.spill = c.qSpill;
+    }
+    q.counter = c.qCtr;
+    return true;
+}
+
+// Enqueues rays [first, first + m) of a query whose pointers (q.rays, q.t, ...) are already those of
+// ray `first`.
+bool query_enqueue(Ctx &c, hippt::QueryParams q, unsigned first, unsigned m, const QueryCall &call, const char **err) {
+    q.numRays = m;
+    q.firstItem = first;
+    q.chunk = m >= (1u << 20) ? 256u : 64u;
+    const long long blocks =
+        std::max(1LL, std::min<long long>((long long)c.cus * c.qBlocksPerCu, (m + hippt::kMeshBlock - 1) / hippt::kMeshBlock));
+    HIP_TRY(hipMemsetAsync(c.qCtr, 0, hippt::kQueryCtrBytes, c.stream));
+    HIP_TRY(hippt::launch_query(q, int(blocks), call.any, call.camera, c.stream));
+    return true;
+}
+
+bool query_locked(const QueryCall &call, const char **err) {
+    State &s = S();
+    // argument and state checks first: none of them touches the GPU
+    if (call.n < 0) return fail(err, "ray query: negative ray count");
+    if (!call.camera && !call.rays && call.n > 0) return fail(err, "ray query: null ray buffer");
+    if (call.any ? !call.occ : (!call.t && !call.prim)) return fail(err, "ray query: no output buffer");
+    if (call.camera && call.frame < 0) return fail(err, "ray query: negative frame");
+    if (s.scene.kind != HIPPT_SCENE_MESH)
+        return fail(err, "ray query: needs a scene from hipptUploadMesh or hipptUploadScene (the built-in scene has none)");
+    if (!s.ready || s.ctxs.empty()) return fail(err, "ray query: HIP path tracer not initialized");
+    long long n = call.n;
+    if (call.camera) {
+        n = (long long)s.width * (long long)s.height;
+        if (n > (1LL << 31) - 1) return fail(err, "ray query: image too large");
+    }
+    if (n == 0) return true;
+    const bool device = (call.flags & HIPPT_RAYS_DEVICE) != 0;
+    if (call.flags & ~HIPPT_RAYS_DEVICE) return fail(err, "ray query: unknown flags");
+    constexpr long long kLaunchRays = 1LL << 30;
+    if (device) {
+        // every pointer on the device of one context: the whole batch runs there, unstaged
+        int dev = -1;
+        const void *ptrs[4] = {call.rays, call.t, call.prim, call.occ};
+        const size_t align[4] = {16, 4, 4, 1};
+        for (int k = 0; k < 4; ++k) {
+            if (!ptrs[k]) continue;
+            hipPointerAttribute_t a{};
+            if (hipPointerGetAttributes(&a, ptrs[k]) != hipSuccess || a.type != hipMemoryTypeDevice) {
+                (void)hipGetLastError();
+                return fail(err, "ray query: HIPPT_RAYS_DEVICE needs device memory pointers");
+            }
+            if (dev >= 0 && a.device != dev) return fail(err, "ray query: pointers on different devices");
+            dev = a.device;
+            if (reinterpret_cast<uintptr_t>(ptrs[k]) % align[k]) return fail(err, "ray query: misaligned device pointer");
+        }
+        Ctx *cp = nullptr;
+        for (Ctx &c : s.ctxs)
+            if (c.device == dev && !cp) cp = &c;
+        if (!cp) return fail(err, "ray query: the pointers are on a device that is none of hipptSetDevices'");
+        Ctx &c = *cp;
+        HIP_TRY(hipSetDevice(c.device));
+        if (!ensure_scene(c, err)) return false;
+        hippt::QueryParams q;
+        if (!query_setup(c, call, q, err)) return false;
+        for (long long at = 0; at < n; at += kLaunchRays) {
+            const unsigned m = unsigned(std::min(kLaunchRays, n - at));
+            q.rays = call.rays ? reinterpret_cast<const float4 *>(call.rays + 8 * at) : nullptr;
+            q.t = call.t ? call.t + at : nullptr;
+            q.prim = call.prim ? call.prim + at : nullptr;
+            q.occluded = call.occ ? call.occ + at : nullptr;
+            if (!query_enqueue(c, q, unsigned(at), m, call, err)) return false;
+        }
+        HIP_TRY(hipEventRecord(c.qDone, c.stream));
+        HIP_TRY(hipEventSynchronize(c.qDone));
+        return true;
+    }
+    // host memory: contiguous shares over the contexts, each cut into slices staged through the
+    // context's buffers (rays in, results out); slice j of every context is enqueued before slice j + 1
+    const long long slice = s.querySlice > 0 ? std::max(64LL, s.querySlice) : (1LL << 22);
+    const size_t K = s.ctxs.size();
+    std::vector<hippt::QueryParams> qs(K);
+    std::vector<char *> stage(K, nullptr);
+    const size_t cap = size_t(std::min(slice, n));
+    const size_t offT = cap * 32, offP = offT + cap * 4, offO = offP + cap * 4, stageBytes = offO + ((cap + 15) & ~size_t(15));
+    for (size_t k = 0; k < K; ++k) {
+        Ctx &c = s.ctxs[k];
+        if (n * (long long)(k + 1) / (long long)K == n * (long long)k / (long long)K) continue;  // an empty share
+        HIP_TRY(hipSetDevice(c.device));
+        if (!ensure_scene(c, err)) return false;
+        if (!query_setup(c, call, qs[k], err)) return false;
+        if (c.qStageBytes < stageBytes) {
+            (void)hipFree(c.qStage);
+            c.qStage = nullptr;
+            c.qStageBytes = 0;
+            HIP_TRY(hipMalloc(&c.qStage, stageBytes));
+            c.qStageBytes = stageBytes;
+        }
+        stage[k] = static_cast<char *>(c.qStage);
+    }
+    bool left = true;
+    for (long long j = 0; left; ++j) {
+        left = false;
+        for (size_t k = 0; k < K; ++k) {
+            const long long a = n * (long long)k / (long long)K, b = n * (long long)(k + 1) / (long long)K;
+            const long long at = a + j * slice;
+            if (at >= b) continue;
+            left = true;
+            Ctx &c = s.ctxs[k];
+            const unsigned m = unsigned(std::min(slice, b - at));
+            HIP_TRY(hipSetDevice(c.device));
+            hippt::QueryParams q = qs[k];
+            char *const st = stage[k];
+            if (!call.camera) {
+                HIP_TRY(hipMemcpyAsync(st, call.rays + 8 * at, size_t(m) * 32, hipMemcpyHostToDevice, c.stream));
+                q.rays = reinterpret_cast<const float4 *>(st);
+            }
+            q.t = call.t ? reinterpret_cast<float *>(st + offT) : nullptr;
+            q.prim = call.prim ? reinterpret_cast<int *>(st + offP) : nullptr;
+            q.occluded = call.occ ? reinterpret_cast<unsigned char *>(st + offO) : nullptr;
+            if (!query_enqueue(c, q, unsigned(at), m, call, err)) return false;
+            if (call.t) HIP_TRY(hipMemcpyAsync(call.t + at, q.t, size_t(m) * 4, hipMemcpyDeviceToHost, c.stream));
+            if (call.prim) HIP_TRY(hipMemcpyAsync(call.prim + at, q.prim, size_t(m) * 4, hipMemcpyDeviceToHost, c.stream));
+            if (call.occ) HIP_TRY(hipMemcpyAsync(call.occ + at, q.occluded, size_t(m), hipMemcpyDeviceToHost, c.stream));
+        }
+    }
+    for (size_t k = 0; k < K; ++k) {
+        if (!stage[k]) continue;
+        Ctx &c = s.ctxs[k];
+        HIP_TRY(hipSetDevice(c.device));
+        HIP_TRY(hipEventRecord(c.qDone, c.stream));
+    }
+    for (size_t k = 0; k < K; ++k)
+        if (stage[k]) HIP_TRY(hipEventSynchronize(s.ctxs[k].qDone));
+    return true;
+}
+
 }  // namespace
 
 // ---- reference ABI ----------------------------------------------------------------------------
@@ -2076,6 +2322,54 @@ extern "C" bool hipptUploadMesh(const float *verts, const int *triMaterial, int 
                                         1.0f};
     return hipptUploadScene(verts, triMaterial, numTris, nullptr, nullptr, 0, mats.data(), numMaterials, lookfrom,
                             lookat, vup, vfovDeg, aperture, focusDist, err);
+} catch (const std::exception &e) {
+    return fail_free(err, e.what());
+} catch (...) {
+    return fail_free(err, "unknown exception");
+}
+
+// ---- ray queries ---------------------------------------------------------------------------------
+extern "C" bool hipptTraceRays(const float *rays, long long numRays, int flags, float *t, int *prim,
+                               const char **err) try {
+    std::lock_guard<std::mutex> g(S().mu);
+    QueryCall q;
+    q.rays = rays;
+    q.n = numRays;
+    q.flags = flags;
+    q.t = t;
+    q.prim = prim;
+    return query_locked(q, err);
+} catch (const std::exception &e) {
+    return fail_free(err, e.what());
+} catch (...) {
+    return fail_free(err, "unknown exception");
+}
+
+extern "C" bool hipptOccluded(const float *rays, long long numRays, int flags, unsigned char *occluded,
+                              const char **err) try {
+    std::lock_guard<std::mutex> g(S().mu);
+    QueryCall q;
+    q.rays = rays;
+    q.n = numRays;
+    q.flags = flags;
+    q.occ = occluded;
+    q.any = true;
+    return query_locked(q, err);
+} catch (const std::exception &e) {
+    return fail_free(err, e.what());
+} catch (...) {
+    return fail_free(err, "unknown exception");
+}
+
+extern "C" bool hipptTraceCamera(int frame, int flags, float *t, int *prim, const char **err) try {
+    std::lock_guard<std::mutex> g(S().mu);
+    QueryCall q;
+    q.camera = true;
+    q.frame = frame;
+    q.flags = flags;
+    q.t = t;
+    q.prim = prim;
+    return query_locked(q, err);
 } catch (const std::exception &e) {
     return fail_free(err, e.what());
 } catch (...) {
@@ -2511,6 +2805,10 @@ extern "C" bool hipptSetOption(int key, long long value) try {
         if (value != -1 && value != 0 && value != 8 && value != 16 && value != 32) return false;
         s.pixelTile = int(value);
         return true;
+    case HIPPT_OPT_QUERY_SLICE:
+        if (value < 0 || value > (1LL << 28)) return false;
+        s.querySlice = value;
+        return true;
     default: return false;
     }
 } catch (const std::exception &e) {
@@ -2563,6 +2861,7 @@ extern "C" long long hipptGetOption(int key) try {
     case HIPPT_OPT_CHAIN: return s.chainBatches;
     case HIPPT_OPT_CHAIN_AUDIT: return s.chainAudit ? 1 : 0;
     case HIPPT_OPT_PIXEL_TILE: return s.pixelTile;
+    case HIPPT_OPT_QUERY_SLICE: return s.querySlice;
     case HIPPT_INFO_LDS_TOP_BYTES: return s.activeTopBytes;
     case HIPPT_INFO_BLOCKS_PER_CU: return s.activeBlocksPerCu;
     case HIPPT_INFO_CHUNK: return s.activeChunk;

@@ -944,9 +944,9 @@ __device__ __forceinline__ void begin(Trav &T) {
 
 // A hit candidate (t >= tmin when `ok`) of primitive i (leaf order, original id `orig`) replaces the
 // closest hit when (t, orig) < (bestT, bestO).  Bitwise and selects: no branch per candidate (the
-// short-circuit form cost three exec-mask branches per triangle test).
-__device__ __forceinline__ void take_hit(Trav &T, float tt, bool ok, int i, int orig) {
-    const float tmin = 0.001f;
+// short-circuit form cost three exec-mask branches per triangle test).  tmin: the renderer's 0.001;
+// the ray queries (hippt_query.hip) pass the ray's own.
+__device__ __forceinline__ void take_hit(Trav &T, float tt, bool ok, int i, int orig, float tmin = 0.001f) {
     const bool win = ok & (tt >= tmin) & ((tt < T.bestT) | ((tt == T.bestT) & (orig < T.bestO)));
     T.bestT = win ? tt : T.bestT;
     T.bestI = win ? i : T.bestI;
@@ -956,14 +956,13 @@ __device__ __forceinline__ void take_hit(Trav &T, float tt, bool ok, int i, int 
 // Primitive i (leaf order) against the ray: closest hit = min (t, primitive id).
 template <bool STATS, bool FULL>
 __device__ __forceinline__ void test_prim_data(Trav &T, const Ray &r, float4 A, float4 B, float4 Cc, int i,
-                                               unsigned long long &ntest, unsigned *pc) {
-    const float tmin = 0.001f;
+                                               unsigned long long &ntest, unsigned *pc, float tmin = 0.001f) {
     prof<STATS>(pc, 5);
     if (STATS) ++ntest;
     if (FULL && __float_as_int(Cc.z) != 0) {
         float tt = 0.0f;
         const bool hit = sphere_t(A, B.x, r, tmin, tt);
-        take_hit(T, tt, hit, i, __float_as_int(Cc.y));
+        take_hit(T, tt, hit, i, __float_as_int(Cc.y), tmin);
         return;
     }
     // Möller–Trumbore, division-free edge tests (pt_oracle.c po_tri_hit)
@@ -983,14 +982,14 @@ __device__ __forceinline__ void test_prim_data(Trav &T, const Ray &r, float4 A, 
     const float us = neg ? -un : un, vs = neg ? -vn : vn;
     const bool inside = (det != 0.0f) & (us >= 0.0f) & (vs >= 0.0f) & (us + vs <= fabsf(det));
     // (the division for every lane, without this branch: blob70k -1%, DESIGN_LOG.md §A.0)
-    if (inside) take_hit(T, fdot(e2x, e2y, e2z, qvx, qvy, qvz) / det, true, i, __float_as_int(Cc.y));
+    if (inside) take_hit(T, fdot(e2x, e2y, e2z, qvx, qvy, qvz) / det, true, i, __float_as_int(Cc.y), tmin);
 }
 
 template <bool STATS, bool FULL>
 __device__ __forceinline__ void test_prim(Trav &T, const Ray &r, const float4 *tris, int i, unsigned long long &ntest,
-                                          unsigned *pc) {
+                                          unsigned *pc, float tmin = 0.001f) {
     const float4 *tp = tris + 3 * i;
-    test_prim_data<STATS, FULL>(T, r, tp[0], tp[1], tp[2], i, ntest, pc);
+    test_prim_data<STATS, FULL>(T, r, tp[0], tp[1], tp[2], i, ntest, pc, tmin);
 }
 
 // One leaf-loop iteration for this lane: the primitives of leaf T.leaf, then the next leaf if it
@@ -998,7 +997,7 @@ __device__ __forceinline__ void test_prim(Trav &T, const Ray &r, const float4 *t
 // so that lanes with short leaves move on: Cornell -9%, blob70k -5%.)
 template <bool STATS, bool FULL, typename Pop, bool PAIRS = false>
 __device__ __forceinline__ void leaf_step(Trav &T, const Ray &r, const float4 *tris, unsigned long long &ntest,
-                                          unsigned *pc, Pop pop) {
+                                          unsigned *pc, Pop pop, float tmin = 0.001f) {
     const int code = ~T.leaf;
     const int first = code >> 4, last = first + (code & 15);
     if (PAIRS) {
@@ -1014,11 +1013,11 @@ __device__ __forceinline__ void leaf_step(Trav &T, const Ray &r, const float4 *t
                 B1 = tp[4];
                 C1 = tp[5];
             }
-            test_prim_data<STATS, FULL>(T, r, A0, B0, C0, i, ntest, pc);
-            if (two) test_prim_data<STATS, FULL>(T, r, A1, B1, C1, i + 1, ntest, pc);
+            test_prim_data<STATS, FULL>(T, r, A0, B0, C0, i, ntest, pc, tmin);
+            if (two) test_prim_data<STATS, FULL>(T, r, A1, B1, C1, i + 1, ntest, pc, tmin);
         }
     } else {
-        for (int i = first; i < last; ++i) test_prim<STATS, FULL>(T, r, tris, i, ntest, pc);
+        for (int i = first; i < last; ++i) test_prim<STATS, FULL>(T, r, tris, i, ntest, pc, tmin);
     }
     // a leaf that was next in line is processed in the same loop
     T.leaf = 0;
@@ -1034,12 +1033,13 @@ __device__ __forceinline__ void leaf_step(Trav &T, const Ray &r, const float4 *t
 // Interior nodes: the far child is written to the slot above the top unconditionally (one
 // spare slot per lane) and kept only when both children are hit; the top is read
 // unconditionally and used only when neither is (branch-free child selection).
+// tmin (here and in traverse_round_wide): the hits' lower bound and the box test's near bound, the
+// renderer's 0.001 or a queried ray's own (>= +0: the child keys are ordered as unsigned).
 template <int NODE_F4, bool STATS, bool FULL>
 __device__ __forceinline__ void traverse_round(Trav &T, const Ray &r, int *my, const float4 *nodes,
                                                const float4 *tris, unsigned long long &nvis,
                                                unsigned long long &ntest, unsigned *pc, unsigned leafExit = 0,
-                                               unsigned nodeExit = 0) {
-    const float tmin = 0.001f;
+                                               unsigned nodeExit = 0, float tmin = 0.001f) {
     while (T.cur >= 0) {
         prof<STATS>(pc, 3);
         const float4 *nd = nodes + __umul24(unsigned(T.cur), unsigned(NODE_F4));  // full-rate 24-bit mul
@@ -1077,7 +1077,7 @@ __device__ __forceinline__ void traverse_round(Trav &T, const Ray &r, int *my, c
     }
     while (T.leaf != 0) {
         prof<STATS>(pc, 4);
-        leaf_step<STATS, FULL>(T, r, tris, ntest, pc, [&] { return T.sp > 0 ? my[T.sp -= kMeshBlock] : kDone; });
+        leaf_step<STATS, FULL>(T, r, tris, ntest, pc, [&] { return T.sp > 0 ? my[T.sp -= kMeshBlock] : kDone; }, tmin);
         // back to the node loop once at most nodeExit lanes still hold a leaf (they keep it)
         if (nodeExit && __popcll(__ballot(T.leaf != 0)) <= nodeExit) break;
     }
@@ -1248,12 +1248,12 @@ __device__ __forceinline__ void traverse_round_wide(Trav &T, const Ray &r, int *
                                                     const float4 *tris, unsigned long long &nvis,
                                                     unsigned long long &ntest, unsigned *pc, unsigned leafExit,
                                                     unsigned nodeExit, const SpillArea &S,
-                                                    unsigned topBytes = 0, unsigned refBits = 0) {
+                                                    unsigned topBytes = 0, unsigned refBits = 0,
+                                                    float tmin = 0.001f) {
     static_assert(!HYBRID || (QUANT && TOP), "hybrid trees: 8-bit nodes below an LDS top");
     static_assert(!PACKED || (LDS0 && !QUANT), "packed keys: LDS-resident float trees");
     static_assert(!HALF || (TOP && !QUANT && !LDS0), "half planes: 4-wide trees in global memory");
     const unsigned refMask = PACKED ? (1u << refBits) - 1u : 0u;
-    const float tmin = 0.001f;
     // near-row byte offsets of this ray's octant within a node (x at 0/16, y at 32/48, z at 64/80)
     const unsigned sx = near_row(r.ix), sy = near_row(r.iy) | 32u, sz = near_row(r.iz) | 64u;
     while (T.cur >= 0) {
@@ -1398,7 +1398,7 @@ __device__ __forceinline__ void traverse_round_wide(Trav &T, const Ray &r, int *
     auto popw = [&] { return pop_wide<SPILL, PACKED>(T, my, S, refBits); };
     while (T.leaf != 0) {
         prof<STATS>(pc, 4);
-        leaf_step<STATS, FULL, decltype(popw), !LDS0>(T, r, tris, ntest, pc, popw);
+        leaf_step<STATS, FULL, decltype(popw), !LDS0>(T, r, tris, ntest, pc, popw, tmin);
         if (nodeExit && __popcll(__ballot(T.leaf != 0)) <= nodeExit) break;
     }
 }

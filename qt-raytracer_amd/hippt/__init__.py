@@ -56,6 +56,7 @@ OPT_WAVEFRONT_SORT = 29
 OPT_CHAIN = 30
 OPT_CHAIN_AUDIT = 31
 OPT_PIXEL_TILE = 32
+OPT_QUERY_SLICE = 33
 OPT_PIXEL_FORMAT = 25
 PIXEL_ARGB = 0
 PIXEL_RGBA8 = 1
@@ -63,6 +64,7 @@ INFO_LDS_TOP_BYTES = 100
 INFO_BLOCKS_PER_CU = 101
 INFO_CHUNK = 102
 INFO_CHAIN_CAP = 103
+RAYS_DEVICE = 1
 
 # Every symbol include/hippt.h declares (checked by tests/test_abi_cpu.py).
 EXPORTS = (
@@ -78,6 +80,7 @@ EXPORTS = (
     "hipptLastError", "hipptBvhBuild", "hipptBvhNodeCount", "hipptBvhDepth", "hipptBvhCopy", "hipptBvhFree",
     "hipptBvh4NodeCount", "hipptBvh4Depth", "hipptBvh4StackBound", "hipptBvh4Copy", "hipptBvh4QCopy", "hipptBvh4QNodeCount",
     "hipptActiveBvhWidth", "hipptChainAudit",
+    "hipptTraceRays", "hipptOccluded", "hipptTraceCamera",
 )
 
 
@@ -189,6 +192,11 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     sig("hipptBvh4QCopy", None, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32))
     sig("hipptBvh4QNodeCount", c_int, ctypes.c_void_p)
     sig("hipptChainAudit", c_int, p_uint, c_int)
+    # ray queries: the buffers as addresses (host arrays or device memory, by the flags)
+    c_void_p = ctypes.c_void_p
+    sig("hipptTraceRays", c_bool, c_void_p, ctypes.c_longlong, c_int, c_void_p, c_void_p, pp_char)
+    sig("hipptOccluded", c_bool, c_void_p, ctypes.c_longlong, c_int, c_void_p, pp_char)
+    sig("hipptTraceCamera", c_bool, c_int, c_int, c_void_p, c_void_p, pp_char)
     _lib = lib
     return lib
 
@@ -203,6 +211,38 @@ def _ptr(a: np.ndarray, ct):
 
 def _d3(v) -> ctypes.Array:
     return (ctypes.c_double * 3)(*[float(x) for x in v])
+
+
+def _is_tensor(a) -> bool:
+    """A torch tensor, without importing torch for callers that never pass one."""
+    return type(a).__module__.split(".")[0] == "torch" and hasattr(a, "data_ptr")
+
+
+def _query_rays(rays):
+    """Validates a ray batch before any call: (N, 8) float32, C-contiguous; a numpy array (a CPU tensor
+    is taken as one) or a tensor on the ROCm device.  Returns (array or tensor, on_device)."""
+    if _is_tensor(rays):
+        import torch
+        if rays.dtype != torch.float32:
+            raise HipptError(f"rays must be float32, not {rays.dtype}")
+        if rays.dim() != 2 or rays.shape[1] != 8:
+            raise HipptError(f"rays must have shape (N, 8), not {tuple(rays.shape)}")
+        if not rays.is_contiguous():
+            raise HipptError("rays must be contiguous")
+        if rays.device.type == "cpu":
+            return rays.numpy(), False
+        if rays.device.type != "cuda":
+            raise HipptError(f"rays on an unsupported device {rays.device}")
+        return rays, True
+    if not isinstance(rays, np.ndarray):
+        raise HipptError("rays must be a numpy array or a torch tensor")
+    if rays.dtype != np.float32:
+        raise HipptError(f"rays must be float32, not {rays.dtype}")
+    if rays.ndim != 2 or rays.shape[1] != 8:
+        raise HipptError(f"rays must have shape (N, 8), not {rays.shape}")
+    if not rays.flags["C_CONTIGUOUS"]:
+        raise HipptError("rays must be contiguous")
+    return rays, False
 
 
 def read_mesh(path: str):
@@ -464,6 +504,66 @@ class PathTracer:
 
     def resetStats(self) -> None:  # noqa: N802
         self._lib.hipptResetStats()
+
+    # --- ray queries (include/hippt.h "ray queries") ----------------------------------------------------
+    def traceRays(self, rays):  # noqa: N802
+        """Closest hit of each ray (origin xyz, tmin, direction xyz, tmax): (t float32 (N,), prim int32
+        (N,)); a miss is (inf, -1).  numpy in, numpy out; a tensor on the ROCm device in, tensors on
+        that device out (torch's current stream is synchronised first; nothing is staged).  Device
+        tensors need torch and libhippt.so on one HIP runtime: import torch before the first hippt
+        call, so that the library binds to the runtime torch has loaded; otherwise the library does not
+        know torch's allocations and reports them as not device memory."""
+        r, dev = _query_rays(rays)
+        n = int(r.shape[0])
+        e = ctypes.c_char_p()
+        if dev:
+            import torch
+            t = torch.empty(n, dtype=torch.float32, device=r.device)
+            prim = torch.empty(n, dtype=torch.int32, device=r.device)
+            torch.cuda.current_stream(r.device).synchronize()
+            ok = self._lib.hipptTraceRays(r.data_ptr(), n, RAYS_DEVICE, t.data_ptr(), prim.data_ptr(), ctypes.byref(e))
+        else:
+            t = np.empty(n, np.float32)
+            prim = np.empty(n, np.int32)
+            ok = self._lib.hipptTraceRays(r.ctypes.data, n, 0, t.ctypes.data, prim.ctypes.data, ctypes.byref(e))
+        if not ok:
+            raise HipptError(_err(e, "ray query failed"))
+        return t, prim
+
+    def occluded(self, rays):
+        """1 where any primitive is hit within [tmin, tmax), else 0: uint8 (N,), numpy or tensor as the rays."""
+        r, dev = _query_rays(rays)
+        n = int(r.shape[0])
+        e = ctypes.c_char_p()
+        if dev:
+            import torch
+            occ = torch.empty(n, dtype=torch.uint8, device=r.device)
+            torch.cuda.current_stream(r.device).synchronize()
+            ok = self._lib.hipptOccluded(r.data_ptr(), n, RAYS_DEVICE, occ.data_ptr(), ctypes.byref(e))
+        else:
+            occ = np.empty(n, np.uint8)
+            ok = self._lib.hipptOccluded(r.ctypes.data, n, 0, occ.ctypes.data, ctypes.byref(e))
+        if not ok:
+            raise HipptError(_err(e, "occlusion query failed"))
+        return occ
+
+    def traceCamera(self, frame: int = 0):  # noqa: N802
+        """First hit of sample `frame`'s camera ray of every pixel: (t float32 (H, W), prim int32 (H, W)),
+        row 0 = v = 0; a miss is (inf, -1)."""
+        t = np.empty((self._height, self._width), np.float32)
+        prim = np.empty((self._height, self._width), np.int32)
+        e = ctypes.c_char_p()
+        if not self._lib.hipptTraceCamera(int(frame), 0, t.ctypes.data, prim.ctypes.data, ctypes.byref(e)):
+            raise HipptError(_err(e, "camera query failed"))
+        return t, prim
+
+    def pick(self, x: int, y: int, frame: int = 0):
+        """(prim, t) under pixel (x, y) (row y = 0 is v = 0) for sample `frame`'s camera ray; (-1, inf)
+        over the sky."""
+        if not (0 <= int(x) < self._width and 0 <= int(y) < self._height):
+            raise HipptError(f"pixel ({x}, {y}) outside the {self._width}x{self._height} image")
+        t, prim = self.traceCamera(frame)
+        return int(prim[int(y), int(x)]), float(t[int(y), int(x)])
 
 
 AUDIT_MAGIC = 0xC4A1D17

@@ -93,6 +93,34 @@ const unsigned int *HipPathTracer::latestFrame(int *frames) {
     return pixels;
 }
 
+bool HipPathTracer::traceRays(const std::vector<float> &rays, std::vector<float> &t, std::vector<int> &prim) {
+    if (rays.size() % 8 != 0) {
+        m_lastError = "rays need 8 floats each";
+        return false;
+    }
+    const long long n = (long long)(rays.size() / 8);
+    t.resize(size_t(n));
+    prim.resize(size_t(n));
+    const char *err = nullptr;
+    if (n > 0 && !hipptTraceRays(rays.data(), n, 0, t.data(), prim.data(), &err)) return fail(err, "ray query failed");
+    return true;
+}
+
+bool HipPathTracer::pick(int x, int y, int *prim, float *t, int frame) {
+    if (x < 0 || y < 0 || x >= m_width || y >= m_height || !prim) {
+        m_lastError = "pick outside the image";
+        return false;
+    }
+    std::vector<float> ts(size_t(m_width) * size_t(m_height));
+    std::vector<int> prims(ts.size());
+    const char *err = nullptr;
+    if (!hipptTraceCamera(frame, 0, ts.data(), prims.data(), &err)) return fail(err, "camera query failed");
+    const size_t i = size_t(y) * size_t(m_width) + size_t(x);
+    *prim = prims[i];
+    if (t) *t = ts[i];
+    return true;
+}
+
 bool HipPathTracer::setOption(int key, long long value) {
     if (!hipptSetOption(key, value)) {
         m_lastError = "invalid option";

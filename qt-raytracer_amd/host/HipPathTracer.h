@@ -44,6 +44,13 @@ public:
     bool presentFrames(int samplesPerFrame, int maxDepth);
     const unsigned int *latestFrame(int *frames);
     bool setOption(int key, long long value);
+    // Ray queries over the uploaded scene (include/hippt.h "ray queries"): rays = 8 floats each (origin
+    // xyz, tmin, direction xyz, tmax); t and prim get one entry per ray (+inf, -1 on a miss).
+    bool traceRays(const std::vector<float> &rays, std::vector<float> &t, std::vector<int> &prim);
+    // The primitive under pixel (x, y) and its distance, for sample `frame`'s camera ray; y counts rows
+    // as hostPixels() does (row 0 = v = 0, the bottom row: a viewport click at yTop is height - 1 - yTop).
+    // *prim = -1 and *t = +inf over the sky.
+    bool pick(int x, int y, int *prim, float *t = nullptr, int frame = 0);
 
 private:
     bool fail(const char *err, const char *fallback);

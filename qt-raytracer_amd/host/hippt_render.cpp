@@ -4,7 +4,7 @@
 //
 //   hippt_render [--backend cuda|vulkan|gl] [--mesh FILE.obj|.ply] [--albedo r,g,b[;r,g,b...]]
 //                [--width W] [--height H] [--spp N] [--depth D] [--per-frame] [--present]
-//                [--out FILE] [--ppm FILE.ppm]
+//                [--out FILE] [--ppm FILE.ppm] [--pick X,Y]
 //
 // --backend cuda (default): HipPathTracer, the CudaPathTracer interface.  Without --mesh: the
 // reference kernel's built-in 4-sphere scene, one renderFrame per frame (the CUDA backend's
@@ -15,11 +15,15 @@
 // branch, RayTracerFboItem.cpp:576-600).  --backend gl: HipGpuPathTracer, initialize + resize,
 // then renderFrame(N, depth) once (or per frame with --per-frame), as the GL branch calls it.
 // --out writes the frame words (cuda: ARGB; vulkan / gl: RGBA8; row 0 = bottom, little endian),
-// --ppm an image (top row first).  Prints one JSON line.
+// --ppm an image (top row first).  --pick X,Y (cuda backend, with --mesh): after the render,
+// HipPathTracer::pick at that pixel (row 0 = bottom) and the pixel centre's pinhole ray through
+// HipPathTracer::traceRays, reported as "pick": {x, y, prim, t_bits, ray_prim, ray_t_bits}.
+// Prints one JSON line.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <sstream>
 #include <string>
 #include <vector>
@@ -33,7 +37,7 @@ int usage() {
     std::fprintf(stderr,
                  "usage: hippt_render [--backend cuda|vulkan|gl] [--mesh FILE] [--albedo r,g,b[;...]] [--width W]\n"
                  "                    [--height H] [--spp N] [--depth D] [--per-frame] [--present] [--out FILE]\n"
-                 "                    [--ppm FILE.ppm]\n");
+                 "                    [--ppm FILE.ppm] [--pick X,Y]\n");
     return 2;
 }
 
@@ -54,7 +58,7 @@ std::vector<float> parse_floats(const std::string &s) {
 }  // namespace
 
 int main(int argc, char **argv) {
-    std::string mesh, out, ppm, albedoArg, backend = "cuda";
+    std::string mesh, out, ppm, albedoArg, pickArg, backend = "cuda";
     int width = 320, height = 180, spp = 16, depth = 8;
     bool perFrame = false, present = false;
     for (int i = 1; i < argc; ++i) {
@@ -73,6 +77,7 @@ int main(int argc, char **argv) {
         else if (a == "--depth") depth = std::atoi(v);
         else if (a == "--out") out = v;
         else if (a == "--ppm") ppm = v;
+        else if (a == "--pick") pickArg = v;
         else return usage();
     }
     if (backend != "cuda" && backend != "vulkan" && backend != "gl") return usage();
@@ -188,9 +193,44 @@ int main(int argc, char **argv) {
             }
         std::fclose(f);
     }
+    std::string pickJson;
+    if (!pickArg.empty()) {
+        const std::vector<float> xy = parse_floats(pickArg);
+        int prim = -1;
+        float t = 0.0f;
+        if (xy.size() != 2 || !tracer.pick(int(xy[0]), int(xy[1]), &prim, &t)) {
+            std::fprintf(stderr, "hippt_render: pick: %s\n", tracer.lastError().c_str());
+            return 1;
+        }
+        // the pinhole ray through the pixel's centre, as a host would build one
+        hipptCamera cam;
+        const double from[3] = {278, 278, -800}, at[3] = {278, 278, 0}, up[3] = {0, 1, 0};
+        hipptBuildCamera(from, at, up, 40.0, double(width) / double(height), 0.0, 10.0, &cam);
+        const float s = (xy[0] + 0.5f) / float(std::max(1, width - 1)), v = (xy[1] + 0.5f) / float(std::max(1, height - 1));
+        std::vector<float> ray(8), ts;
+        std::vector<int> prims;
+        for (int k = 0; k < 3; ++k) {
+            ray[size_t(k)] = cam.origin[k];
+            ray[size_t(4 + k)] = cam.llc[k] + s * cam.horizontal[k] + v * cam.vertical[k] - cam.origin[k];
+        }
+        ray[3] = 0.001f;
+        ray[7] = std::numeric_limits<float>::infinity();
+        if (!tracer.traceRays(ray, ts, prims)) {
+            std::fprintf(stderr, "hippt_render: traceRays: %s\n", tracer.lastError().c_str());
+            return 1;
+        }
+        unsigned tb, rb;
+        std::memcpy(&tb, &t, 4);
+        std::memcpy(&rb, &ts[0], 4);
+        char buf[200];
+        std::snprintf(buf, sizeof buf, ", \"pick\": {\"x\": %d, \"y\": %d, \"prim\": %d, \"t_bits\": %u, \"ray_prim\": %d, "
+                      "\"ray_t_bits\": %u}", int(xy[0]), int(xy[1]), prim, tb, prims[0], rb);
+        pickJson = buf;
+    }
     hipptGetStats(&st);
     std::printf("{\"backend\": \"cuda\", \"frames\": %d, \"seconds\": %.6f, \"segments\": %llu, "
-                "\"pixel_samples\": %llu}\n",
-                tracer.frameIndex(), secs, (unsigned long long)st.segments, (unsigned long long)st.pixelSamples);
+                "\"pixel_samples\": %llu%s}\n",
+                tracer.frameIndex(), secs, (unsigned long long)st.segments, (unsigned long long)st.pixelSamples,
+                pickJson.c_str());
     return 0;
 }
