@@ -115,6 +115,36 @@ void hipptFreeMesh(hipptMesh *mesh);
 /* Optional: replace the camera by a prebuilt one (used as-is, whatever the aspect). */
 bool hipptSetCamera(const hipptCamera *camera, const char **errorMessage);
 
+/* ---- vertex updates (animated or edited meshes) ------------------------------------------------ */
+/* New triangle vertices for the uploaded scene, in place: verts = numTris*9 floats in the upload's
+ * triangle order, numTris the uploaded scene's triangle count.  Spheres, materials, primitive ids,
+ * camera and the BVH's topology stay as uploaded; the primitive records and the boxes of both float
+ * trees are recomputed on every device by the builder's own rule (a refit, bit-identical to the
+ * host's hipptBvhRefit), so every result is the one a fresh hipptUploadScene of these vertices gives:
+ * the BVH only culls.  A refit keeps the topology, so the tree's quality decays under large
+ * deformation; hipptUploadScene is the rebuild.
+ * Stream order, no drain: every render and ray query enqueued later sees the new triangles, everything
+ * enqueued earlier the old ones.  The call does not wait for queued work and reallocates nothing.
+ * Host memory is copied into library-owned staging before the call returns.  With HIPPT_VERTS_DEVICE
+ * (memory of one of the devices of hipptSetDevices; after an Init) the call returns once the work is
+ * enqueued, and the caller keeps the memory unchanged until the next hipptSynchronize or blocking
+ * render.  Before an Init, host vertices update the host copy of the scene only.
+ * After an update the 8-bit, half-precision and hybrid trees (HIPPT_OPT_BVH_QUANT) are stale: every
+ * path reads the float nodes until the next hipptUploadScene (same results).
+ * A non-finite coordinate in host memory is rejected and leaves the scene unchanged; in device
+ * memory the triangle becomes a record no ray hits, is kept out of every box, and is counted:
+ * hipptGetOption(HIPPT_INFO_UPDATE_DROPPED) gives the last update's count (synchronises). */
+enum { HIPPT_VERTS_DEVICE = 1 };   /* flags: verts is device memory of one of the contexts' devices */
+bool hipptUpdateVertices(const float *verts, int numTris, int flags, const char **errorMessage);
+
+/* Inspection aid (in the spirit of hipptChainAudit): copies context 0's device buffer (device layouts:
+ * 2-wide nodes of 16 words as hipptBvhCopy; 4-wide float nodes of 32 words as hipptBvh4Copy except
+ * that interior child codes are byte offsets, node * 128; primitive records of 12 words in BVH leaf
+ * order, the primitive id in word 9, 1 in word 10 for a sphere; shading records of 4 words: normal and
+ * material word) into dst after the queued work; dst null: returns the bytes needed.  -1 on error. */
+enum { HIPPT_SCENE_NODES2 = 0, HIPPT_SCENE_NODES4 = 1, HIPPT_SCENE_PRIMS = 2, HIPPT_SCENE_SHADE = 3 };
+long long hipptSceneDownload(int what, void *dst, long long bytes, const char **errorMessage);
+
 /* ---- devices and row bands ------------------------------------------------------- */
 int hipptDeviceCount(void);
 /* Render on these devices (one context per device, contiguous row bands); takes effect
@@ -324,7 +354,9 @@ enum { HIPPT_PIXEL_ARGB = 0, HIPPT_PIXEL_RGBA8 = 1 };
  * persistent-grid blocks per CU, work items per claim (HIPPT_OPT_CHUNK as applied), batches a launch
  * may trace (HIPPT_OPT_CHAIN as applied: 0 = the batch was not chained). */
 enum { HIPPT_INFO_LDS_TOP_BYTES = 100, HIPPT_INFO_BLOCKS_PER_CU = 101, HIPPT_INFO_CHUNK = 102,
-       HIPPT_INFO_CHAIN_CAP = 103 };
+       HIPPT_INFO_CHAIN_CAP = 103,
+       HIPPT_INFO_UPDATE_DROPPED = 104 /* triangles the last device-memory hipptUpdateVertices dropped
+                                          for a non-finite coordinate; reading it synchronises */ };
 bool hipptSetOption(int key, long long value);
 long long hipptGetOption(int key);
 /* BVH width (2 or 4) the last mesh render traversed (0 before any): what nodeVisits count. */
@@ -342,6 +374,12 @@ int hipptBvhDepth(const hipptBvh *bvh);
 /* nodes: NodeCount*16 words; triOrder: numTris ints (leaf order -> original triangle index). */
 void hipptBvhCopy(const hipptBvh *bvh, uint32_t *nodes, int *triOrder);
 void hipptBvhFree(hipptBvh *bvh);
+/* New boxes for the same topology (what hipptUpdateVertices does to the uploaded scene): every used
+ * slot's box of the 2-wide, 4-wide and 8-bit trees becomes the union of the triangle boxes below it,
+ * each side moved out once by the pad of the new vertices and extentHint, as a build pads; codes and
+ * triangle order stay.  numTris must be the build's; a non-finite coordinate is an error and leaves
+ * the trees unchanged. */
+bool hipptBvhRefit(hipptBvh *bvh, const float *verts, int numTris, float extentHint, const char **errorMessage);
 /* The 4-wide tree the megakernel traverses (HIPPT_OPT_BVH_WIDTH 4), collapsed from the 2-wide
  * one (same leaves and triangle order).  Node = 32 words: lo.x[4] hi.x[4] lo.y[4] hi.y[4]
  * lo.z[4] hi.z[4] (floats), child[4] (codes as above; an unused slot holds an empty leaf under

@@ -607,6 +607,114 @@ int order_bvh4_top(Bvh4 &b, int topNodes) {
     return int(bfs.size());
 }
 
+namespace {
+
+// Nodes by depth, deepest first (children are node indices).
+void level_lists(const uint32_t *nodes, size_t numNodes, int width, std::vector<int> &list, std::vector<int> &level) {
+    const int nw = width == 2 ? kNodeWords : kNode4Words;
+    list.clear();
+    level.clear();
+    if (numNodes == 0) {
+        level.push_back(0);
+        return;
+    }
+    std::vector<int> bfs, start;  // breadth-first: depth d is bfs[start[d] .. start[d + 1])
+    bfs.reserve(numNodes);
+    bfs.push_back(0);
+    start.push_back(0);
+    for (size_t h = 0; h < bfs.size();) {
+        const size_t end = bfs.size();
+        for (; h < end; ++h)
+            for (int i = 0; i < width; ++i) {
+                const int32_t c = int32_t(nodes[size_t(bfs[h]) * nw + size_t(node_code_word(width, i))]);
+                if (c >= 0) bfs.push_back(c);
+            }
+        start.push_back(int(end));
+    }
+    list.reserve(bfs.size());
+    for (size_t d = start.size() - 1; d-- > 0;) {
+        level.push_back(int(list.size()));
+        list.insert(list.end(), bfs.begin() + start[d], bfs.begin() + start[d + 1]);
+    }
+    level.push_back(int(list.size()));
+}
+
+// One tree's refit over its level lists.  pbox: unpadded primitive boxes in LEAF order (6 floats).
+void refit_tree(uint32_t *nodes, int width, const std::vector<int> &list, const float *pbox, float pad,
+                std::vector<float> &ubox) {
+    const int nw = width == 2 ? kNodeWords : kNode4Words;
+    for (const int node : list) {
+        uint32_t *w = nodes + size_t(node) * nw;
+        for (int i = 0; i < width; ++i) {
+            const int32_t code = int32_t(w[node_code_word(width, i)]);
+            Box b;
+            if (code < 0) {
+                const int first = (~code) >> 4, count = (~code) & 15;
+                for (int p = first; p < first + count; ++p) b.grow(pbox + 6 * size_t(p), pbox + 6 * size_t(p) + 3);
+                if (count == 0) {  // an unused slot: left alone, and nothing for the parent's union
+                    std::memcpy(&ubox[(size_t(node) * width + i) * 6], &b, 6 * sizeof(float));
+                    continue;
+                }
+            } else {
+                const float *u = &ubox[size_t(code) * width * 6];
+                for (int c = 0; c < width; ++c) b.grow(u + 6 * c, u + 6 * c + 3);
+            }
+            std::memcpy(&ubox[(size_t(node) * width + i) * 6], &b, 6 * sizeof(float));
+            const bool have = b.lo[0] <= b.hi[0];
+            for (int a = 0; a < 3; ++a) {
+                const float lo = have ? b.lo[a] - pad : kFarPoint[a], hi = have ? b.hi[a] + pad : kFarPoint[a];
+                std::memcpy(&w[node_lo_word(width, i, a)], &lo, 4);
+                std::memcpy(&w[node_hi_word(width, i, a)], &hi, 4);
+            }
+        }
+    }
+}
+
+}  // namespace
+
+void refit_plan(const Bvh &bvh2, const Bvh4 &bvh4, RefitPlan &out) {
+    level_lists(bvh2.nodes.data(), bvh2.nodes.size() / kNodeWords, 2, out.list2, out.level2);
+    level_lists(bvh4.nodes.data(), bvh4.nodes.size() / kNode4Words, 4, out.list4, out.level4);
+}
+
+bool refit_bvh(Bvh &bvh2, Bvh4 &bvh4, const float *boxes, int numPrims, float extentHint, std::string &err,
+               const RefitPlan *plan) {
+    if (!boxes) {
+        err = "null box pointer";
+        return false;
+    }
+    if (numPrims <= 0 || size_t(numPrims) != bvh2.order.size()) {
+        err = "refit: primitive count differs from the build's";
+        return false;
+    }
+    float maxabs = std::fabs(extentHint);
+    std::vector<float> pbox(size_t(numPrims) * 6);
+    for (int k = 0; k < numPrims; ++k) {
+        const float *bx = boxes + 6 * size_t(bvh2.order[size_t(k)]);
+        std::memcpy(&pbox[6 * size_t(k)], bx, 6 * sizeof(float));
+        if (bx[0] == INFINITY && bx[1] == INFINITY && bx[2] == INFINITY && bx[3] == -INFINITY && bx[4] == -INFINITY &&
+            bx[5] == -INFINITY)
+            continue;  // no primitive
+        for (int a = 0; a < 6; ++a) {
+            if (!std::isfinite(bx[a])) {
+                err = "non-finite primitive coordinate";
+                return false;
+            }
+            maxabs = std::max(maxabs, std::fabs(bx[a]));
+        }
+    }
+    const float pad = std::max(maxabs, 1e-3f) * (1.0f / 65536.0f);
+    RefitPlan own;
+    if (!plan) {
+        refit_plan(bvh2, bvh4, own);
+        plan = &own;
+    }
+    std::vector<float> ubox(std::max(bvh2.nodes.size() / kNodeWords * 12, bvh4.nodes.size() / kNode4Words * 24));
+    refit_tree(bvh2.nodes.data(), 2, plan->list2, pbox.data(), pad, ubox);
+    refit_tree(bvh4.nodes.data(), 4, plan->list4, pbox.data(), pad, ubox);
+    return true;
+}
+
 bool quantize_bvh4(const Bvh4 &in, std::vector<uint32_t> &out) {
     const size_t n = in.nodes.size() / kNode4Words;
     out.assign(n * kNode4QWords, 0u);

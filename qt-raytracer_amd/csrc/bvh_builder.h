@@ -78,6 +78,36 @@ void collapse_bvh4(const Bvh &bvh2, Bvh4 &out, const BvhParams &params = BvhPara
 // global memory.  Returns the number of nodes ordered breadth-first.
 int order_bvh4_top(Bvh4 &b, int topNodes);
 
+// Refit: new boxes for an unchanged topology (animated or edited vertices; include/hippt.h
+// hipptUpdateVertices, hipptBvhRefit).  What a refit needs of the topology: each tree's nodes by depth,
+// deepest level first, so that a level's interior children are refitted before it (on the device one
+// launch per level: the kernel boundary is the hand-off).  Level k of a tree is
+// list[level[k] .. level[k + 1]).
+struct RefitPlan {
+    std::vector<int> list2, level2;  // the 2-wide tree
+    std::vector<int> list4, level4;  // the 4-wide tree
+};
+void refit_plan(const Bvh &bvh2, const Bvh4 &bvh4, RefitPlan &out);
+// Child-slot words of both node layouts (slot = child index, a = axis), shared with the device refit.
+constexpr int node_lo_word(int width, int slot, int a) { return width == 2 ? 6 * slot + a : 8 * a + slot; }
+constexpr int node_hi_word(int width, int slot, int a) { return width == 2 ? 6 * slot + 3 + a : 8 * a + 4 + slot; }
+constexpr int node_code_word(int width, int slot) { return (width == 2 ? 12 : 24) + slot; }
+// The far point an unused 4-wide slot holds (collapse_bvh4), also written for a slot whose subtree
+// has no box left.
+constexpr float kFarPoint[3] = {3.0e38f, -1.0e20f, 7.0e33f};
+// Rewrites every used slot's box of both trees (bvh4 with node-index codes) by the builder's rule:
+// the float min/max union of the primitive boxes of the slot's subtree, each side then moved out
+// ONCE by pad = max(maxabs, 1e-3f) * 2^-16, maxabs over the new boxes and extentHint
+// (build_bvh_boxes).  Padded child boxes are never unioned: the unpadded boxes are kept on the side.
+// Codes, order and slots holding an empty leaf are left alone, so refitting to the build's own boxes
+// gives the build's bytes back.  boxes = numPrims * 6 floats by primitive index, as build_bvh_boxes
+// takes them; a box with lo = +inf, hi = -inf is "no primitive" (a dropped triangle): it enters no
+// union and not maxabs, and a slot left without a box gets kFarPoint on both sides.  Any other
+// non-finite value, or a count other than the build's, is an error and leaves the trees unchanged.
+// plan: refit_plan of the same trees (built here when null).
+bool refit_bvh(Bvh &bvh2, Bvh4 &bvh4, const float *boxes, int numPrims, float extentHint, std::string &err,
+               const RefitPlan *plan = nullptr);
+
 // The 4-wide tree with 8-bit child boxes (Ylitie et al. 2017, "Efficient incoherent ray traversal
 // on GPUs through compressed wide BVHs", reduced to 4 children): 64-byte nodes, same node
 // indices, child codes and primitive order as Bvh4.  Words:

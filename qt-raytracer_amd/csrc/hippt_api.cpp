@@ -22,6 +22,7 @@
 #include <exception>
 #include <memory>
 #include <mutex>
+#include <stdexcept>
 #include <string>
 #include <system_error>
 #include <thread>
@@ -32,6 +33,7 @@
 #include "mesh_io.h"
 #include "hippt_device.h"
 #include "hippt_query.h"
+#include "hippt_refit.h"
 #include "hippt_wavefront.h"
 
 struct hipptBvh {
@@ -143,6 +145,13 @@ struct Ctx {
     float4 *nodes4f = nullptr; // the 4-wide BVH with half-precision planes (half_bvh4; on use)
     int halfVersion = -1;      // scene version of nodes4f
     int hybridTop = -1;
+    // Vertex updates (hipptUpdateVertices, hippt_refit.h): the refit's own buffers for the uploaded
+    // scene, allocated at the context's first update and freed with the scene buffers
+    float *rfVerts = nullptr;   // the update's vertices (host memory, or memory of another device)
+    float *rfBoxes = nullptr;   // pbox, ubox2, ubox4
+    int *rfLists = nullptr;     // RefitPlan list2, list4
+    unsigned *rfWords = nullptr;
+    bool rfUpdated = false;     // rfWords hold an update's counts
     // the queues' pixel-run order of this context's rows (HIPPT_OPT_ITEM_ORDER): run costs per key,
     // device item tables per batch size for those costs
     OrderKey orderKey;            // of runCosts
@@ -190,6 +199,8 @@ struct Ctx {
         hippt::MeshParams key{};  // what every batch of the run shares (chain_same)
         long long blocks = 0;
         unsigned lastOwn = 0;     // the batch of the run's last enqueued launch
+        unsigned geomRev = 0;     // SceneHost::geomRev of the run's batches (MeshParams' pointers do not
+                                  // change across hipptUpdateVertices)
         // batches held for one group launch while the run's last launch has not started (chain_batch):
         // the first one's parameters and their count; flush_chain launches them if the run ends first
         unsigned pendN = 0;
@@ -252,6 +263,14 @@ struct SceneHost {
     double vfov = 90, aperture = 0, focus = 1;
     bool rawCamera = false;
     CameraF cam{};
+    // hipptUpdateVertices: the 2-wide tree with its primitive order, both trees' level lists, what the
+    // pad's maxabs starts from (the upload's extent hint and the spheres' boxes, which no update
+    // changes), and the number of updates (a chained run's key)
+    hippt::Bvh bvh2;
+    hippt::RefitPlan plan;
+    int numTriangles = 0;
+    float extent = 0.0f, padSeed = 0.0f;
+    unsigned geomRev = 0;
 };
 
 struct State {
@@ -308,6 +327,20 @@ struct State {
         size_t bytes;
     };
     std::vector<SpareBuf> spare;
+    // hipptUpdateVertices: two pinned staging arrays of the scene's triangle vertices, used in turn, so
+    // that an update does not wait for the copies of the one before it (only for those of the one
+    // before that), and the events of the copies still reading or writing each.  hostStale: the newest
+    // update's vertices (stage[staleBuf], complete once staleEv has passed; null: already) are not
+    // yet in SceneHost; settle_scene brings them in before anything on the host reads it.
+    struct Update {
+        float *stage[2] = {nullptr, nullptr};
+        size_t floats = 0;
+        int next = 0;
+        std::vector<std::pair<int, hipEvent_t>> busy[2];  // (device, event)
+        bool hostStale = false;
+        int staleBuf = 0;
+        hipEvent_t staleEv = nullptr;  // one of busy[staleBuf]
+    } upd;
     unsigned activeTopBytes = 0;  // of the last mesh render (hipptGetOption HIPPT_INFO_*)
     int activeBlocksPerCu = 0;
     int activeChunk = 0;     // the last megakernel batch's claim size
@@ -497,6 +530,14 @@ void free_scene_buffers(Ctx &c) {
     (void)hipFree(c.nodes4h);
     (void)hipFree(c.nodes4f);
     c.nodes = c.tris = c.shade = c.mats = c.nodes4 = c.nodes4q = c.nodes4h = c.nodes4f = nullptr;
+    (void)hipFree(c.rfVerts);
+    (void)hipFree(c.rfBoxes);
+    (void)hipFree(c.rfLists);
+    (void)hipFree(c.rfWords);
+    c.rfVerts = c.rfBoxes = nullptr;
+    c.rfLists = nullptr;
+    c.rfWords = nullptr;
+    c.rfUpdated = false;
     c.halfVersion = -1;
     c.hybridTop = -1;
     drop_order(c);
@@ -504,6 +545,130 @@ void free_scene_buffers(Ctx &c) {
 }
 
 void harvest_audit(Ctx &c);
+
+// Waits for the copies that still read or write staging array b (State::Update) and forgets them.
+void stage_wait(int b) {
+    State::Update &u = S().upd;
+    for (auto &de : u.busy[b]) {
+        (void)hipSetDevice(de.first);
+        (void)hipEventSynchronize(de.second);
+        (void)hipEventDestroy(de.second);
+        if (u.staleEv == de.second) u.staleEv = nullptr;
+    }
+    u.busy[b].clear();
+}
+
+// A triangle's primitive record (3 words of SceneHost::tris) and shading normal, as the oracle's
+// po_tri_setup: e1 = v1-v0, e2 = v2-v0, n = cross/len; the zero record when !(len > 0).  The material
+// word (shade.w) is the caller's.  hippt_refit.hip's primitive pass restates this operation by operation.
+void tri_record(const float *v, int id, float4 *rec, float4 &shade) {
+    float e1[3] = {v[3] - v[0], v[4] - v[1], v[5] - v[2]};
+    float e2[3] = {v[6] - v[0], v[7] - v[1], v[8] - v[2]};
+    float cr[3], n[3];
+    fcross(e1, e2, cr);
+    const float len = std::sqrt(fdot(cr, cr));
+    if (!(len > 0.0f)) {
+        e1[0] = e1[1] = e1[2] = 0.0f;
+        e2[0] = e2[1] = e2[2] = 0.0f;
+        n[0] = n[1] = n[2] = 0.0f;
+    } else {
+        const float inv = 1.0f / len;
+        for (int a = 0; a < 3; ++a) n[a] = cr[a] * inv;
+    }
+    rec[0] = float4{v[0], v[1], v[2], e1[0]};
+    rec[1] = float4{e1[1], e1[2], e2[0], e2[1]};
+    rec[2] = float4{e2[2], as_float(id), 0.0f, 0.0f};
+    shade = float4{n[0], n[1], n[2], shade.w};
+}
+
+// Primitive boxes as build_bvh_boxes takes them: triangles from verts, then the spheres.
+void triangle_boxes(const float *verts, int numTris, float *boxes) {
+    for (int i = 0; i < numTris; ++i) {
+        const float *v = verts + 9 * size_t(i);
+        float *bx = boxes + 6 * size_t(i);
+        for (int a = 0; a < 3; ++a) {
+            bx[a] = std::min(v[a], std::min(v[3 + a], v[6 + a]));
+            bx[3 + a] = std::max(v[a], std::max(v[3 + a], v[6 + a]));
+        }
+    }
+}
+void sphere_box(const float *q, float *bx) {
+    // slack for the FP32 root's error near the box faces (pt_oracle.c po_scene_create2)
+    const float r = std::fabs(q[3]) * (1.0f + 1.0f / 4096.0f);
+    for (int a = 0; a < 3; ++a) {
+        bx[a] = q[a] - r;
+        bx[3 + a] = q[a] + r;
+    }
+}
+
+// SceneHost refitted to `verts` (numTriangles * 9 floats) as the device refit does it: a triangle with
+// a non-finite coordinate becomes the zero record without a box (the host-memory path of
+// hipptUpdateVertices has rejected those before).
+void refit_scene_host(SceneHost &sc, const float *verts) {
+    const int numPrims = sc.numTris, nt = sc.numTriangles;
+    std::vector<float> boxes(size_t(numPrims) * 6);
+    triangle_boxes(verts, nt, boxes.data());
+    std::vector<char> dropped(size_t(nt), 0);
+    for (int i = 0; i < nt; ++i) {
+        bool finite = true;
+        for (int j = 0; j < 9; ++j) finite = finite && std::isfinite(verts[9 * size_t(i) + j]);
+        if (finite) continue;
+        dropped[size_t(i)] = 1;
+        for (int a = 0; a < 3; ++a) {
+            boxes[6 * size_t(i) + a] = INFINITY;
+            boxes[6 * size_t(i) + 3 + a] = -INFINITY;
+        }
+    }
+    for (int k = 0; k < numPrims; ++k) {
+        const int id = sc.bvh2.order[size_t(k)];
+        float4 *rec = &sc.tris[3 * size_t(k)];
+        if (id >= nt) {
+            const float q[4] = {rec[0].x, rec[0].y, rec[0].z, rec[0].w};
+            sphere_box(q, &boxes[6 * size_t(id)]);
+        } else if (dropped[size_t(id)]) {
+            rec[0] = rec[1] = float4{};
+            rec[2] = float4{0.0f, as_float(id), 0.0f, 0.0f};
+            sc.shade[size_t(k)] = float4{0.0f, 0.0f, 0.0f, sc.shade[size_t(k)].w};
+        } else {
+            tri_record(verts + 9 * size_t(id), id, rec, sc.shade[size_t(k)]);
+        }
+    }
+    std::string msg;
+    if (!hippt::refit_bvh(sc.bvh2, sc.bvh4, boxes.data(), numPrims, sc.extent, msg, &sc.plan))
+        throw std::runtime_error("vertex update: " + msg);  // (sizes and values were checked: not reached)
+    std::memcpy(sc.nodes.data(), sc.bvh2.nodes.data(), sc.bvh2.nodes.size() * sizeof(uint32_t));
+    auto *w4 = reinterpret_cast<uint32_t *>(sc.nodes4.data());
+    for (size_t k = 0; k < size_t(sc.numNodes4); ++k)  // the boxes; the device layout keeps its byte codes
+        std::memcpy(w4 + k * hippt::kNode4Words, &sc.bvh4.nodes[k * hippt::kNode4Words], 24 * sizeof(uint32_t));
+}
+
+// After an update the 8-bit, half and hybrid trees are stale: dropped, so that every path reads the
+// refitted float nodes (the kernels' own fallback for a scene without an 8-bit tree; same results).
+// A fresh hipptUploadScene builds them again.
+void drop_derived_trees(SceneHost &sc) {
+    sc.nodes4q.clear();
+    sc.q4.clear();
+    sc.nodes4f.clear();
+    sc.halfState = -1;
+    sc.hybrid.clear();
+    sc.hybridTop = -1;
+}
+
+// Brings the newest update's vertices into SceneHost before the host reads it (a new context's
+// upload, the run-cost estimate, the wavefront sort's scene box).
+void settle_scene() {
+    State &s = S();
+    State::Update &u = s.upd;
+    if (!u.hostStale) return;
+    if (u.staleEv) {
+        for (auto &de : u.busy[u.staleBuf])
+            if (de.second == u.staleEv) (void)hipSetDevice(de.first);
+        (void)hipEventSynchronize(u.staleEv);  // the device-to-host copy of a HIPPT_VERTS_DEVICE update
+        u.staleEv = nullptr;
+    }
+    u.hostStale = false;
+    refit_scene_host(s.scene, u.stage[u.staleBuf]);
+}
 
 // keep: the big work buffers go to State::spare (a re-initialization) instead of hipFree.
 void destroy_ctx(Ctx &c, bool keep) {
@@ -565,6 +730,16 @@ void destroy_all(bool keep = false) {
         (void)hipFree(t.second);
     }
     s.rngTables.clear();
+    stage_wait(0);  // (the contexts' streams are finished: these return at once)
+    stage_wait(1);
+    if (!keep) {
+        settle_scene();
+        for (float *&p : s.upd.stage) {
+            if (p) (void)hipHostFree(p);
+            p = nullptr;
+        }
+        s.upd.floats = 0;
+    }
     if (s.host) (void)hipHostFree(s.host);
     s.host = nullptr;
     s.hostCount = 0;
@@ -622,6 +797,7 @@ bool harvest_locked(Ctx &c, const char **err) {
 bool ensure_scene(Ctx &c, const char **err) {
     State &s = S();
     if (s.scene.kind != HIPPT_SCENE_MESH || c.sceneVersion == s.scene.version) return true;
+    settle_scene();  // (a vertex update not yet in the host copy)
     if (!launch_held(c, err)) return false;
     HIP_TRY(hipSetDevice(c.device));
     HIP_TRY(hipStreamSynchronize(c.stream));  // queued launches read the old buffers
@@ -691,6 +867,7 @@ bool ensure_order(Ctx &c, const CameraF &cam, int frames, int maxDepth, bool for
             c.costJob.reset();
         } else if (forced) {
             abandon_cost_job(c);  // a stale key's job: not joined on the render path
+            settle_scene();
             hippt::run_costs(s.scene.bvh4, reinterpret_cast<const float *>(s.scene.tris.data()), cam,
                              hippt::RunLayout{unsigned(s.width), unsigned(c.rows), key.tileShift}, s.height, c.y0,
                              c.stride, maxDepth, cost, cost_threads());
@@ -698,6 +875,7 @@ bool ensure_order(Ctx &c, const CameraF &cam, int frames, int maxDepth, bool for
             if (c.costJob && !jobForKey) abandon_cost_job(c);
             if (!c.costJob) {
                 auto job = std::make_shared<CostJob>();
+                settle_scene();
                 job->key = key;
                 job->bvh = s.scene.bvh4;
                 job->tris = s.scene.tris;
@@ -992,6 +1170,7 @@ bool run_wavefront(Ctx &c, hippt::MeshParams p, bool cnt, bool spills, int spill
     W.sortBits = unsigned(s.wfSort > 0 ? s.wfSort : 0);
     if (W.sortBits > 3) {
         // the scene box: the union of the 4-wide root's child boxes (Bvh4 words lo.x[4] hi.x[4] ...)
+        settle_scene();
         const std::vector<uint32_t> &n = s.scene.bvh4.nodes;
         for (int a = 0; a < 3; ++a) {
             float lo = INFINITY, hi = -INFINITY;
@@ -1352,7 +1531,7 @@ void harvest_audit(Ctx &c) {
 bool chain_batch(Ctx &c, hippt::MeshParams &p, long long blocks, const RingPlan &ring, const char **err) {
     Ctx::Chain &ch = c.chain;
     p.comb = hippt::CombineParams{c.accum, c.out, nullptr, p.bandPixels, p.totalItems, 0, p.frames, p.comb.format};
-    bool same = ch.live && blocks == ch.blocks && chain_same(p, ch.key);
+    bool same = ch.live && blocks == ch.blocks && ch.geomRev == S().scene.geomRev && chain_same(p, ch.key);
     if (same && ch.seq == 1) {  // the run's frame pattern: every batch the same frames, or the next ones
         const int d = p.firstFrame - ch.firstFrame;
         if (d == 0 || d == p.frames)
@@ -1379,6 +1558,7 @@ bool chain_batch(Ctx &c, hippt::MeshParams &p, long long blocks, const RingPlan 
         ch.shift = shift;
         ch.cap = cap;
         ch.blocks = blocks;
+        ch.geomRev = S().scene.geomRev;
         p.comb.scratch = c.chainScratch;
         p.comb.firstFrame = p.firstFrame;
         ch.key = p;
@@ -2171,24 +2351,8 @@ extern "C" bool hipptUploadScene(const float *verts, const int *triMaterial, int
     // primitive id p: triangles 0..numTris-1, then spheres (the closest-hit tie order)
     const int numPrims = numTris + numSpheres;
     std::vector<float> boxes(size_t(numPrims) * 6);
-    for (int i = 0; i < numTris; ++i) {
-        const float *v = verts + 9 * size_t(i);
-        float *bx = &boxes[6 * size_t(i)];
-        for (int a = 0; a < 3; ++a) {
-            bx[a] = std::min(v[a], std::min(v[3 + a], v[6 + a]));
-            bx[3 + a] = std::max(v[a], std::max(v[3 + a], v[6 + a]));
-        }
-    }
-    for (int j = 0; j < numSpheres; ++j) {
-        const float *q = spheres + 4 * size_t(j);
-        // slack for the FP32 root's error near the box faces (pt_oracle.c po_scene_create2)
-        const float r = std::fabs(q[3]) * (1.0f + 1.0f / 4096.0f);
-        float *bx = &boxes[6 * size_t(numTris + j)];
-        for (int a = 0; a < 3; ++a) {
-            bx[a] = q[a] - r;
-            bx[3 + a] = q[a] + r;
-        }
-    }
+    triangle_boxes(verts, numTris, boxes.data());
+    for (int j = 0; j < numSpheres; ++j) sphere_box(spheres + 4 * size_t(j), &boxes[6 * size_t(numTris + j)]);
     float extent = 0.0f;
     for (int i = 0; i < 3; ++i) extent = std::max(extent, float(std::fabs(lookfrom[i])));
     hippt::Bvh bvh;
@@ -2259,26 +2423,17 @@ extern "C" bool hipptUploadScene(const float *verts, const int *triMaterial, int
                 float4{q[0], q[1], q[2], as_float(sphereMaterial[id - numTris] | hippt::kShadeSphere)};
             continue;
         }
-        const float *v = verts + 9 * size_t(id);
-        // po_tri_setup (oracle) restated: e1 = v1-v0, e2 = v2-v0, n = cross/len
-        float e1[3] = {v[3] - v[0], v[4] - v[1], v[5] - v[2]};
-        float e2[3] = {v[6] - v[0], v[7] - v[1], v[8] - v[2]};
-        float cr[3], n[3];
-        fcross(e1, e2, cr);
-        const float len = std::sqrt(fdot(cr, cr));
-        if (!(len > 0.0f)) {
-            e1[0] = e1[1] = e1[2] = 0.0f;
-            e2[0] = e2[1] = e2[2] = 0.0f;
-            n[0] = n[1] = n[2] = 0.0f;
-        } else {
-            const float inv = 1.0f / len;
-            for (int a = 0; a < 3; ++a) n[a] = cr[a] * inv;
-        }
-        sc.tris[3 * size_t(k)] = float4{v[0], v[1], v[2], e1[0]};
-        sc.tris[3 * size_t(k) + 1] = float4{e1[1], e1[2], e2[0], e2[1]};
-        sc.tris[3 * size_t(k) + 2] = float4{e2[2], as_float(id), 0.0f, 0.0f};
-        sc.shade[size_t(k)] = float4{n[0], n[1], n[2], as_float(triMaterial[id])};
+        sc.shade[size_t(k)].w = as_float(triMaterial[id]);
+        tri_record(verts + 9 * size_t(id), id, &sc.tris[3 * size_t(k)], sc.shade[size_t(k)]);
     }
+    // what hipptUpdateVertices needs: the level lists and the pad's seed (extent hint and sphere boxes)
+    hippt::refit_plan(bvh, bvh4, sc.plan);
+    sc.numTriangles = numTris;
+    sc.extent = extent;
+    sc.padSeed = std::fabs(extent);
+    for (size_t k = size_t(numTris) * 6; k < boxes.size(); ++k) sc.padSeed = std::max(sc.padSeed, std::fabs(boxes[k]));
+    sc.geomRev = s.scene.geomRev + 1;
+    sc.bvh2 = std::move(bvh);
     sc.mats.assign(size_t(numMaterials) * 2, float4{});
     for (int m = 0; m < numMaterials; ++m) {
         const hipptMaterial &mt = materials[m];
@@ -2288,8 +2443,8 @@ extern "C" bool hipptUploadScene(const float *verts, const int *triMaterial, int
         sc.mats[2 * size_t(m) + 1] = float4{fuzz, mt.ir, 0.0f, 0.0f};
     }
     sc.numTris = numPrims;
-    sc.numNodes = int(bvh.nodes.size() / hippt::kNodeWords);
-    sc.levels = bvh.levels;
+    sc.numNodes = int(sc.bvh2.nodes.size() / hippt::kNodeWords);
+    sc.levels = sc.bvh2.levels;
     sc.full = full;
     for (int i = 0; i < 3; ++i) {
         sc.lookfrom[i] = lookfrom[i];
@@ -2303,6 +2458,7 @@ extern "C" bool hipptUploadScene(const float *verts, const int *triMaterial, int
     sc.kind = HIPPT_SCENE_MESH;
     ++sc.version;
     s.scene = std::move(sc);
+    s.upd.hostStale = false;  // (an update of the replaced scene)
     return true;
 } catch (const std::exception &e) {
     return fail_free(err, e.what());
@@ -2326,6 +2482,192 @@ extern "C" bool hipptUploadMesh(const float *verts, const int *triMaterial, int 
     return fail_free(err, e.what());
 } catch (...) {
     return fail_free(err, "unknown exception");
+}
+
+// ---- vertex updates --------------------------------------------------------------------------------
+namespace {
+
+// The refit's buffers of context c for the uploaded scene (first update of the scene there).
+bool ensure_refit_buffers(Ctx &c, const char **err) {
+    const SceneHost &sc = S().scene;
+    if (c.rfWords) return true;
+    const size_t n2 = size_t(sc.numNodes), n4 = size_t(sc.numNodes4), np = size_t(sc.numTris);
+    HIP_TRY(hipMalloc(&c.rfVerts, std::max<size_t>(1, size_t(sc.numTriangles) * 9) * sizeof(float)));
+    HIP_TRY(hipMalloc(&c.rfBoxes, (np * 6 + n2 * 12 + n4 * 24) * sizeof(float)));
+    HIP_TRY(hipMalloc(&c.rfLists, std::max<size_t>(1, n2 + n4) * sizeof(int)));
+    HIP_TRY(hipMalloc(&c.rfWords, 2 * sizeof(unsigned)));
+    // fresh buffers: the copies need not wait for the launches queued on the context's stream
+    HIP_TRY(hipMemcpy(c.rfLists, sc.plan.list2.data(), sc.plan.list2.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c.rfLists + n2, sc.plan.list4.data(), sc.plan.list4.size() * sizeof(int), hipMemcpyHostToDevice));
+    return true;
+}
+
+bool update_vertices_locked(const float *verts, int numTris, int flags, const char **err) {
+    State &s = S();
+    SceneHost &sc = s.scene;
+    State::Update &u = s.upd;
+    // argument and state checks first: none of them touches the GPU
+    if (s.scene.kind != HIPPT_SCENE_MESH)
+        return fail(err, s.scene.version == 0 ? "vertex update: no mesh scene (hipptUploadMesh or hipptUploadScene first)"
+                                              : "vertex update: the built-in scene is active");
+    if (flags & ~HIPPT_VERTS_DEVICE) return fail(err, "vertex update: unknown flags");
+    if (numTris != sc.numTriangles) return fail(err, "vertex update: numTris differs from the uploaded scene's");
+    if (numTris <= 0) return fail(err, "vertex update: the uploaded scene has no triangles");
+    if (!verts) return fail(err, "vertex update: null vertex pointer");
+    const bool device = (flags & HIPPT_VERTS_DEVICE) != 0;
+    const size_t floats = size_t(numTris) * 9;
+    if (device && (!s.ready || s.ctxs.empty()))
+        return fail(err, "vertex update: HIPPT_VERTS_DEVICE needs an initialized path tracer");
+    if (!device)
+        for (size_t k = 0; k < floats; ++k)
+            if (!std::isfinite(verts[k])) return fail(err, "vertex update: non-finite vertex coordinate");
+    if (!s.ready || s.ctxs.empty()) {  // no device yet: the host copy only, which the next Init uploads
+        settle_scene();
+        refit_scene_host(sc, verts);
+        drop_derived_trees(sc);
+        ++sc.geomRev;
+        return true;
+    }
+    Ctx *owner = nullptr;  // device vertices: the first context of the memory's device
+    if (device) {
+        hipPointerAttribute_t a{};
+        if (hipPointerGetAttributes(&a, verts) != hipSuccess || a.type != hipMemoryTypeDevice) {
+            (void)hipGetLastError();
+            return fail(err, "vertex update: HIPPT_VERTS_DEVICE needs a device memory pointer");
+        }
+        for (Ctx &c : s.ctxs)
+            if (c.device == a.device && !owner) owner = &c;
+        if (!owner) return fail(err, "vertex update: the vertices are on a device that is none of hipptSetDevices'");
+    }
+    // the staging array of this update: pinned, shared by every device; the one before the last
+    // update's, whose copies are long done in a pipeline one update deep
+    if (u.floats != floats) {
+        stage_wait(0);
+        stage_wait(1);
+        settle_scene();
+        for (float *&p : u.stage) {
+            if (p) (void)hipHostFree(p);
+            p = nullptr;
+        }
+        u.floats = 0;
+        for (float *&p : u.stage)
+            HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&p), floats * sizeof(float), hipHostMallocPortable));
+        u.floats = floats;
+    }
+    const int b = u.next;
+    u.next ^= 1;
+    stage_wait(b);
+    auto record = [&](Ctx &c, hipEvent_t *out) -> bool {
+        hipEvent_t e = nullptr;
+        HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        u.busy[b].push_back({c.device, e});
+        HIP_TRY(hipEventRecord(e, c.stream));
+        if (out) *out = e;
+        return true;
+    };
+    hipEvent_t staged = nullptr;  // device vertices: their copy into the staging array
+    if (device) {
+        HIP_TRY(hipSetDevice(owner->device));
+        HIP_TRY(hipMemcpyAsync(u.stage[b], verts, floats * sizeof(float), hipMemcpyDeviceToHost, owner->stream));
+        if (!record(*owner, &staged)) return false;
+    } else {
+        std::memcpy(u.stage[b], verts, floats * sizeof(float));  // the caller may reuse its array at once
+    }
+    // the host copy follows when something on the host reads it (settle_scene); every path reads the
+    // float nodes from here on
+    u.hostStale = true;
+    u.staleBuf = b;
+    u.staleEv = staged;
+    drop_derived_trees(sc);
+    ++sc.geomRev;
+    unsigned seedBits;
+    std::memcpy(&seedBits, &sc.padSeed, 4);
+    for (Ctx &c : s.ctxs) {
+        // a context that has not uploaded this scene yet uploads the settled host copy when it renders
+        if (c.sceneVersion != sc.version) continue;
+        HIP_TRY(hipSetDevice(c.device));
+        // Pending work is closed first: the held batches launched and the open chained run ended (its
+        // flush enqueued), so that no persistent launch of the run goes on with a batch posted behind
+        // the update; the next batch opens a new run (Ctx::Chain::geomRev).  The deferred combine
+        // stays deferred: it reads no geometry.
+        if (!flush_chain(c, err)) return false;
+        if (!ensure_refit_buffers(c, err)) return false;
+        const float *dv = verts;
+        if (!device || c.device != owner->device) {
+            if (staged && &c != owner) HIP_TRY(hipStreamWaitEvent(c.stream, staged, 0));
+            HIP_TRY(hipMemcpyAsync(c.rfVerts, u.stage[b], floats * sizeof(float), hipMemcpyHostToDevice, c.stream));
+            if (!record(c, nullptr)) return false;
+            dv = c.rfVerts;
+        }
+        hippt::RefitBuffers r{};
+        r.verts = dv;
+        r.tris = c.tris;
+        r.shade = c.shade;
+        r.nodes2 = reinterpret_cast<uint32_t *>(c.nodes);
+        r.nodes4 = reinterpret_cast<uint32_t *>(c.nodes4);
+        r.pbox = c.rfBoxes;
+        r.ubox2 = r.pbox + size_t(sc.numTris) * 6;
+        r.ubox4 = r.ubox2 + size_t(sc.numNodes) * 12;
+        r.words = c.rfWords;
+        r.list2 = c.rfLists;
+        r.list4 = c.rfLists + sc.numNodes;
+        r.numPrims = sc.numTris;
+        r.numTris = sc.numTriangles;
+        r.numNodes2 = sc.numNodes;
+        r.numNodes4 = sc.numNodes4;
+        HIP_TRY(hippt::launch_refit(r, sc.plan.level2, sc.plan.level4, seedBits, c.stream));
+        c.rfUpdated = true;
+    }
+    return true;
+}
+
+}  // namespace
+
+extern "C" bool hipptUpdateVertices(const float *verts, int numTris, int flags, const char **err) try {
+    std::lock_guard<std::mutex> g(S().mu);
+    return update_vertices_locked(verts, numTris, flags, err);
+} catch (const std::exception &e) {
+    return fail_free(err, e.what());
+} catch (...) {
+    return fail_free(err, "unknown exception");
+}
+
+extern "C" long long hipptSceneDownload(int what, void *dst, long long bytes, const char **err) try {
+    std::lock_guard<std::mutex> g(S().mu);
+    State &s = S();
+    auto bad = [&](const char *m) -> long long { return (fail(err, m), -1); };
+    if (s.scene.kind != HIPPT_SCENE_MESH) return bad("scene download: no mesh scene");
+    const SceneHost &sc = s.scene;
+    size_t need = 0;
+    switch (what) {
+    case HIPPT_SCENE_NODES2: need = sc.nodes.size(); break;
+    case HIPPT_SCENE_NODES4: need = sc.nodes4.size(); break;
+    case HIPPT_SCENE_PRIMS: need = sc.tris.size(); break;
+    case HIPPT_SCENE_SHADE: need = sc.shade.size(); break;
+    default: return bad("scene download: unknown buffer");
+    }
+    need *= sizeof(float4);
+    if (!dst) return (long long)need;
+    if (bytes < (long long)need) return bad("scene download: destination too small");
+    if (!s.ready || s.ctxs.empty()) return bad("scene download: HIP path tracer not initialized");
+    Ctx &c = s.ctxs[0];
+    if (!ensure_scene(c, err)) return -1;
+    if (!launch_held(c, err)) return -1;
+    const float4 *src = what == HIPPT_SCENE_NODES2   ? c.nodes
+                        : what == HIPPT_SCENE_NODES4 ? c.nodes4
+                        : what == HIPPT_SCENE_PRIMS  ? c.tris
+                                                     : c.shade;
+    if (hipSetDevice(c.device) != hipSuccess ||
+        hipMemcpyAsync(dst, src, need, hipMemcpyDeviceToHost, c.stream) != hipSuccess ||
+        hipStreamSynchronize(c.stream) != hipSuccess) {
+        (void)hipGetLastError();
+        return bad("scene download: copy failed");
+    }
+    return (long long)need;
+} catch (const std::exception &e) {
+    return (fail_free(err, e.what()), -1);
+} catch (...) {
+    return (fail_free(err, "unknown exception"), -1);
 }
 
 // ---- ray queries ---------------------------------------------------------------------------------
@@ -2866,6 +3208,19 @@ extern "C" long long hipptGetOption(int key) try {
     case HIPPT_INFO_BLOCKS_PER_CU: return s.activeBlocksPerCu;
     case HIPPT_INFO_CHUNK: return s.activeChunk;
     case HIPPT_INFO_CHAIN_CAP: return s.activeChainCap;
+    case HIPPT_INFO_UPDATE_DROPPED:
+        // the last update's count, from the first context that ran it (every context counts the same)
+        for (Ctx &c : s.ctxs) {
+            if (!c.rfUpdated) continue;
+            unsigned w[2] = {0, 0};
+            if (hipSetDevice(c.device) != hipSuccess || hipStreamSynchronize(c.stream) != hipSuccess ||
+                hipMemcpy(w, c.rfWords, sizeof(w), hipMemcpyDeviceToHost) != hipSuccess) {
+                (void)hipGetLastError();
+                return -1;
+            }
+            return w[1];
+        }
+        return 0;
     default: return -1;
     }
 } catch (const std::exception &e) {
@@ -2919,6 +3274,28 @@ extern "C" hipptBvh *hipptBvhBuild(const float *verts, int numTris, float extent
     return (fail_free(err, e.what()), nullptr);
 } catch (...) {
     return (fail_free(err, "unknown exception"), nullptr);
+}
+
+extern "C" bool hipptBvhRefit(hipptBvh *b, const float *verts, int numTris, float extentHint, const char **err) try {
+    auto bad = [&](const std::string &m) {
+        std::lock_guard<std::mutex> g(S().mu);
+        return fail(err, m);
+    };
+    if (!b) return bad("null BVH");
+    if (!verts) return bad("null vertex pointer");
+    if (numTris <= 0 || size_t(numTris) != b->bvh.order.size()) return bad("refit: numTris differs from the build's");
+    for (size_t k = 0; k < size_t(numTris) * 9; ++k)
+        if (!std::isfinite(verts[k])) return bad("non-finite primitive coordinate");
+    std::vector<float> boxes(size_t(numTris) * 6);
+    triangle_boxes(verts, numTris, boxes.data());
+    std::string msg;
+    if (!hippt::refit_bvh(b->bvh, b->bvh4, boxes.data(), numTris, extentHint, msg)) return bad(msg);
+    (void)hippt::quantize_bvh4(b->bvh4, b->bvh4q);  // linear in the nodes; empty for boxes near +-FLT_MAX
+    return true;
+} catch (const std::exception &e) {
+    return fail_free(err, e.what());
+} catch (...) {
+    return fail_free(err, "unknown exception");
 }
 
 extern "C" int hipptBvhNodeCount(const hipptBvh *b) { return b ? int(b->bvh.nodes.size() / hippt::kNodeWords) : 0; }

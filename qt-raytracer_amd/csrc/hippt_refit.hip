@@ -1,0 +1,177 @@
+// hippt_refit.hip — device refit of an uploaded scene to new triangle vertices (hippt_refit.h).
+//
+// Three kinds of launch, all plain stream-ordered kernels (no launch waits on another block; the
+// hand-off between tree levels is the kernel boundary):
+//   refit_prims   one lane per primitive record in leaf order: the triangle's record and normal as
+//                 hipptUploadScene writes them (same operations in the same order: explicit fmaf only,
+//                 IEEE sqrt and division; the library is built with -ffp-contract=off), its unpadded
+//                 box, and the largest |coordinate| folded into one word by an integer max of the
+//                 float's bits (non-negative floats order like their bits)
+//   refit_level   one lane per child slot of one level of a tree: the slot's unpadded box = the union
+//                 of its leaf's primitive boxes or of its child node's unpadded slot boxes (written
+//                 by the previous launch), kept on the side, and the node's box = that moved out once
+//                 by the pad of the update's largest |coordinate| (bvh_builder.h refit_bvh)
+#include "hippt_refit.h"
+
+#include "bvh_builder.h"
+
+namespace hippt {
+namespace {
+
+__device__ inline float f_of(unsigned u) { return __uint_as_float(u); }
+__device__ inline int i_of(float f) { return __float_as_int(f); }
+
+__global__ __launch_bounds__(kRefitBlock) void refit_prims(RefitBuffers B) {
+    const int k = int(blockIdx.x) * kRefitBlock + int(threadIdx.x);
+    unsigned maxBits = 0u;
+    if (k < B.numPrims) {
+        const float4 r2 = B.tris[3 * size_t(k) + 2];
+        const int id = i_of(r2.y);
+        float lo[3], hi[3];
+        bool have = true;
+        if (i_of(r2.z) == 1) {  // sphere: its record stays; the upload's box
+            const float4 q = B.tris[3 * size_t(k)];
+            const float c[3] = {q.x, q.y, q.z};
+            const float r = fabsf(q.w) * (1.0f + 1.0f / 4096.0f);
+            for (int a = 0; a < 3; ++a) {
+                lo[a] = c[a] - r;
+                hi[a] = c[a] + r;
+            }
+        } else {
+            float v[9];
+            bool finite = unsigned(id) < unsigned(B.numTris);
+            for (int j = 0; j < 9; ++j) {
+                v[j] = finite ? B.verts[9 * size_t(id) + j] : 0.0f;
+                finite = finite && isfinite(v[j]);
+            }
+            const float w = B.shade[k].w;  // the material word
+            if (!finite) {
+                // a non-finite vertex the host could not see: the upload's degenerate record with v0
+                // zeroed (no ray hits it), no box, counted
+                have = false;
+                B.tris[3 * size_t(k)] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                B.tris[3 * size_t(k) + 1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                B.tris[3 * size_t(k) + 2] = make_float4(0.0f, r2.y, 0.0f, 0.0f);
+                B.shade[k] = make_float4(0.0f, 0.0f, 0.0f, w);
+                atomicAdd(&B.words[1], 1u);
+            } else {
+                float e1[3] = {v[3] - v[0], v[4] - v[1], v[5] - v[2]};
+                float e2[3] = {v[6] - v[0], v[7] - v[1], v[8] - v[2]};
+                float cr[3], n[3];
+                cr[0] = fmaf(e1[1], e2[2], -(e1[2] * e2[1]));
+                cr[1] = fmaf(e1[2], e2[0], -(e1[0] * e2[2]));
+                cr[2] = fmaf(e1[0], e2[1], -(e1[1] * e2[0]));
+                const float len = sqrtf(fmaf(cr[0], cr[0], fmaf(cr[1], cr[1], cr[2] * cr[2])));
+                if (!(len > 0.0f)) {
+                    e1[0] = e1[1] = e1[2] = 0.0f;
+                    e2[0] = e2[1] = e2[2] = 0.0f;
+                    n[0] = n[1] = n[2] = 0.0f;
+                } else {
+                    const float inv = 1.0f / len;
+                    for (int a = 0; a < 3; ++a) n[a] = cr[a] * inv;
+                }
+                B.tris[3 * size_t(k)] = make_float4(v[0], v[1], v[2], e1[0]);
+                B.tris[3 * size_t(k) + 1] = make_float4(e1[1], e1[2], e2[0], e2[1]);
+                B.tris[3 * size_t(k) + 2] = make_float4(e2[2], r2.y, 0.0f, 0.0f);
+                B.shade[k] = make_float4(n[0], n[1], n[2], w);
+                for (int a = 0; a < 3; ++a) {
+                    lo[a] = fminf(v[a], fminf(v[3 + a], v[6 + a]));
+                    hi[a] = fmaxf(v[a], fmaxf(v[3 + a], v[6 + a]));
+                }
+            }
+        }
+        if (!have)
+            for (int a = 0; a < 3; ++a) {
+                lo[a] = INFINITY;
+                hi[a] = -INFINITY;
+            }
+        float2 *pb = reinterpret_cast<float2 *>(B.pbox + 6 * size_t(k));
+        pb[0] = make_float2(lo[0], lo[1]);
+        pb[1] = make_float2(lo[2], hi[0]);
+        pb[2] = make_float2(hi[1], hi[2]);
+        if (have)
+            for (int a = 0; a < 3; ++a)
+                maxBits = max(maxBits, max(__float_as_uint(fabsf(lo[a])), __float_as_uint(fabsf(hi[a]))));
+    }
+    // one atomic per wave
+    for (int d = 32; d > 0; d >>= 1) maxBits = max(maxBits, unsigned(__shfl_xor(int(maxBits), d)));
+    if ((threadIdx.x & 63u) == 0u && maxBits) atomicMax(&B.words[0], maxBits);
+}
+
+// WIDTH 2: 16-word nodes, codes are node indices.  WIDTH 4: 32-word nodes, interior codes are byte
+// offsets (node * 128).
+template <int WIDTH>
+__global__ __launch_bounds__(kRefitBlock) void refit_level(uint32_t *nodes, const int *list, int count,
+                                                          const float *pbox, float *ubox, const unsigned *words,
+                                                          unsigned seedBits, int numNodes, int numPrims) {
+    constexpr int NW = WIDTH == 2 ? kNodeWords : kNode4Words;
+    const int lane = int(blockIdx.x) * kRefitBlock + int(threadIdx.x);
+    if (lane >= count * WIDTH) return;
+    const int node = list[lane / WIDTH], slot = lane % WIDTH;
+    if (unsigned(node) >= unsigned(numNodes)) return;
+    uint32_t *w = nodes + size_t(node) * NW;
+    const int code = int(w[node_code_word(WIDTH, slot)]);
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    bool used = true;
+    if (code < 0) {
+        const int first = (~code) >> 4, n = (~code) & 15;
+        used = n != 0;
+        if (first + n <= numPrims)
+            for (int p = first; p < first + n; ++p) {
+                const float *b = pbox + 6 * size_t(p);
+                for (int a = 0; a < 3; ++a) {
+                    lo[a] = fminf(lo[a], b[a]);
+                    hi[a] = fmaxf(hi[a], b[3 + a]);
+                }
+            }
+    } else {
+        const int child = WIDTH == 2 ? code : code >> 7;
+        if (unsigned(child) < unsigned(numNodes)) {
+            const float *u = ubox + size_t(child) * WIDTH * 6;
+            for (int c = 0; c < WIDTH; ++c)
+                for (int a = 0; a < 3; ++a) {
+                    lo[a] = fminf(lo[a], u[6 * c + a]);
+                    hi[a] = fmaxf(hi[a], u[6 * c + 3 + a]);
+                }
+        }
+    }
+    float2 *ub = reinterpret_cast<float2 *>(ubox + (size_t(node) * WIDTH + slot) * 6);
+    ub[0] = make_float2(lo[0], lo[1]);
+    ub[1] = make_float2(lo[2], hi[0]);
+    ub[2] = make_float2(hi[1], hi[2]);
+    if (!used) return;  // an unused slot keeps its box
+    const float pad = fmaxf(f_of(max(words[0], seedBits)), 1e-3f) * (1.0f / 65536.0f);
+    const bool have = lo[0] <= hi[0];
+    const float farPoint[3] = {kFarPoint[0], kFarPoint[1], kFarPoint[2]};  // every primitive below dropped
+    for (int a = 0; a < 3; ++a) {
+        w[node_lo_word(WIDTH, slot, a)] = __float_as_uint(have ? lo[a] - pad : farPoint[a]);
+        w[node_hi_word(WIDTH, slot, a)] = __float_as_uint(have ? hi[a] + pad : farPoint[a]);
+    }
+}
+
+template <int WIDTH>
+void launch_levels(uint32_t *nodes, const int *list, const std::vector<int> &level, const RefitBuffers &b, float *ubox,
+                   unsigned seedBits, int numNodes, hipStream_t s) {
+    for (size_t k = 0; k + 1 < level.size(); ++k) {
+        const int count = level[k + 1] - level[k];
+        if (count <= 0) continue;
+        const int blocks = (count * WIDTH + kRefitBlock - 1) / kRefitBlock;
+        hipLaunchKernelGGL(refit_level<WIDTH>, dim3(blocks), dim3(kRefitBlock), 0, s, nodes, list + level[k], count,
+                           b.pbox, ubox, b.words, seedBits, numNodes, b.numPrims);
+    }
+}
+
+}  // namespace
+
+hipError_t launch_refit(const RefitBuffers &b, const std::vector<int> &level2, const std::vector<int> &level4,
+                        unsigned seedBits, hipStream_t s) {
+    if (b.numPrims <= 0) return hipSuccess;
+    hipError_t e = hipMemsetAsync(b.words, 0, 2 * sizeof(unsigned), s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(refit_prims, dim3((b.numPrims + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, s, b);
+    launch_levels<2>(b.nodes2, b.list2, level2, b, b.ubox2, seedBits, b.numNodes2, s);
+    launch_levels<4>(b.nodes4, b.list4, level4, b, b.ubox4, seedBits, b.numNodes4, s);
+    return hipGetLastError();
+}
+
+}  // namespace hippt

@@ -64,7 +64,13 @@ INFO_LDS_TOP_BYTES = 100
 INFO_BLOCKS_PER_CU = 101
 INFO_CHUNK = 102
 INFO_CHAIN_CAP = 103
+INFO_UPDATE_DROPPED = 104
 RAYS_DEVICE = 1
+VERTS_DEVICE = 1
+SCENE_NODES2 = 0
+SCENE_NODES4 = 1
+SCENE_PRIMS = 2
+SCENE_SHADE = 3
 
 # Every symbol include/hippt.h declares (checked by tests/test_abi_cpu.py).
 EXPORTS = (
@@ -81,6 +87,7 @@ EXPORTS = (
     "hipptBvh4NodeCount", "hipptBvh4Depth", "hipptBvh4StackBound", "hipptBvh4Copy", "hipptBvh4QCopy", "hipptBvh4QNodeCount",
     "hipptActiveBvhWidth", "hipptChainAudit",
     "hipptTraceRays", "hipptOccluded", "hipptTraceCamera",
+    "hipptUpdateVertices", "hipptSceneDownload", "hipptBvhRefit",
 )
 
 
@@ -197,6 +204,9 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     sig("hipptTraceRays", c_bool, c_void_p, ctypes.c_longlong, c_int, c_void_p, c_void_p, pp_char)
     sig("hipptOccluded", c_bool, c_void_p, ctypes.c_longlong, c_int, c_void_p, pp_char)
     sig("hipptTraceCamera", c_bool, c_int, c_int, c_void_p, c_void_p, pp_char)
+    sig("hipptUpdateVertices", c_bool, c_void_p, c_int, c_int, pp_char)
+    sig("hipptSceneDownload", ctypes.c_longlong, c_int, c_void_p, ctypes.c_longlong, pp_char)
+    sig("hipptBvhRefit", c_bool, c_void_p, p_float, c_int, c_float, pp_char)
     _lib = lib
     return lib
 
@@ -245,6 +255,53 @@ def _query_rays(rays):
     return rays, False
 
 
+def _update_verts(verts):
+    """Validates new vertices before any call: (n, 9) float32, C-contiguous; a numpy array (a CPU tensor
+    is taken as one) or a tensor on the ROCm device.  Returns (array or tensor, on_device)."""
+    if _is_tensor(verts):
+        import torch
+        if verts.dtype != torch.float32:
+            raise HipptError(f"verts must be float32, not {verts.dtype}")
+        if verts.dim() != 2 or verts.shape[1] != 9:
+            raise HipptError(f"verts must have shape (n, 9), not {tuple(verts.shape)}")
+        if not verts.is_contiguous():
+            raise HipptError("verts must be contiguous")
+        if verts.device.type == "cpu":
+            return verts.numpy(), False
+        if verts.device.type != "cuda":
+            raise HipptError(f"verts on an unsupported device {verts.device}")
+        return verts, True
+    if not isinstance(verts, np.ndarray):
+        raise HipptError("verts must be a numpy array or a torch tensor")
+    if verts.dtype != np.float32:
+        raise HipptError(f"verts must be float32, not {verts.dtype}")
+    if verts.ndim != 2 or verts.shape[1] != 9:
+        raise HipptError(f"verts must have shape (n, 9), not {verts.shape}")
+    if not verts.flags["C_CONTIGUOUS"]:
+        raise HipptError("verts must be contiguous")
+    return verts, False
+
+
+_SCENE_WORDS = {SCENE_NODES2: 16, SCENE_NODES4: 32, SCENE_PRIMS: 12, SCENE_SHADE: 4}
+
+
+def scene_download(what: int) -> np.ndarray:
+    """hipptSceneDownload: context 0's device copy of the 2-wide nodes (N, 16), the 4-wide float nodes
+    (M, 32; interior child codes are byte offsets), the primitive records (P, 12; leaf order, id in
+    word 9) or the shading records (P, 4), as uint32, after the queued work."""
+    if what not in _SCENE_WORDS:
+        raise HipptError(f"unknown scene buffer {what}")
+    lib = load_library()
+    e = ctypes.c_char_p()
+    need = lib.hipptSceneDownload(int(what), None, 0, ctypes.byref(e))
+    if need < 0:
+        raise HipptError(_err(e, "scene download failed"))
+    out = np.zeros(need // 4, np.uint32)
+    if lib.hipptSceneDownload(int(what), out.ctypes.data, need, ctypes.byref(e)) < 0:
+        raise HipptError(_err(e, "scene download failed"))
+    return out.reshape(-1, _SCENE_WORDS[what])
+
+
 def read_mesh(path: str):
     """hipptReadMesh: (verts (n, 9) float32, tri_group (n,) int32, group names) of an OBJ/PLY file."""
     lib = load_library()
@@ -278,23 +335,45 @@ class Bvh:
         lib = load_library()
         v = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 9)
         e = ctypes.c_char_p()
-        h = lib.hipptBvhBuild(_ptr(v, ctypes.c_float), int(v.shape[0]), float(extent_hint), ctypes.byref(e))
-        if not h:
+        self._h = lib.hipptBvhBuild(_ptr(v, ctypes.c_float), int(v.shape[0]), float(extent_hint), ctypes.byref(e))
+        if not self._h:
             raise HipptError(_err(e, "BVH build failed"))
+        self._tris = int(v.shape[0])
+        self._extent = float(extent_hint)
+        self._read()
+
+    def _read(self) -> None:
+        lib, h = load_library(), self._h
+        n = lib.hipptBvhNodeCount(h)
+        self.depth = lib.hipptBvhDepth(h)
+        self.nodes = np.zeros((n, 16), dtype=np.uint32)
+        self.order = np.zeros(self._tris, dtype=np.int32)
+        lib.hipptBvhCopy(h, _ptr(self.nodes, ctypes.c_uint32), _ptr(self.order, ctypes.c_int))
+        self.depth4 = lib.hipptBvh4Depth(h)
+        self.stack_bound4 = lib.hipptBvh4StackBound(h)
+        self.nodes4 = np.zeros((lib.hipptBvh4NodeCount(h), 32), dtype=np.uint32)
+        lib.hipptBvh4Copy(h, _ptr(self.nodes4, ctypes.c_uint32))
+        self.nodes4q = np.zeros((lib.hipptBvh4QNodeCount(h), 16), dtype=np.uint32)
+        lib.hipptBvh4QCopy(h, _ptr(self.nodes4q, ctypes.c_uint32))
+
+    def refit(self, verts: np.ndarray, extent_hint: Optional[float] = None) -> None:
+        """hipptBvhRefit: new boxes for the same topology (nodes, nodes4, nodes4q are read again; codes
+        and order stay).  extent_hint defaults to the build's.  Raises and leaves the trees unchanged
+        on a count mismatch or a non-finite coordinate."""
+        v = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 9)
+        e = ctypes.c_char_p()
+        hint = self._extent if extent_hint is None else float(extent_hint)
+        if not load_library().hipptBvhRefit(self._h, _ptr(v, ctypes.c_float), int(v.shape[0]), hint, ctypes.byref(e)):
+            raise HipptError(_err(e, "BVH refit failed"))
+        self._read()
+
+    def __del__(self):
         try:
-            n = lib.hipptBvhNodeCount(h)
-            self.depth = lib.hipptBvhDepth(h)
-            self.nodes = np.zeros((n, 16), dtype=np.uint32)
-            self.order = np.zeros(v.shape[0], dtype=np.int32)
-            lib.hipptBvhCopy(h, _ptr(self.nodes, ctypes.c_uint32), _ptr(self.order, ctypes.c_int))
-            self.depth4 = lib.hipptBvh4Depth(h)
-            self.stack_bound4 = lib.hipptBvh4StackBound(h)
-            self.nodes4 = np.zeros((lib.hipptBvh4NodeCount(h), 32), dtype=np.uint32)
-            lib.hipptBvh4Copy(h, _ptr(self.nodes4, ctypes.c_uint32))
-            self.nodes4q = np.zeros((lib.hipptBvh4QNodeCount(h), 16), dtype=np.uint32)
-            lib.hipptBvh4QCopy(h, _ptr(self.nodes4q, ctypes.c_uint32))
-        finally:
-            lib.hipptBvhFree(h)
+            if getattr(self, "_h", None):
+                load_library().hipptBvhFree(self._h)
+                self._h = None
+        except Exception:
+            pass
 
 
 class PathTracer:
@@ -455,6 +534,28 @@ class PathTracer:
                                        float(scene.aperture), float(scene.focus), ctypes.byref(e))
         if not ok:
             raise HipptError(_err(e, "mesh upload failed"))
+
+    def updateVertices(self, verts) -> None:  # noqa: N802
+        """hipptUpdateVertices: new vertices (n, 9) float32 for the uploaded scene's n triangles, in place
+        and in stream order (renders and queries enqueued later see them; nothing is drained or
+        reallocated; the BVH is refitted, not rebuilt: uploadScene is the rebuild).  A numpy array is
+        copied before the call returns.  A tensor on the ROCm device is read from where it is, after
+        torch's current stream is synchronised (see traceRays on sharing one HIP runtime with torch):
+        keep it unchanged until the next synchronize() or blocking render."""
+        v, dev = _update_verts(verts)
+        e = ctypes.c_char_p()
+        if dev:
+            import torch
+            torch.cuda.current_stream(v.device).synchronize()
+            ok = self._lib.hipptUpdateVertices(v.data_ptr(), int(v.shape[0]), VERTS_DEVICE, ctypes.byref(e))
+        else:
+            ok = self._lib.hipptUpdateVertices(v.ctypes.data, int(v.shape[0]), 0, ctypes.byref(e))
+        if not ok:
+            raise HipptError(_err(e, "vertex update failed"))
+
+    def updateDropped(self) -> int:  # noqa: N802
+        """Triangles the last device-memory update dropped for a non-finite coordinate (synchronises)."""
+        return int(self._lib.hipptGetOption(INFO_UPDATE_DROPPED))
 
     def setDevices(self, device_ids: Sequence[int]) -> None:  # noqa: N802
         arr = (ctypes.c_int * max(1, len(device_ids)))(*device_ids)

@@ -67,6 +67,16 @@ bool HipPathTracer::useBuiltinScene() {
     return true;
 }
 
+bool HipPathTracer::updateVertices(const std::vector<float> &verts) {
+    if (verts.size() % 9 != 0) {
+        m_lastError = "vertices need 9 floats per triangle";
+        return false;
+    }
+    const char *err = nullptr;
+    if (!hipptUpdateVertices(verts.data(), int(verts.size() / 9), 0, &err)) return fail(err, "vertex update failed");
+    return true;
+}
+
 bool HipPathTracer::renderFrames(int samplesPerFrame, int maxDepth) {
     const char *err = nullptr;
     const unsigned int *pixels = nullptr;

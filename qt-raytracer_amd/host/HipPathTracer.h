@@ -38,6 +38,10 @@ public:
                      const std::vector<hipptMaterial> &materials, const double lookfrom[3], const double lookat[3],
                      const double vup[3], double vfovDeg, double aperture, double focus);
     bool useBuiltinScene();  // the reference kernel's 4 spheres (the default)
+    // New vertices (9 floats per triangle, the upload's triangle order and count) for the uploaded
+    // scene, in place and in stream order: the frames rendered next show them; nothing queued is
+    // drained.  The BVH is refitted, not rebuilt (hipptUpdateVertices): uploadScene is the rebuild.
+    bool updateVertices(const std::vector<float> &verts);
     // samplesPerFrame frames in one call (GpuPathTracer::renderFrame(spp, depth) shape).
     bool renderFrames(int samplesPerFrame, int maxDepth);
     // Enqueue frames + copy to a hand-off frame; latestFrame() never blocks.

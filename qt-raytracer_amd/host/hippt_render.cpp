@@ -37,7 +37,7 @@ int usage() {
     std::fprintf(stderr,
                  "usage: hippt_render [--backend cuda|vulkan|gl] [--mesh FILE] [--albedo r,g,b[;...]] [--width W]\n"
                  "                    [--height H] [--spp N] [--depth D] [--per-frame] [--present] [--out FILE]\n"
-                 "                    [--ppm FILE.ppm] [--pick X,Y]\n");
+                 "                    [--ppm FILE.ppm] [--pick X,Y] [--update-mesh FILE]\n");
     return 2;
 }
 
@@ -58,7 +58,7 @@ std::vector<float> parse_floats(const std::string &s) {
 }  // namespace
 
 int main(int argc, char **argv) {
-    std::string mesh, out, ppm, albedoArg, pickArg, backend = "cuda";
+    std::string mesh, out, ppm, albedoArg, pickArg, updateMesh, backend = "cuda";
     int width = 320, height = 180, spp = 16, depth = 8;
     bool perFrame = false, present = false;
     for (int i = 1; i < argc; ++i) {
@@ -78,6 +78,7 @@ int main(int argc, char **argv) {
         else if (a == "--out") out = v;
         else if (a == "--ppm") ppm = v;
         else if (a == "--pick") pickArg = v;
+        else if (a == "--update-mesh") updateMesh = v;
         else return usage();
     }
     if (backend != "cuda" && backend != "vulkan" && backend != "gl") return usage();
@@ -167,6 +168,22 @@ int main(int argc, char **argv) {
         pixels = ok ? tracer.latestFrame(&frames) : nullptr;
         ok = ok && pixels && frames == spp;
         if (ok) std::fprintf(stderr, "hippt_render: %d intermediate images were ready without waiting\n", shown);
+    } else if (!updateMesh.empty()) {
+        // an animated mesh: sample 0 over --mesh, then the same triangles at --update-mesh's vertices
+        // (HipPathTracer::updateVertices) for the remaining samples
+        hipptMesh m{};
+        const char *err = nullptr;
+        ok = tracer.renderFrames(1, depth);
+        if (ok && !hipptReadMesh(updateMesh.c_str(), &m, &err)) {
+            std::fprintf(stderr, "hippt_render: %s\n", err ? err : "cannot read the update mesh");
+            return 1;
+        }
+        if (ok) {
+            ok = tracer.updateVertices(std::vector<float>(m.verts, m.verts + size_t(m.numTris) * 9));
+            hipptFreeMesh(&m);
+        }
+        ok = ok && tracer.renderFrames(spp - 1, depth);
+        pixels = tracer.hostPixels();
     } else {
         ok = tracer.renderFrames(spp, depth);
         pixels = tracer.hostPixels();
