@@ -207,6 +207,27 @@ bool hipptOccluded(const float *rays, long long numRays, int flags, unsigned cha
  * t and prim hold width*height entries, row 0 = v = 0. */
 bool hipptTraceCamera(int frame, int flags, float *t, int *prim, const char **errorMessage);
 
+/* Hit records: everything the renderer knows about the closest hit, formed with the renderer's
+ * arithmetic (bit for bit what its scatter step starts from).
+ * One closest hit, 32 bytes.  A miss: t = +inf, prim = -1, normal/u/v = 0, matFlags = -1. */
+typedef struct hipptHit {
+    float t;          /* as hipptTraceRays */
+    int   prim;       /* as hipptTraceRays */
+    float normal[3];  /* the renderer's shading normal at the hit, faced against the ray: a triangle's
+                       * unit normal as uploaded (or as the last hipptUpdateVertices refitted it), a
+                       * sphere's (p - centre) / radius at p = origin + t * direction; negated unless
+                       * dot(direction, normal) < 0 */
+    float u, v;       /* triangles: hit point = (1-u-v) v0 + u v1 + v v2; spheres: 0 */
+    int   matFlags;   /* bits 0..29 material index as uploaded; HIPPT_HIT_SPHERE; HIPPT_HIT_BACKFACE */
+} hipptHit;
+/* HIPPT_HIT_BACKFACE: the normal was negated (the ray met the side the stored normal points away from). */
+enum { HIPPT_HIT_SPHERE = 1 << 30, HIPPT_HIT_BACKFACE = (int)(1u << 31) };
+/* hipptTraceRays with a record per ray: rays, validity, tmin/tmax, ties, blocking, shares, slices and
+ * HIPPT_RAYS_DEVICE as there (hits then 32-byte aligned memory of the rays' device). */
+bool hipptTraceHits(const float *rays, long long numRays, int flags, hipptHit *hits, const char **errorMessage);
+/* hipptTraceCamera with a record per pixel: width*height records, row 0 = v = 0. */
+bool hipptTraceCameraHits(int frame, int flags, hipptHit *hits, const char **errorMessage);
+
 /* ---- counters and options ---------------------------------------------------------- */
 typedef struct hipptStats {
     unsigned long long segments;      /* closest-hit queries traced (rays x bounces) */

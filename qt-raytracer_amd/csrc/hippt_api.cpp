@@ -2011,7 +2011,8 @@ bool render_locked(int frameIndex, int count, int maxDepth, const unsigned int *
     return true;
 }
 
-// ---- ray queries (hippt_query.hip; include/hippt.h hipptTraceRays, hipptOccluded, hipptTraceCamera) ----
+// ---- ray queries (hippt_query.hip; include/hippt.h hipptTraceRays, hipptOccluded, hipptTraceCamera,
+// hipptTraceHits, hipptTraceCameraHits) ----
 // A query is one or more launches of the query kernel on a context's stream, after whatever the stream
 // already holds, followed by a wait for the query's own event.  It reads the scene buffers only: it
 // does not flush the deferred combine or the chain, launches no held batch, and leaves the stats and
@@ -2023,7 +2024,8 @@ struct QueryCall {
     float *t = nullptr;
     int *prim = nullptr;
     unsigned char *occ = nullptr;
-    bool any = false, camera = false;
+    hipptHit *hits = nullptr;  // hit records (hipptTraceHits, hipptTraceCameraHits): these, not t / prim
+    bool any = false, camera = false, records = false;
     int frame = 0;
 };
 
@@ -2059,6 +2061,7 @@ bool query_setup(Ctx &c, const QueryCall &call, hippt::QueryParams &q, const cha
     q = hippt::QueryParams{};
     q.nodes = wide ? c.nodes4 : c.nodes;
     q.tris = c.tris;
+    q.shade = c.shade;
     q.stackDepth = stackDepth;
     q.numNodes = numNodes;
     q.numTris = numTris;
@@ -2088,9 +2091,9 @@ bool query_setup(Ctx &c, const QueryCall &call, hippt::QueryParams &q, const cha
     HIP_TRY(hipSetDevice(c.device));
     const long long occKey = ((long long)s.scene.version << 24) ^ ((long long)topBytes << 40) ^ (stackDepth << 8) ^
                              (ldsScene ? 16 : 0) ^ (wide ? 8 : 0) ^ (s.scene.full ? 4 : 0) ^ (call.any ? 2 : 0) ^
-                             (call.camera ? 1 : 0);
+                             (call.camera ? 1 : 0) ^ (call.records ? 32 : 0);
     if (c.qOccKey != occKey) {
-        c.qBlocksPerCu = hippt::query_blocks_per_cu(q, call.any, call.camera);
+        c.qBlocksPerCu = hippt::query_blocks_per_cu(q, call.any, call.camera, call.records);
         c.qOccKey = occKey;
     }
     if (!c.qCtr) HIP_TRY(hipMalloc(&c.qCtr, hippt::kQueryCtrBytes));
@@ -2119,7 +2122,7 @@ bool query_enqueue(Ctx &c, hippt::QueryParams q, unsigned first, unsigned m, con
     const long long blocks =
         std::max(1LL, std::min<long long>((long long)c.cus * c.qBlocksPerCu, (m + hippt::kMeshBlock - 1) / hippt::kMeshBlock));
     HIP_TRY(hipMemsetAsync(c.qCtr, 0, hippt::kQueryCtrBytes, c.stream));
-    HIP_TRY(hippt::launch_query(q, int(blocks), call.any, call.camera, c.stream));
+    HIP_TRY(hippt::launch_query(q, int(blocks), call.any, call.camera, call.records, c.stream));
     return true;
 }
 
@@ -2128,7 +2131,8 @@ bool query_locked(const QueryCall &call, const char **err) {
     // argument and state checks first: none of them touches the GPU
     if (call.n < 0) return fail(err, "ray query: negative ray count");
     if (!call.camera && !call.rays && call.n > 0) return fail(err, "ray query: null ray buffer");
-    if (call.any ? !call.occ : (!call.t && !call.prim)) return fail(err, "ray query: no output buffer");
+    if (call.records ? !call.hits : call.any ? !call.occ : (!call.t && !call.prim))
+        return fail(err, "ray query: no output buffer");
     if (call.camera && call.frame < 0) return fail(err, "ray query: negative frame");
     if (s.scene.kind != HIPPT_SCENE_MESH)
         return fail(err, "ray query: needs a scene from hipptUploadMesh or hipptUploadScene (the built-in scene has none)");
@@ -2145,9 +2149,9 @@ bool query_locked(const QueryCall &call, const char **err) {
     if (device) {
         // every pointer on the device of one context: the whole batch runs there, unstaged
         int dev = -1;
-        const void *ptrs[4] = {call.rays, call.t, call.prim, call.occ};
-        const size_t align[4] = {16, 4, 4, 1};
-        for (int k = 0; k < 4; ++k) {
+        const void *ptrs[5] = {call.rays, call.t, call.prim, call.occ, call.hits};
+        const size_t align[5] = {16, 4, 4, 1, 32};
+        for (int k = 0; k < 5; ++k) {
             if (!ptrs[k]) continue;
             hipPointerAttribute_t a{};
             if (hipPointerGetAttributes(&a, ptrs[k]) != hipSuccess || a.type != hipMemoryTypeDevice) {
@@ -2173,6 +2177,7 @@ bool query_locked(const QueryCall &call, const char **err) {
             q.t = call.t ? call.t + at : nullptr;
             q.prim = call.prim ? call.prim + at : nullptr;
             q.occluded = call.occ ? call.occ + at : nullptr;
+            q.hits = call.hits ? reinterpret_cast<float4 *>(call.hits + at) : nullptr;
             if (!query_enqueue(c, q, unsigned(at), m, call, err)) return false;
         }
         HIP_TRY(hipEventRecord(c.qDone, c.stream));
@@ -2186,7 +2191,9 @@ bool query_locked(const QueryCall &call, const char **err) {
     std::vector<hippt::QueryParams> qs(K);
     std::vector<char *> stage(K, nullptr);
     const size_t cap = size_t(std::min(slice, n));
-    const size_t offT = cap * 32, offP = offT + cap * 4, offO = offP + cap * 4, stageBytes = offO + ((cap + 15) & ~size_t(15));
+    // (rays, then the results: hit records, or t, prim and the occlusion bytes)
+    const size_t offT = cap * 32, offP = offT + cap * 4, offO = offP + cap * 4, offH = offT;
+    const size_t stageBytes = call.records ? offH + cap * sizeof(hipptHit) : offO + ((cap + 15) & ~size_t(15));
     for (size_t k = 0; k < K; ++k) {
         Ctx &c = s.ctxs[k];
         if (n * (long long)(k + 1) / (long long)K == n * (long long)k / (long long)K) continue;  // an empty share
@@ -2222,7 +2229,10 @@ bool query_locked(const QueryCall &call, const char **err) {
             q.t = call.t ? reinterpret_cast<float *>(st + offT) : nullptr;
             q.prim = call.prim ? reinterpret_cast<int *>(st + offP) : nullptr;
             q.occluded = call.occ ? reinterpret_cast<unsigned char *>(st + offO) : nullptr;
+            q.hits = call.hits ? reinterpret_cast<float4 *>(st + offH) : nullptr;
             if (!query_enqueue(c, q, unsigned(at), m, call, err)) return false;
+            if (call.hits)
+                HIP_TRY(hipMemcpyAsync(call.hits + at, q.hits, size_t(m) * sizeof(hipptHit), hipMemcpyDeviceToHost, c.stream));
             if (call.t) HIP_TRY(hipMemcpyAsync(call.t + at, q.t, size_t(m) * 4, hipMemcpyDeviceToHost, c.stream));
             if (call.prim) HIP_TRY(hipMemcpyAsync(call.prim + at, q.prim, size_t(m) * 4, hipMemcpyDeviceToHost, c.stream));
             if (call.occ) HIP_TRY(hipMemcpyAsync(call.occ + at, q.occluded, size_t(m), hipMemcpyDeviceToHost, c.stream));
@@ -2711,6 +2721,36 @@ extern "C" bool hipptTraceCamera(int frame, int flags, float *t, int *prim, cons
     q.flags = flags;
     q.t = t;
     q.prim = prim;
+    return query_locked(q, err);
+} catch (const std::exception &e) {
+    return fail_free(err, e.what());
+} catch (...) {
+    return fail_free(err, "unknown exception");
+}
+
+extern "C" bool hipptTraceHits(const float *rays, long long numRays, int flags, hipptHit *hits, const char **err) try {
+    std::lock_guard<std::mutex> g(S().mu);
+    QueryCall q;
+    q.rays = rays;
+    q.n = numRays;
+    q.flags = flags;
+    q.hits = hits;
+    q.records = true;
+    return query_locked(q, err);
+} catch (const std::exception &e) {
+    return fail_free(err, e.what());
+} catch (...) {
+    return fail_free(err, "unknown exception");
+}
+
+extern "C" bool hipptTraceCameraHits(int frame, int flags, hipptHit *hits, const char **err) try {
+    std::lock_guard<std::mutex> g(S().mu);
+    QueryCall q;
+    q.camera = true;
+    q.frame = frame;
+    q.flags = flags;
+    q.hits = hits;
+    q.records = true;
     return query_locked(q, err);
 } catch (const std::exception &e) {
     return fail_free(err, e.what());

@@ -26,8 +26,8 @@ constexpr unsigned kQueryShards = 8, kQueryCtrStride = 32;
 constexpr size_t kQueryCtrBytes = size_t(kQueryShards) * kQueryCtrStride * sizeof(unsigned);
 
 // One launch traces rays [0, numRays) of `rays` (or, camera: pixels firstItem .. firstItem + numRays
-// - 1 of the image) and writes result i to t[i], prim[i], occluded[i] (each may be null).  Every
-// pointer is device memory of the launch's device.
+// - 1 of the image) and writes result i to t[i], prim[i], occluded[i] (each may be null), or, a
+// hit-record launch, to hits[2 i], hits[2 i + 1] alone.  Every pointer is device memory of the launch's device.
 struct QueryParams {
     const float4 *nodes;  // float nodes: the 2-wide tree or the 4-wide one (Bvh4 layout)
     const float4 *tris;   // MeshParams::tris
@@ -44,12 +44,15 @@ struct QueryParams {
     unsigned topBytes, leafExit, nodeExit;
     int waveThreshold;
     QueryCam cam;
+    // hit records (last, so that the other modes' kernel arguments stay where they were)
+    const float4 *shade;  // MeshParams::shade
+    float4 *hits;         // 2 float4 per ray (hipptHit)
 };
 
 // any: occlusion (the traversal of a ray ends at its first accepted hit); camera: rays generated in
-// the kernel.
-hipError_t launch_query(const QueryParams &q, int blocks, bool any, bool camera, hipStream_t s);
+// the kernel; hits: hit records (not with any).
+hipError_t launch_query(const QueryParams &q, int blocks, bool any, bool camera, bool hits, hipStream_t s);
 size_t query_lds_bytes(const QueryParams &q);
-int query_blocks_per_cu(const QueryParams &q, bool any, bool camera);
+int query_blocks_per_cu(const QueryParams &q, bool any, bool camera, bool hits);
 
 }  // namespace hippt

@@ -66,6 +66,9 @@ INFO_CHUNK = 102
 INFO_CHAIN_CAP = 103
 INFO_UPDATE_DROPPED = 104
 RAYS_DEVICE = 1
+HIT_SPHERE = 1 << 30
+HIT_BACKFACE = -(1 << 31)  # the int's sign bit
+HIT_MATERIAL_MASK = (1 << 30) - 1
 VERTS_DEVICE = 1
 SCENE_NODES2 = 0
 SCENE_NODES4 = 1
@@ -86,7 +89,7 @@ EXPORTS = (
     "hipptLastError", "hipptBvhBuild", "hipptBvhNodeCount", "hipptBvhDepth", "hipptBvhCopy", "hipptBvhFree",
     "hipptBvh4NodeCount", "hipptBvh4Depth", "hipptBvh4StackBound", "hipptBvh4Copy", "hipptBvh4QCopy", "hipptBvh4QNodeCount",
     "hipptActiveBvhWidth", "hipptChainAudit",
-    "hipptTraceRays", "hipptOccluded", "hipptTraceCamera",
+    "hipptTraceRays", "hipptOccluded", "hipptTraceCamera", "hipptTraceHits", "hipptTraceCameraHits",
     "hipptUpdateVertices", "hipptSceneDownload", "hipptBvhRefit",
 )
 
@@ -110,6 +113,26 @@ class Mesh(ctypes.Structure):
     _fields_ = [("verts", ctypes.POINTER(ctypes.c_float)), ("triGroup", ctypes.POINTER(ctypes.c_int)),
                 ("numTris", ctypes.c_int), ("numGroups", ctypes.c_int),
                 ("groupNames", ctypes.POINTER(ctypes.c_char_p)), ("owner_", ctypes.c_void_p)]
+
+
+class Hit(ctypes.Structure):
+    """hipptHit (include/hippt.h), 32 bytes."""
+    _fields_ = [("t", ctypes.c_float), ("prim", ctypes.c_int), ("normal", ctypes.c_float * 3),
+                ("u", ctypes.c_float), ("v", ctypes.c_float), ("matFlags", ctypes.c_int)]
+
+
+# hipptHit as a numpy record: what traceHits / traceCameraHits return for numpy rays
+HIT_DTYPE = np.dtype([("t", "<f4"), ("prim", "<i4"), ("normal", "<f4", (3,)), ("u", "<f4"), ("v", "<f4"),
+                      ("matFlags", "<i4")])
+
+
+def split_hits(hits) -> dict:
+    """Views of the (..., 8) float32 tensor traceHits returns for device rays, by hipptHit's fields: t
+    (...,) float32, prim (...,) int32, normal (..., 3), u, v, matFlags (...,) int32.  No copy: the
+    integer fields are the same bytes seen as int32."""
+    import torch
+    return {"t": hits[..., 0], "prim": hits[..., 1].view(torch.int32), "normal": hits[..., 2:5],
+            "u": hits[..., 5], "v": hits[..., 6], "matFlags": hits[..., 7].view(torch.int32)}
 
 
 class Stats(ctypes.Structure):
@@ -204,6 +227,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     sig("hipptTraceRays", c_bool, c_void_p, ctypes.c_longlong, c_int, c_void_p, c_void_p, pp_char)
     sig("hipptOccluded", c_bool, c_void_p, ctypes.c_longlong, c_int, c_void_p, pp_char)
     sig("hipptTraceCamera", c_bool, c_int, c_int, c_void_p, c_void_p, pp_char)
+    sig("hipptTraceHits", c_bool, c_void_p, ctypes.c_longlong, c_int, c_void_p, pp_char)
+    sig("hipptTraceCameraHits", c_bool, c_int, c_int, c_void_p, pp_char)
     sig("hipptUpdateVertices", c_bool, c_void_p, c_int, c_int, pp_char)
     sig("hipptSceneDownload", ctypes.c_longlong, c_int, c_void_p, ctypes.c_longlong, pp_char)
     sig("hipptBvhRefit", c_bool, c_void_p, p_float, c_int, c_float, pp_char)
@@ -386,6 +411,7 @@ class PathTracer:
         self._frame_index = 0
         self._pixels: Optional[ctypes.POINTER] = None
         self._last_error = ""
+        self._albedo: Optional[np.ndarray] = None  # (materials, 3) of the scene uploaded last (gbuffer)
 
     def __del__(self):  # ~CudaPathTracer -> cudaPathTracerShutdown (CudaPathTracer.cpp:14-18)
         try:
@@ -519,6 +545,7 @@ class PathTracer:
                                         float(scene.aperture), float(scene.focus), ctypes.byref(e))
         if not ok:
             raise HipptError(_err(e, "scene upload failed"))
+        self._albedo = np.array(mats["albedo"], np.float32).reshape(-1, 3)
 
     def uploadMesh(self, scene) -> None:  # noqa: N802
         """hipptUploadMesh for Lambertian triangle scenes; other scenes go through uploadScene."""
@@ -534,6 +561,7 @@ class PathTracer:
                                        float(scene.aperture), float(scene.focus), ctypes.byref(e))
         if not ok:
             raise HipptError(_err(e, "mesh upload failed"))
+        self._albedo = a.copy()
 
     def updateVertices(self, verts) -> None:  # noqa: N802
         """hipptUpdateVertices: new vertices (n, 9) float32 for the uploaded scene's n triangles, in place
@@ -665,6 +693,60 @@ class PathTracer:
             raise HipptError(f"pixel ({x}, {y}) outside the {self._width}x{self._height} image")
         t, prim = self.traceCamera(frame)
         return int(prim[int(y), int(x)]), float(t[int(y), int(x)])
+
+    def traceHits(self, rays):  # noqa: N802
+        """The hit record of each ray's closest hit (hipptHit: t and prim as traceRays, the renderer's
+        shading normal faced against the ray, the barycentrics u, v of a triangle hit, matFlags = material
+        index | HIT_SPHERE | HIT_BACKFACE); a miss is (inf, -1, 0, 0, 0, 0, 0, -1).  numpy rays in: a
+        structured array (N,) of HIT_DTYPE.  A tensor on the ROCm device in (as for traceRays): an
+        (N, 8) float32 tensor on that device, one record per row; split_hits() gives the fields as views."""
+        r, dev = _query_rays(rays)
+        n = int(r.shape[0])
+        e = ctypes.c_char_p()
+        if dev:
+            import torch
+            hits = torch.empty((n, 8), dtype=torch.float32, device=r.device)
+            torch.cuda.current_stream(r.device).synchronize()
+            ok = self._lib.hipptTraceHits(r.data_ptr(), n, RAYS_DEVICE, hits.data_ptr(), ctypes.byref(e))
+        else:
+            hits = np.empty(n, HIT_DTYPE)
+            ok = self._lib.hipptTraceHits(r.ctypes.data, n, 0, hits.ctypes.data, ctypes.byref(e))
+        if not ok:
+            raise HipptError(_err(e, "hit query failed"))
+        return hits
+
+    def traceCameraHits(self, frame: int = 0):  # noqa: N802
+        """The hit record of sample `frame`'s camera ray of every pixel: HIT_DTYPE (H, W), row 0 = v = 0."""
+        hits = np.empty((self._height, self._width), HIT_DTYPE)
+        e = ctypes.c_char_p()
+        if not self._lib.hipptTraceCameraHits(int(frame), 0, hits.ctypes.data, ctypes.byref(e)):
+            raise HipptError(_err(e, "camera hit query failed"))
+        return hits
+
+    def gbuffer(self, frame: int = 0) -> dict:
+        """The guide buffers of sample `frame`'s camera rays, each (H, W) with row 0 = v = 0: depth (t;
+        inf over the sky), prim (-1), normal (H, W, 3) faced towards the camera (0), albedo (H, W, 3)
+        of the hit's material as uploaded (0 over the sky), material (the index; -1)."""
+        if self._albedo is None:
+            raise HipptError("gbuffer: no scene uploaded through this PathTracer")
+        hits = self.traceCameraHits(frame)
+        hit = hits["prim"] >= 0
+        material = np.where(hit, hits["matFlags"] & HIT_MATERIAL_MASK, -1).astype(np.int32)
+        albedo = np.zeros(hit.shape + (3,), np.float32)
+        albedo[hit] = self._albedo[material[hit]]
+        return {"depth": hits["t"].copy(), "prim": hits["prim"].copy(), "normal": hits["normal"].copy(),
+                "albedo": albedo, "material": material}
+
+    def pickHit(self, x: int, y: int, frame: int = 0) -> dict:  # noqa: N802
+        """The hit record under pixel (x, y) (row y = 0 is v = 0) for sample `frame`'s camera ray, as a
+        dict: t, prim, normal (3 floats), u, v, material (-1 over the sky), sphere, backface."""
+        if not (0 <= int(x) < self._width and 0 <= int(y) < self._height):
+            raise HipptError(f"pixel ({x}, {y}) outside the {self._width}x{self._height} image")
+        h = self.traceCameraHits(frame)[int(y), int(x)]
+        hit, mf = int(h["prim"]) >= 0, int(h["matFlags"])
+        return {"t": float(h["t"]), "prim": int(h["prim"]), "normal": tuple(float(c) for c in h["normal"]),
+                "u": float(h["u"]), "v": float(h["v"]), "material": mf & HIT_MATERIAL_MASK if hit else -1,
+                "sphere": hit and bool(mf & HIT_SPHERE), "backface": hit and mf < 0}
 
 
 AUDIT_MAGIC = 0xC4A1D17

@@ -116,6 +116,18 @@ bool HipPathTracer::traceRays(const std::vector<float> &rays, std::vector<float>
     return true;
 }
 
+bool HipPathTracer::traceHits(const std::vector<float> &rays, std::vector<hipptHit> &hits) {
+    if (rays.size() % 8 != 0) {
+        m_lastError = "rays need 8 floats each";
+        return false;
+    }
+    const long long n = (long long)(rays.size() / 8);
+    hits.resize(size_t(n));
+    const char *err = nullptr;
+    if (n > 0 && !hipptTraceHits(rays.data(), n, 0, hits.data(), &err)) return fail(err, "hit query failed");
+    return true;
+}
+
 bool HipPathTracer::pick(int x, int y, int *prim, float *t, int frame) {
     if (x < 0 || y < 0 || x >= m_width || y >= m_height || !prim) {
         m_lastError = "pick outside the image";

@@ -51,6 +51,9 @@ public:
     // Ray queries over the uploaded scene (include/hippt.h "ray queries"): rays = 8 floats each (origin
     // xyz, tmin, direction xyz, tmax); t and prim get one entry per ray (+inf, -1 on a miss).
     bool traceRays(const std::vector<float> &rays, std::vector<float> &t, std::vector<int> &prim);
+    // The same query with a hit record per ray (hipptHit: t, prim, the shading normal faced against the
+    // ray, the barycentrics, material index | HIPPT_HIT_SPHERE | HIPPT_HIT_BACKFACE).
+    bool traceHits(const std::vector<float> &rays, std::vector<hipptHit> &hits);
     // The primitive under pixel (x, y) and its distance, for sample `frame`'s camera ray; y counts rows
     // as hostPixels() does (row 0 = v = 0, the bottom row: a viewport click at yTop is height - 1 - yTop).
     // *prim = -1 and *t = +inf over the sky.

@@ -17,7 +17,8 @@
 // --out writes the frame words (cuda: ARGB; vulkan / gl: RGBA8; row 0 = bottom, little endian),
 // --ppm an image (top row first).  --pick X,Y (cuda backend, with --mesh): after the render,
 // HipPathTracer::pick at that pixel (row 0 = bottom) and the pixel centre's pinhole ray through
-// HipPathTracer::traceRays, reported as "pick": {x, y, prim, t_bits, ray_prim, ray_t_bits}.
+// HipPathTracer::traceRays and HipPathTracer::traceHits, reported as "pick": {x, y, prim, t_bits,
+// ray_prim, ray_t_bits, ray_hit_words (the hipptHit's 8 words)}.
 // Prints one JSON line.
 #include <chrono>
 #include <cstdio>
@@ -236,12 +237,20 @@ int main(int argc, char **argv) {
             std::fprintf(stderr, "hippt_render: traceRays: %s\n", tracer.lastError().c_str());
             return 1;
         }
-        unsigned tb, rb;
+        std::vector<hipptHit> hits;
+        if (!tracer.traceHits(ray, hits)) {
+            std::fprintf(stderr, "hippt_render: traceHits: %s\n", tracer.lastError().c_str());
+            return 1;
+        }
+        unsigned tb, rb, hw[8];
         std::memcpy(&tb, &t, 4);
         std::memcpy(&rb, &ts[0], 4);
-        char buf[200];
+        static_assert(sizeof(hipptHit) == sizeof hw, "hipptHit is 8 words");
+        std::memcpy(hw, &hits[0], sizeof hw);
+        char buf[400];
         std::snprintf(buf, sizeof buf, ", \"pick\": {\"x\": %d, \"y\": %d, \"prim\": %d, \"t_bits\": %u, \"ray_prim\": %d, "
-                      "\"ray_t_bits\": %u}", int(xy[0]), int(xy[1]), prim, tb, prims[0], rb);
+                      "\"ray_t_bits\": %u, \"ray_hit_words\": [%u, %u, %u, %u, %u, %u, %u, %u]}", int(xy[0]), int(xy[1]), prim,
+                      tb, prims[0], rb, hw[0], hw[1], hw[2], hw[3], hw[4], hw[5], hw[6], hw[7]);
         pickJson = buf;
     }
     hipptGetStats(&st);

@@ -9,7 +9,12 @@ same image: the rays generated in the kernel, no ray buffer read.
 
 Each figure: warm-up calls, then the median of --runs calls, each a host clock around the blocking
 call (so it includes the launch and the wait, as a caller sees it).  Writes one JSON file per scene
-into --out and prints one summary line per measurement."""
+into --out and prints one summary line per measurement.
+
+--hits: hit records against the closest-hit query they extend.  In one process, on the same rays,
+hipptTraceRays and hipptTraceHits alternate call by call (so that clock and thermal drift fall on both
+alike); per ray set the median of --runs calls of each and the ratio traceHits / traceRays of the
+medians, written to profiles/hit_records/ unless --out says otherwise."""
 import argparse
 import ctypes
 import json
@@ -65,6 +70,71 @@ def timed(call, warmup, runs):
     return ms
 
 
+def alternated(calls, warmup, runs):
+    """{name: [ms]}: `runs` rounds, each timing every call once, in the order given."""
+    for _ in range(warmup):
+        for _, call in calls:
+            call()
+    ms = {name: [] for name, _ in calls}
+    for _ in range(runs):
+        for name, call in calls:
+            t0 = time.perf_counter()
+            call()
+            ms[name].append((time.perf_counter() - t0) * 1e3)
+    return ms
+
+
+def hits_mode(args, lib, dev, n):
+    for name in args.scenes.split(","):
+        sc = scenes.get_scene(name)
+        pt = hippt.PathTracer()
+        pt.setDevices([args.device])
+        pt.uploadMesh(sc)
+        if not pt.initialize(args.side, args.side):
+            raise SystemExit(pt.lastError())
+        t = torch.empty(n, dtype=torch.float32, device=dev)
+        prim = torch.empty(n, dtype=torch.int32, device=dev)
+        hits = torch.empty((n, 8), dtype=torch.float32, device=dev)
+        e = ctypes.c_char_p()
+        rows = []
+
+        def check(ok):
+            if not ok:
+                raise SystemExit(e.value.decode() if e.value else "query failed")
+
+        for rayset, make in (("camera", lambda: camera_rays(sc, args.side)), ("inbox", lambda: inbox_rays(sc, n))):
+            rays = torch.from_numpy(make()).to(dev)
+            torch.cuda.synchronize(dev)
+            ms = alternated((
+                ("traceRays", lambda: check(lib.hipptTraceRays(rays.data_ptr(), n, hippt.RAYS_DEVICE, t.data_ptr(),
+                                                               prim.data_ptr(), ctypes.byref(e)))),
+                ("traceHits", lambda: check(lib.hipptTraceHits(rays.data_ptr(), n, hippt.RAYS_DEVICE, hits.data_ptr(),
+                                                               ctypes.byref(e))))), args.warmup, args.runs)
+            f = hippt.split_hits(hits)
+            if not (torch.equal(f["prim"], prim) and torch.equal(f["t"].view(torch.int32), t.view(torch.int32))):
+                raise SystemExit(f"{name} {rayset}: traceHits and traceRays disagree")
+            med = {k: statistics.median(v) for k, v in ms.items()}
+            rows.append({"rays": rayset, "n": n, "ms": {k: [round(x, 4) for x in v] for k, v in ms.items()},
+                         "median_ms": {k: round(v, 4) for k, v in med.items()},
+                         "grays_per_s": {k: round(n / v / 1e6, 3) for k, v in med.items()},
+                         "ratio_hits_over_rays": round(med["traceHits"] / med["traceRays"], 4),
+                         "hit_share": round(int((prim >= 0).sum()) / n, 4),
+                         "backface_share": round(int((f["matFlags"] < 0).logical_and(prim >= 0).sum()) / n, 4)})
+            del rays, f
+        out = {"scene": name, "triangles": sc.num_tris, "side": args.side, "warmup": args.warmup, "runs": args.runs,
+               "device": torch.cuda.get_device_name(dev), "order": "traceRays, traceHits alternating per call",
+               "lds_scene": bool(lib.hipptGetOption(hippt.OPT_LDS_SCENE)), "results": rows}
+        with open(os.path.join(args.out, f"{name}.json"), "w") as fo:
+            json.dump(out, fo, indent=1)
+            fo.write("\n")
+        for r in rows:
+            print(f"{name:10s} {r['rays']:7s} traceRays {r['median_ms']['traceRays']:8.3f} ms "
+                  f"{r['grays_per_s']['traceRays']:7.3f} G/s  traceHits {r['median_ms']['traceHits']:8.3f} ms "
+                  f"{r['grays_per_s']['traceHits']:7.3f} G/s  ratio {r['ratio_hits_over_rays']:.3f}", flush=True)
+        del pt, t, prim, hits
+        lib.cudaPathTracerShutdown()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--scenes", default="cornell34,blob70k")
@@ -72,14 +142,19 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--device", type=int, default=0)
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "ray_query"))
+    ap.add_argument("--hits", action="store_true", help="traceHits against traceRays, alternating (see above)")
+    ap.add_argument("--out", default=None, help="default profiles/ray_query, with --hits profiles/hit_records")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(REPO, "profiles", "hit_records" if args.hits else "ray_query")
     if not torch.cuda.is_available():
         raise SystemExit("no ROCm device visible to torch")
     os.makedirs(args.out, exist_ok=True)
     lib = hippt.load_library()
     dev = torch.device("cuda", args.device)
     n = args.side * args.side
+    if args.hits:
+        return hits_mode(args, lib, dev, n)
     for name in args.scenes.split(","):
         sc = scenes.get_scene(name)
         pt = hippt.PathTracer()
