@@ -350,6 +350,18 @@ enum {
     , HIPPT_OPT_QUERY_SLICE = 33    /* ray queries from host memory: rays per slice staged through a device's
                                        buffers, 64..2^28; 0 (default): automatic (2^22).  Same results either
                                        way */
+    , HIPPT_OPT_RENDER_PAD = 34     /* render megakernel over an LDS-resident 4-wide float tree: the node boxes
+                                       of its LDS scene copy keep a pad of M * 2^-value (17..21) of the
+                                       builder's M * 2^-16 (M: the largest |coordinate| of the scene and the
+                                       camera), so that a scattered ray's own flat leaf is culled at its
+                                       parent's visit; 0: the builder's pad, no trim.  Default 19 (DESIGN.md
+                                       §5).  Applied only where the pad's bound holds: the camera's origin (lens
+                                       included; hipptSetCamera may move it) within that M, and every
+                                       triangle's two edges from its first vertex meeting at a sine of at least
+                                       0.3 (not known after a device-memory hipptUpdateVertices until the host
+                                       copy has caught up); otherwise, and for trees in global memory, the
+                                       wavefront path and the ray queries, the builder's pad stays
+                                       (HIPPT_INFO_RENDER_PAD: 0).  Same results either way */
 };
 /* Records of the chained runs closed since the last call (HIPPT_OPT_CHAIN_AUDIT), as 32-bit words:
  * per run a 16-word header  [0] 0xC4A1D17 [1] run id [2] device [3] batch 0's first frame [4] frames
@@ -373,11 +385,13 @@ int hipptChainAudit(unsigned int *words, int maxWords);
 enum { HIPPT_PIXEL_ARGB = 0, HIPPT_PIXEL_RGBA8 = 1 };
 /* Read-only (hipptGetOption) facts of the last megakernel render: LDS bytes of the top of the tree,
  * persistent-grid blocks per CU, work items per claim (HIPPT_OPT_CHUNK as applied), batches a launch
- * may trace (HIPPT_OPT_CHAIN as applied: 0 = the batch was not chained). */
+ * may trace (HIPPT_OPT_CHAIN as applied: 0 = the batch was not chained), the node-box pad exponent of
+ * the LDS scene copy (HIPPT_OPT_RENDER_PAD as applied: 0 = the builder's pad, no trim). */
 enum { HIPPT_INFO_LDS_TOP_BYTES = 100, HIPPT_INFO_BLOCKS_PER_CU = 101, HIPPT_INFO_CHUNK = 102,
        HIPPT_INFO_CHAIN_CAP = 103,
        HIPPT_INFO_UPDATE_DROPPED = 104 /* triangles the last device-memory hipptUpdateVertices dropped
-                                          for a non-finite coordinate; reading it synchronises */ };
+                                          for a non-finite coordinate; reading it synchronises */,
+       HIPPT_INFO_RENDER_PAD = 105 };
 bool hipptSetOption(int key, long long value);
 long long hipptGetOption(int key);
 /* BVH width (2 or 4) the last mesh render traversed (0 before any): what nodeVisits count. */

@@ -283,6 +283,7 @@ bool build_bvh_boxes(const float *boxes, int numPrims, float extentHint, Bvh &ou
     out.nodes = std::move(bld.nodes);
     out.levels = bld.levels;
     out.leaves = bld.leaves;
+    out.pad = pad;
     out.order.resize(size_t(numPrims));
     for (int i = 0; i < numPrims; ++i) out.order[size_t(i)] = prims[size_t(i)].id;
     if (out.levels > params.maxDepth) {
@@ -712,6 +713,7 @@ bool refit_bvh(Bvh &bvh2, Bvh4 &bvh4, const float *boxes, int numPrims, float ex
     std::vector<float> ubox(std::max(bvh2.nodes.size() / kNodeWords * 12, bvh4.nodes.size() / kNode4Words * 24));
     refit_tree(bvh2.nodes.data(), 2, plan->list2, pbox.data(), pad, ubox);
     refit_tree(bvh4.nodes.data(), 4, plan->list4, pbox.data(), pad, ubox);
+    bvh2.pad = pad;
     return true;
 }
 

@@ -45,6 +45,8 @@ struct Bvh {
     std::vector<int> order;       // leaf order -> original primitive index
     int levels = 0;               // interior levels on the deepest path (= max stack use)
     int leaves = 0;
+    float pad = 0.0f;             // what every box of the nodes (and of a Bvh4 collapsed from them) was
+                                  // moved out by: set by build_bvh_boxes and by refit_bvh
 };
 
 // verts: numTris * 9 floats.  extentHint: largest |coordinate| any ray origin can have

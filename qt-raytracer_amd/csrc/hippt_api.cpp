@@ -34,6 +34,7 @@
 #include "hippt_device.h"
 #include "hippt_query.h"
 #include "hippt_refit.h"
+#include "hippt_slab.h"
 #include "hippt_wavefront.h"
 
 struct hipptBvh {
@@ -145,6 +146,9 @@ struct Ctx {
     float4 *nodes4f = nullptr; // the 4-wide BVH with half-precision planes (half_bvh4; on use)
     int halfVersion = -1;      // scene version of nodes4f
     int hybridTop = -1;
+    // the pad the float nodes were built or last refitted with (MeshParams::padWord): written by the
+    // scene upload and by every vertex update, in stream order
+    float *padDev = nullptr;
     // Vertex updates (hipptUpdateVertices, hippt_refit.h): the refit's own buffers for the uploaded
     // scene, allocated at the context's first update and freed with the scene buffers
     float *rfVerts = nullptr;   // the update's vertices (host memory, or memory of another device)
@@ -270,6 +274,10 @@ struct SceneHost {
     hippt::RefitPlan plan;
     int numTriangles = 0;
     float extent = 0.0f, padSeed = 0.0f;
+    float pad = 0.0f;  // the pad the host copy's node boxes carry (Bvh::pad; Ctx::padDev on upload)
+    // smallest sine of the angle between a triangle's edges (min_edge_sine); 0: not known (a vertex
+    // update from device memory that the host copy has not caught up with)
+    float minEdgeSine = 0.0f;
     unsigned geomRev = 0;
 };
 
@@ -314,6 +322,7 @@ struct State {
     int pixelTile = -1;    // the item order's runs: tile columns (HIPPT_OPT_PIXEL_TILE; 0 rows, -1 automatic)
     int chainBatches = -1; // batches a chained launch may trace (HIPPT_OPT_CHAIN; 0 off, -1 automatic)
     bool chainAudit = false;            // HIPPT_OPT_CHAIN_AUDIT
+    int renderPad = hippt::slab::kRenderPadDefault;  // HIPPT_OPT_RENDER_PAD (0: the builder's pad)
     long long querySlice = 0;           // rays per staged slice of a host-memory query (HIPPT_OPT_QUERY_SLICE; 0 automatic)
     std::vector<unsigned> auditWords;   // closed runs' audit words not yet read (hipptChainAudit)
     std::vector<std::pair<int, uint32_t *>> rngTables;  // per device, built on first use
@@ -345,6 +354,7 @@ struct State {
     int activeBlocksPerCu = 0;
     int activeChunk = 0;     // the last megakernel batch's claim size
     int activeChainCap = 0;  // its run's chain cap (0: not chained)
+    int activeRenderPad = 0; // its LDS scene copy's pad exponent (HIPPT_OPT_RENDER_PAD as applied; 0: no trim)
     int activeWidth = 0;  // BVH width of the last mesh render (hipptActiveBvhWidth)
     int blocksPerCu = 0;
     bool ldsScene = true;
@@ -529,6 +539,8 @@ void free_scene_buffers(Ctx &c) {
     (void)hipFree(c.nodes4q);
     (void)hipFree(c.nodes4h);
     (void)hipFree(c.nodes4f);
+    (void)hipFree(c.padDev);
+    c.padDev = nullptr;
     c.nodes = c.tris = c.shade = c.mats = c.nodes4 = c.nodes4q = c.nodes4h = c.nodes4f = nullptr;
     (void)hipFree(c.rfVerts);
     (void)hipFree(c.rfBoxes);
@@ -601,6 +613,24 @@ void sphere_box(const float *q, float *bx) {
     }
 }
 
+// Smallest sine of the angle between the two edges e1, e2 of any non-degenerate triangle of `verts`
+// (numTris * 9 floats): what the render pad's bound depends on (the error of an
+// accepted Möller–Trumbore hit's t grows with 1 / sin).  1 for no triangles.
+float min_edge_sine(const float *verts, int numTris) {
+    double m = 1.0;
+    for (int i = 0; i < numTris; ++i) {
+        const float *v = verts + 9 * size_t(i);
+        const double a[3] = {double(v[3]) - v[0], double(v[4]) - v[1], double(v[5]) - v[2]};
+        const double b[3] = {double(v[6]) - v[0], double(v[7]) - v[1], double(v[8]) - v[2]};
+        const double c[3] = {a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]};
+        const double cc = c[0] * c[0] + c[1] * c[1] + c[2] * c[2];
+        const double ab = (a[0] * a[0] + a[1] * a[1] + a[2] * a[2]) * (b[0] * b[0] + b[1] * b[1] + b[2] * b[2]);
+        if (!(cc > 0.0) || !std::isfinite(ab)) continue;  // degenerate or dropped: no ray hits it
+        m = std::min(m, std::sqrt(cc / ab));
+    }
+    return float(m);
+}
+
 // SceneHost refitted to `verts` (numTriangles * 9 floats) as the device refit does it: a triangle with
 // a non-finite coordinate becomes the zero record without a box (the host-memory path of
 // hipptUpdateVertices has rejected those before).
@@ -636,6 +666,8 @@ void refit_scene_host(SceneHost &sc, const float *verts) {
     std::string msg;
     if (!hippt::refit_bvh(sc.bvh2, sc.bvh4, boxes.data(), numPrims, sc.extent, msg, &sc.plan))
         throw std::runtime_error("vertex update: " + msg);  // (sizes and values were checked: not reached)
+    sc.pad = sc.bvh2.pad;
+    sc.minEdgeSine = min_edge_sine(verts, nt);
     std::memcpy(sc.nodes.data(), sc.bvh2.nodes.data(), sc.bvh2.nodes.size() * sizeof(uint32_t));
     auto *w4 = reinterpret_cast<uint32_t *>(sc.nodes4.data());
     for (size_t k = 0; k < size_t(sc.numNodes4); ++k)  // the boxes; the device layout keeps its byte codes
@@ -810,8 +842,24 @@ bool ensure_scene(Ctx &c, const char **err) {
     if (!up(c.nodes, s.scene.nodes) || !up(c.tris, s.scene.tris) || !up(c.shade, s.scene.shade) ||
         !up(c.mats, s.scene.mats) || !up(c.nodes4, s.scene.nodes4) || !up(c.nodes4q, s.scene.nodes4q))
         return false;
+    HIP_TRY(hipMalloc(&c.padDev, 16));
+    HIP_TRY(hipMemcpy(c.padDev, &s.scene.pad, sizeof(float), hipMemcpyHostToDevice));
     c.sceneVersion = s.scene.version;
     return true;
+}
+
+// The preconditions of the render pad's bound, without which the LDS scene copy keeps
+// the builder's pad: every ray origin within the M the pad was sized from (the camera's origin, lens
+// included; hipptSetCamera may have moved it since the upload), and no triangle whose edges meet at
+// a sine below kRenderPadMinSine.  M: the host copy's pad * 2^16, or, while a vertex update is not in
+// the host copy yet, its lower bound padSeed (no update lowers it; the device's M is at least that).
+constexpr float kRenderPadMinSine = 0.3f;
+bool render_pad_holds(const SceneHost &sc, bool hostStale, const CameraF &cam) {
+    const float M = hostStale ? sc.padSeed : std::max(sc.padSeed, sc.pad * 65536.0f);
+    float o = 0.0f;
+    for (int k = 0; k < 3; ++k) o = std::max(o, std::fabs(cam.origin[k]));
+    const float reach = o + 1.5f * std::fabs(cam.lens_radius);  // (a lens offset's component: at most sqrt(2) radii)
+    return std::isfinite(reach) && reach <= M && sc.minEdgeSine >= kRenderPadMinSine;
 }
 
 // Low bits of a packed child key (trace::child_key_p) that give an LDS-resident 4-wide tree's child
@@ -1458,7 +1506,8 @@ bool chain_same(const hippt::MeshParams &a, const hippt::MeshParams &b) {
            a.nodeExit == b.nodeExit && a.wide == b.wide && a.stackCap == b.stackCap && a.spillCap == b.spillCap &&
            a.spill == b.spill && a.topBytes == b.topBytes && a.refBits == b.refBits && a.runOrder == b.runOrder &&
            a.runCount == b.runCount && a.runTileShift == b.runTileShift && a.rngTable == b.rngTable && a.poolOffset == b.poolOffset &&
-           a.poolWords == b.poolWords && a.comb.format == b.comb.format;
+           a.poolWords == b.poolWords && a.comb.format == b.comb.format && a.padWord == b.padWord &&
+           a.trimScale == b.trimScale;
 }
 
 // Enqueues the launch of chained batch p (its chain fields set by chain_batch but the epoch): the run's
@@ -1910,6 +1959,13 @@ bool enqueue_locked(int firstFrame, int count, int maxDepth, bool copy, const ch
                         p.stackCap = stackCap;
                         p.topBytes = topBytes;
                         p.refBits = ldsScene && wide ? packed_ref_bits(numNodes, numTris) : 0u;
+                        // the LDS scene copy's node boxes trimmed to the render pad (HIPPT_OPT_RENDER_PAD;
+                        // megakernel over an LDS-resident 4-wide float tree only)
+                        const bool trims = s.pathMode == 0 && ldsScene && fmt == hippt::kWideFloat && s.renderPad != 0 &&
+                                           render_pad_holds(s.scene, s.upd.hostStale, cam);
+                        p.padWord = c.padDev;
+                        p.trimScale = trims ? hippt::slab::trim_scale(s.renderPad) : 0.0f;
+                        s.activeRenderPad = trims ? s.renderPad : 0;
                         p.rngTable = nullptr;
                         p.poolWords = poolWords;
                         // Pixel runs by estimated sample length, longest first, per XCD queue
@@ -2440,6 +2496,8 @@ extern "C" bool hipptUploadScene(const float *verts, const int *triMaterial, int
     hippt::refit_plan(bvh, bvh4, sc.plan);
     sc.numTriangles = numTris;
     sc.extent = extent;
+    sc.pad = bvh.pad;
+    sc.minEdgeSine = min_edge_sine(verts, numTris);
     sc.padSeed = std::fabs(extent);
     for (size_t k = size_t(numTris) * 6; k < boxes.size(); ++k) sc.padSeed = std::max(sc.padSeed, std::fabs(boxes[k]));
     sc.geomRev = s.scene.geomRev + 1;
@@ -2585,6 +2643,8 @@ bool update_vertices_locked(const float *verts, int numTris, int flags, const ch
     }
     // the host copy follows when something on the host reads it (settle_scene); every path reads the
     // float nodes from here on
+    // (the render pad's precondition: known at once for host vertices, with the host copy for others)
+    sc.minEdgeSine = device ? 0.0f : min_edge_sine(verts, numTris);
     u.hostStale = true;
     u.staleBuf = b;
     u.staleEv = staged;
@@ -2619,6 +2679,7 @@ bool update_vertices_locked(const float *verts, int numTris, int flags, const ch
         r.ubox2 = r.pbox + size_t(sc.numTris) * 6;
         r.ubox4 = r.ubox2 + size_t(sc.numNodes) * 12;
         r.words = c.rfWords;
+        r.padOut = c.padDev;
         r.list2 = c.rfLists;
         r.list4 = c.rfLists + sc.numNodes;
         r.numPrims = sc.numTris;
@@ -3191,6 +3252,10 @@ extern "C" bool hipptSetOption(int key, long long value) try {
         if (value < 0 || value > (1LL << 28)) return false;
         s.querySlice = value;
         return true;
+    case HIPPT_OPT_RENDER_PAD:
+        if (value != 0 && (value < hippt::slab::kRenderPadMin || value > hippt::slab::kRenderPadMax)) return false;
+        s.renderPad = int(value);
+        return true;
     default: return false;
     }
 } catch (const std::exception &e) {
@@ -3244,10 +3309,12 @@ extern "C" long long hipptGetOption(int key) try {
     case HIPPT_OPT_CHAIN_AUDIT: return s.chainAudit ? 1 : 0;
     case HIPPT_OPT_PIXEL_TILE: return s.pixelTile;
     case HIPPT_OPT_QUERY_SLICE: return s.querySlice;
+    case HIPPT_OPT_RENDER_PAD: return s.renderPad;
     case HIPPT_INFO_LDS_TOP_BYTES: return s.activeTopBytes;
     case HIPPT_INFO_BLOCKS_PER_CU: return s.activeBlocksPerCu;
     case HIPPT_INFO_CHUNK: return s.activeChunk;
     case HIPPT_INFO_CHAIN_CAP: return s.activeChainCap;
+    case HIPPT_INFO_RENDER_PAD: return s.activeRenderPad;
     case HIPPT_INFO_UPDATE_DROPPED:
         // the last update's count, from the first context that ran it (every context counts the same)
         for (Ctx &c : s.ctxs) {

@@ -137,6 +137,13 @@ struct MeshParams {
     // HIPPT_OPT_CHAIN_AUDIT: the run's audit records (kAuditBatches + 1 records of kAuditWords words:
     // per batch what was traced and combined, hipptChainAudit), or null
     unsigned *chainAudit;
+    // HIPPT_OPT_RENDER_PAD (LDS-resident 4-wide float trees; hippt_slab.h): the LDS scene copy moves
+    // every node plane inward by *padWord * trimScale.  padWord: the pad the nodes were built or last
+    // refitted with, a device word the scene upload and the refit write in stream order (a launch
+    // reads the pad of the tree it traces: a vertex update closes the open chained run first).
+    // trimScale 0: no trim (padWord is not read).
+    const float *padWord;
+    float trimScale;
 };
 
 // Chained batches: the control block (unsigned words).  Ring slot k's block at k * kChainBlockWords:

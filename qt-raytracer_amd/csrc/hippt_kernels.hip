@@ -388,8 +388,19 @@ __global__ __launch_bounds__(kMeshBlock, (FULL || WIDE) ? HIPPT_WIDE_WAVES_PER_E
             // packed keys: the copy's code rows hold each code's low refBits bits (child_key_p merges
             // them into the key with one v_and_or)
             const unsigned refMask = PACKED ? (1u << P.refBits) - 1u : ~0u;
+            // the node boxes trimmed to the render pad (HIPPT_OPT_RENDER_PAD, hippt_slab.h): rows 0-5
+            // of a node are lo.x hi.x lo.y hi.y lo.z hi.z; an unused slot's far point stays as it is
+            const float trim = P.trimScale != 0.0f ? slab::trim_of(*P.padWord, P.trimScale) : 0.0f;
             for (int i = threadIdx.x; i < P.numNodes * kLdsNode4F4; i += kMeshBlock) {
                 float4 v = P.nodes[i];
+                if (trim != 0.0f && (i & 7) < 6) {
+                    if (i & 1)
+                        v = make_float4(slab::trim_hi(v.x, trim), slab::trim_hi(v.y, trim), slab::trim_hi(v.z, trim),
+                                        slab::trim_hi(v.w, trim));
+                    else
+                        v = make_float4(slab::trim_lo(v.x, trim), slab::trim_lo(v.y, trim), slab::trim_lo(v.z, trim),
+                                        slab::trim_lo(v.w, trim));
+                }
                 if (PACKED && (i & 7) == 6) {
                     v.x = __uint_as_float(__float_as_uint(v.x) & refMask);
                     v.y = __uint_as_float(__float_as_uint(v.y) & refMask);

@@ -25,6 +25,7 @@ struct RefitBuffers {
     float *ubox2;        // numNodes2 * 12: unpadded slot boxes of the 2-wide tree
     float *ubox4;        // numNodes4 * 24: of the 4-wide tree
     unsigned *words;     // [0] bits of the largest |coordinate| of the update, [1] triangles dropped
+    float *padOut;       // null, or the word that receives the pad the nodes are refitted with (MeshParams::padWord)
     const int *list2;    // RefitPlan::list2
     const int *list4;    // RefitPlan::list4
     int numPrims, numTris, numNodes2, numNodes4;

@@ -103,10 +103,14 @@ __global__ __launch_bounds__(kRefitBlock) void refit_prims(RefitBuffers B) {
 template <int WIDTH>
 __global__ __launch_bounds__(kRefitBlock) void refit_level(uint32_t *nodes, const int *list, int count,
                                                           const float *pbox, float *ubox, const unsigned *words,
-                                                          unsigned seedBits, int numNodes, int numPrims) {
+                                                          unsigned seedBits, int numNodes, int numPrims,
+                                                          float *padOut) {
     constexpr int NW = WIDTH == 2 ? kNodeWords : kNode4Words;
     const int lane = int(blockIdx.x) * kRefitBlock + int(threadIdx.x);
     if (lane >= count * WIDTH) return;
+    const float pad = fmaxf(f_of(max(words[0], seedBits)), 1e-3f) * (1.0f / 65536.0f);
+    // the update's pad for the renderer (every level's launch writes the same value)
+    if (lane == 0 && padOut) *padOut = pad;
     const int node = list[lane / WIDTH], slot = lane % WIDTH;
     if (unsigned(node) >= unsigned(numNodes)) return;
     uint32_t *w = nodes + size_t(node) * NW;
@@ -140,7 +144,6 @@ __global__ __launch_bounds__(kRefitBlock) void refit_level(uint32_t *nodes, cons
     ub[1] = make_float2(lo[2], hi[0]);
     ub[2] = make_float2(hi[1], hi[2]);
     if (!used) return;  // an unused slot keeps its box
-    const float pad = fmaxf(f_of(max(words[0], seedBits)), 1e-3f) * (1.0f / 65536.0f);
     const bool have = lo[0] <= hi[0];
     const float farPoint[3] = {kFarPoint[0], kFarPoint[1], kFarPoint[2]};  // every primitive below dropped
     for (int a = 0; a < 3; ++a) {
@@ -151,13 +154,13 @@ __global__ __launch_bounds__(kRefitBlock) void refit_level(uint32_t *nodes, cons
 
 template <int WIDTH>
 void launch_levels(uint32_t *nodes, const int *list, const std::vector<int> &level, const RefitBuffers &b, float *ubox,
-                   unsigned seedBits, int numNodes, hipStream_t s) {
+                   unsigned seedBits, int numNodes, float *padOut, hipStream_t s) {
     for (size_t k = 0; k + 1 < level.size(); ++k) {
         const int count = level[k + 1] - level[k];
         if (count <= 0) continue;
         const int blocks = (count * WIDTH + kRefitBlock - 1) / kRefitBlock;
         hipLaunchKernelGGL(refit_level<WIDTH>, dim3(blocks), dim3(kRefitBlock), 0, s, nodes, list + level[k], count,
-                           b.pbox, ubox, b.words, seedBits, numNodes, b.numPrims);
+                           b.pbox, ubox, b.words, seedBits, numNodes, b.numPrims, padOut);
     }
 }
 
@@ -169,8 +172,8 @@ hipError_t launch_refit(const RefitBuffers &b, const std::vector<int> &level2, c
     hipError_t e = hipMemsetAsync(b.words, 0, 2 * sizeof(unsigned), s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(refit_prims, dim3((b.numPrims + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, s, b);
-    launch_levels<2>(b.nodes2, b.list2, level2, b, b.ubox2, seedBits, b.numNodes2, s);
-    launch_levels<4>(b.nodes4, b.list4, level4, b, b.ubox4, seedBits, b.numNodes4, s);
+    launch_levels<2>(b.nodes2, b.list2, level2, b, b.ubox2, seedBits, b.numNodes2, nullptr, s);
+    launch_levels<4>(b.nodes4, b.list4, level4, b, b.ubox4, seedBits, b.numNodes4, b.padOut, s);
     return hipGetLastError();
 }
 

@@ -12,6 +12,7 @@
 #include "bvh_builder.h"
 #include "hippt_chain_logic.h"
 #include "hippt_device.h"
+#include "hippt_slab.h"
 
 #pragma clang fp contract(off)
 
@@ -284,16 +285,15 @@ struct Ray {
     float ix, iy, iz, oix, oiy, oiz;  // box-test reciprocals (fast rcp; not result-defining)
 };
 
+// (the arithmetic: hippt_slab.h, shared with the host model of the box test)
 __device__ __forceinline__ void prepare(Ray &r) {
-    const float cx = copysignf(fmaxf(fabsf(r.dx), 1e-20f), r.dx);
-    const float cy = copysignf(fmaxf(fabsf(r.dy), 1e-20f), r.dy);
-    const float cz = copysignf(fmaxf(fabsf(r.dz), 1e-20f), r.dz);
+    const float cx = slab::clamp_dir(r.dx), cy = slab::clamp_dir(r.dy), cz = slab::clamp_dir(r.dz);
     r.ix = __builtin_amdgcn_rcpf(cx);
     r.iy = __builtin_amdgcn_rcpf(cy);
     r.iz = __builtin_amdgcn_rcpf(cz);
-    r.oix = r.ox * r.ix;
-    r.oiy = r.oy * r.iy;
-    r.oiz = r.oz * r.iz;
+    r.oix = slab::origin_term(r.ox, r.ix);
+    r.oiy = slab::origin_term(r.oy, r.iy);
+    r.oiz = slab::origin_term(r.oz, r.iz);
 }
 
 // A MeshParams field (the kernels' only argument, at kernarg offset 0) loaded where it is used: the
@@ -1125,14 +1125,7 @@ __device__ __forceinline__ int pop_wide(Trav &T, int *my, const SpillArea &S, un
     return PACKED ? key_code(unsigned(my[T.sp]), refBits) : my[T.sp];
 }
 
-// min(a, b) as one v_min_f32: fminf() of the loop-carried bestT makes the compiler quieten a
-// possible signaling NaN first (a v_max_f32 b, b per node visit); the box test has no NaN
-// (finite padded boxes, clamped reciprocals), and v_min_f32 of non-NaN inputs is fminf.
-__device__ __forceinline__ float fmin_raw(float a, float b) {
-    float d;
-    asm("v_min_f32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
-    return d;
-}
+using slab::fmin_raw;  // min(a, b) as one v_min_f32 (hippt_slab.h)
 
 // Sort key of a child box from its near and far planes on each axis (the ray's direction signs
 // choose them, see traverse_round_wide): entry distance bits (>= tmin > 0, so ordered as
@@ -1140,12 +1133,12 @@ __device__ __forceinline__ float fmin_raw(float a, float b) {
 // min/max ordering.
 __device__ __forceinline__ unsigned child_key(float nx, float fx, float ny, float fy, float nz, float fz,
                                               const Ray &r, float tmin, float bestT) {
-    const float ax = fmaf(nx, r.ix, -r.oix), bx = fmaf(fx, r.ix, -r.oix);
-    const float ay = fmaf(ny, r.iy, -r.oiy), by = fmaf(fy, r.iy, -r.oiy);
-    const float az = fmaf(nz, r.iz, -r.oiz), bz = fmaf(fz, r.iz, -r.oiz);
-    const float n = fmaxf(fmaxf(ax, ay), fmaxf(az, tmin));
-    const float f = fminf(fminf(bx, by), fmin_raw(bz, bestT));
-    return n <= f ? __float_as_uint(n) : 0xffffffffu;
+    const float ax = slab::plane_t(nx, r.ix, r.oix), bx = slab::plane_t(fx, r.ix, r.oix);
+    const float ay = slab::plane_t(ny, r.iy, r.oiy), by = slab::plane_t(fy, r.iy, r.oiy);
+    const float az = slab::plane_t(nz, r.iz, r.oiz), bz = slab::plane_t(fz, r.iz, r.oiz);
+    const float n = slab::entry_t(ax, ay, az, tmin);
+    const float f = slab::exit_t(bx, by, bz, bestT);
+    return HIPPT_SLAB_MEETS(n, f) ? __float_as_uint(n) : 0xffffffffu;
 }
 
 // child_key over a quantized node: byte I of each plane word (v_cvt_f32_ubyteI), scaled
@@ -1211,12 +1204,12 @@ template <bool PACKED>
 __device__ __forceinline__ unsigned child_key_p(float nx, float fx, float ny, float fy, float nz, float fz,
                                                 const Ray &r, float tmin, float bestT, int code, unsigned mask) {
     if (!PACKED) return child_key(nx, fx, ny, fy, nz, fz, r, tmin, bestT);
-    const float ax = fmaf(nx, r.ix, -r.oix), bx = fmaf(fx, r.ix, -r.oix);
-    const float ay = fmaf(ny, r.iy, -r.oiy), by = fmaf(fy, r.iy, -r.oiy);
-    const float az = fmaf(nz, r.iz, -r.oiz), bz = fmaf(fz, r.iz, -r.oiz);
-    const float n = fmaxf(fmaxf(ax, ay), fmaxf(az, tmin));
-    const float f = fminf(fminf(bx, by), fmin_raw(bz, bestT));
-    return n <= f ? (__float_as_uint(n) & ~mask) | unsigned(code) : 0xffffffffu;  // code: pre-masked
+    const float ax = slab::plane_t(nx, r.ix, r.oix), bx = slab::plane_t(fx, r.ix, r.oix);
+    const float ay = slab::plane_t(ny, r.iy, r.oiy), by = slab::plane_t(fy, r.iy, r.oiy);
+    const float az = slab::plane_t(nz, r.iz, r.oiz), bz = slab::plane_t(fz, r.iz, r.oiz);
+    const float n = slab::entry_t(ax, ay, az, tmin);
+    const float f = slab::exit_t(bx, by, bz, bestT);
+    return HIPPT_SLAB_MEETS(n, f) ? (__float_as_uint(n) & ~mask) | unsigned(code) : 0xffffffffu;  // code: pre-masked
 }
 
 __device__ __forceinline__ void cas_key(unsigned &ka, unsigned &kb) {

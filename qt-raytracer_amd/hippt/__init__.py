@@ -57,6 +57,7 @@ OPT_CHAIN = 30
 OPT_CHAIN_AUDIT = 31
 OPT_PIXEL_TILE = 32
 OPT_QUERY_SLICE = 33
+OPT_RENDER_PAD = 34
 OPT_PIXEL_FORMAT = 25
 PIXEL_ARGB = 0
 PIXEL_RGBA8 = 1
@@ -65,6 +66,7 @@ INFO_BLOCKS_PER_CU = 101
 INFO_CHUNK = 102
 INFO_CHAIN_CAP = 103
 INFO_UPDATE_DROPPED = 104
+INFO_RENDER_PAD = 105
 RAYS_DEVICE = 1
 HIT_SPHERE = 1 << 30
 HIT_BACKFACE = -(1 << 31)  # the int's sign bit
