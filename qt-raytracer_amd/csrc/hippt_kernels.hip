@@ -652,7 +652,8 @@ __global__ __launch_bounds__(kMeshBlock, (FULL || WIDE) ? HIPPT_WIDE_WAVES_PER_E
         if (!CAP || __any(busy(T))) do {
             prof<STATS>(pc, 2);
             if (WIDE)
-                traverse_round_wide<nodeF4, STATS, FULL, QUANT, SPILL, LDS_SCENE, TOP, HYBRID, PACKED, HALF>(
+                traverse_round_wide<nodeF4, STATS, FULL, QUANT, SPILL, LDS_SCENE, TOP, HYBRID, PACKED, HALF,
+                                    LDS_SCENE && !FULL>(
                     T, r, my, nodes, tris, nvis, ntest, pc, P.leafExit, P.nodeExit, S, P.topBytes, P.refBits);
             else
                 traverse_round<nodeF4, STATS, FULL>(T, r, my, nodes, tris, nvis, ntest, pc, P.leafExit, P.nodeExit);
@@ -704,8 +705,10 @@ __global__ __launch_bounds__(kMeshBlock, (FULL || WIDE) ? HIPPT_WIDE_WAVES_PER_E
                 finished = true;
             } else if (++depth >= P.maxDepth) {
                 finished = true;  // depth exhausted: contributes 0 (RayTracer.h:582-583)
-            } else if (scatter<FULL, STATS>(r, T.bestT, T.bestI, shade, tris, mats, rng, tr, tg, tb, pc,
-                                            P.rngTable)) {
+            } else if (scatter<FULL, STATS, CHAIN ? kRiusTail : -1>(r, T.bestT, T.bestI, shade, tris, mats, rng, tr, tg,
+                                                                    tb, pc, P.rngTable)) {
+                // (the unchained kernels keep rius's plain loop: the wave-level one costs the spill-free
+                // general LDS kernel a VGPR spill there)
                 fresh = true;
             } else {
                 finished = true;  // absorbed: contributes 0 (RayTracer.h:590)

@@ -83,6 +83,10 @@ __device__ __forceinline__ float rsqrt_unit_draw(float r2) {
     return r2 == 0.0f ? INFINITY : rcp_nr(sqrt_fix(r2));
 }
 
+// rius's scalar tail takes over once at most this many lanes of a wave are pending (measured: 1 gains,
+// 2 and 3 lose; DESIGN_LOG.md §A.D).
+constexpr int kRiusTail = 1;
+
 // Short-cycle escape of the rejection loops (pt_oracle.c PO_ESCAPE).
 __device__ __forceinline__ void escape_cycle(uint32_t &s, unsigned tries) {
     if ((tries & 63u) == 0u) s ^= 0x9E3779B9u;
@@ -727,7 +731,10 @@ __device__ __forceinline__ void sky(const Ray &r, float tr, float tg, float tb, 
 // Measured (r2zd): Cornell -3%, blob70k -18%, random_scene -8%, cornell_mixed +8% — the random
 // 4-byte reads over 16 GiB cost more than the loop's tail; loading the entry when the segment's
 // ray starts (latency behind the traversal) was worse still (Cornell -15%).  Off by default.
-template <bool STATS>
+// TAIL < 0: the plain per-lane loop (the wavefront's shade kernel keeps it).  TAIL >= 0: the
+// wave-level loop below, bit for bit the same draws (Cornell -1.5%, cornell_mixed
+// -1.5% at TAIL = 1).
+template <bool STATS, int TAIL = kRiusTail>
 __device__ __forceinline__ float rius(uint32_t &rng, float &rx, float &ry, float &rz, unsigned *pc,
                                       const uint32_t *table = nullptr) {
     if (table) {
@@ -738,15 +745,70 @@ __device__ __forceinline__ float rius(uint32_t &rng, float &rx, float &ry, float
         rz = rand_pm1(rng);
         return fmaf(rx, rx, fmaf(ry, ry, rz * rz));
     }
-    float r2;
-    for (unsigned tries = 1;; ++tries) {
-        prof<STATS>(pc, 7);
-        rx = rand_pm1(rng);
-        ry = rand_pm1(rng);
-        rz = rand_pm1(rng);
-        r2 = fmaf(rx, rx, fmaf(ry, ry, rz * rz));
-        if (r2 < 1.0f) break;
-        escape_cycle(rng, tries);
+    float r2 = 2.0f;  // pending
+    if (TAIL < 0) {
+        for (unsigned tries = 1;; ++tries) {
+            prof<STATS>(pc, 7);
+            rx = rand_pm1(rng);
+            ry = rand_pm1(rng);
+            rz = rand_pm1(rng);
+            r2 = fmaf(rx, rx, fmaf(ry, ry, rz * rz));
+            if (r2 < 1.0f) break;
+            escape_cycle(rng, tries);
+        }
+        return r2;
+    }
+    // Vector loop: every lane still pending draws one candidate per pass.  The pending lanes are
+    // a wave-uniform mask `pm` (one compare per pass makes it, and it masks the next pass and the
+    // escape directly); `tries` is the wave's (every lane enters at try 1), so the escape is a
+    // scalar branch taken once in 64 passes.  The loop ends once at most TAIL lanes are pending.
+    unsigned tries = 0;
+    unsigned long long pm = __ballot(1);
+    do {
+        ++tries;
+        if (__builtin_amdgcn_inverse_ballot_w64(pm)) {
+            prof<STATS>(pc, 7);
+            rx = rand_pm1(rng);
+            ry = rand_pm1(rng);
+            rz = rand_pm1(rng);
+            r2 = fmaf(rx, rx, fmaf(ry, ry, rz * rz));
+        }
+        pm = __ballot(!(r2 < 1.0f));
+        if (__builtin_expect((tries & 63u) == 0u, 0)) {  // escape_cycle, wave-uniform
+            asm volatile("");  // keeps the branch: no select in every pass
+            if (__builtin_amdgcn_inverse_ballot_w64(pm)) rng ^= 0x9E3779B9u;
+        }
+        // (two 32-bit counts: the 64-bit count's compare is a vector instruction)
+    } while (__popc(unsigned(pm)) + __popc(unsigned(pm >> 32)) > TAIL);
+    // Scalar tail: the last lanes' chains, one lane at a time, as wave-uniform code (the hash is
+    // integer multiply, shift, xor: scalar instructions) instead of vector passes for one or two
+    // lanes.  The same draws, acceptance test and escape points: try numbers go on from `tries`.
+    while (TAIL > 0 && pm) {
+        const int lane = __ffsll(pm) - 1;
+        pm &= pm - 1ull;
+        uint32_t s = uint32_t(__builtin_amdgcn_readlane(int(rng), lane));
+        float x, y, z, q;
+        unsigned t = tries;
+        for (;;) {
+            ++t;
+            x = rand_pm1(s);
+            y = rand_pm1(s);
+            z = rand_pm1(s);
+            q = fmaf(x, x, fmaf(y, y, z * z));
+            if (q < 1.0f) break;
+            escape_cycle(s, t);
+        }
+        if (int(__lane_id()) == lane) {
+            rng = s;
+            rx = x;
+            ry = y;
+            rz = z;
+            r2 = q;
+            if (STATS) {  // the tail's tries, on the lane they belong to
+                pc[2 * 7] += t - tries;
+                pc[2 * 7 + 1] += t - tries;
+            }
+        }
     }
     return r2;
 }
@@ -773,8 +835,8 @@ __device__ __forceinline__ float rius_capped(uint32_t &rng, float &rx, float &ry
 // Scatter at the closest hit (ray_color :585-590 + the material's scatter, :473-540) of
 // primitive `prim` at t.  The ray becomes the scattered ray and the throughput takes the
 // attenuation; false = absorbed (Metal below the surface), which contributes 0.  FULL=false
-// is the Lambertian-triangle specialisation (no sphere normals, no material dispatch).
-template <bool FULL, bool STATS>
+// is the Lambertian-triangle specialisation (no sphere normals, no material dispatch).  TAIL: rius's.
+template <bool FULL, bool STATS, int TAIL = kRiusTail>
 __device__ __forceinline__ bool scatter(Ray &r, float t, int prim, const float4 *shade, const float4 *prims,
                                         const float4 *mats, uint32_t &rng, float &tr, float &tg, float &tb,
                                         unsigned *pc, const uint32_t *rngTable = nullptr) {
@@ -804,7 +866,7 @@ __device__ __forceinline__ bool scatter(Ray &r, float t, int prim, const float4 
         const float ux = r.dx * il, uy = r.dy * il, uz = r.dz * il;
         const float k = 2.0f * fdot(ux, uy, uz, nx, ny, nz);  // reflect, :174-176
         float qx, qy, qz;
-        rius<STATS>(rng, qx, qy, qz, pc, rngTable);
+        rius<STATS, TAIL>(rng, qx, qy, qz, pc, rngTable);
         sx = (ux - k * nx) + fuzz * qx;
         sy = (uy - k * ny) + fuzz * qy;
         sz = (uz - k * nz) + fuzz * qz;
@@ -840,7 +902,7 @@ __device__ __forceinline__ bool scatter(Ray &r, float t, int prim, const float4 
         }
     } else {  // Lambertian::scatter, :477-484: n + unit(random_in_unit_sphere), 1e-8 fallback
         float qx, qy, qz;
-        const float r2 = rius<STATS>(rng, qx, qy, qz, pc, rngTable);
+        const float r2 = rius<STATS, TAIL>(rng, qx, qy, qz, pc, rngTable);
         const float inv = rsqrt_unit_draw(r2);  // unit_vector = (1/len)*v, :137-139,151-153
         sx = nx + qx * inv;
         sy = ny + qy * inv;
@@ -953,13 +1015,32 @@ __device__ __forceinline__ void take_hit(Trav &T, float tt, bool ok, int i, int 
     T.bestO = win ? orig : T.bestO;
 }
 
+// A lane's triangle candidate of the leaf under test whose division is still owed (leaf_step's
+// DEFER form): t = num / det of primitive idx (leaf order); idx < 0 = none.
+struct PendingHit {
+    float num, det;
+    int idx;
+};
+
+// The owed take_hit of a pending candidate: the same division, operands and id as the immediate
+// form's (the original id is the primitive record's third row, .y).
+__device__ __forceinline__ void resolve_pending(Trav &T, const float4 *tris, PendingHit &H, float tmin) {
+    take_hit(T, H.num / H.det, true, H.idx, __float_as_int(tris[3 * H.idx + 2].y), tmin);
+    H.idx = -1;
+}
+
 // Primitive i (leaf order) against the ray: closest hit = min (t, primitive id).
-template <bool STATS, bool FULL>
+// DEFER: a triangle that passes the edge tests becomes the lane's pending candidate H instead of
+// paying its division here; a candidate already pending is resolved first, so the candidates
+// reach take_hit in the same order with the same operands.
+template <bool STATS, bool FULL, bool DEFER = false>
 __device__ __forceinline__ void test_prim_data(Trav &T, const Ray &r, float4 A, float4 B, float4 Cc, int i,
-                                               unsigned long long &ntest, unsigned *pc, float tmin = 0.001f) {
+                                               unsigned long long &ntest, unsigned *pc, float tmin = 0.001f,
+                                               const float4 *tris = nullptr, PendingHit *H = nullptr) {
     prof<STATS>(pc, 5);
     if (STATS) ++ntest;
     if (FULL && __float_as_int(Cc.z) != 0) {
+        if (DEFER && H->idx >= 0) resolve_pending(T, tris, *H, tmin);
         float tt = 0.0f;
         const bool hit = sphere_t(A, B.x, r, tmin, tt);
         take_hit(T, tt, hit, i, __float_as_int(Cc.y), tmin);
@@ -981,23 +1062,37 @@ __device__ __forceinline__ void test_prim_data(Trav &T, const Ray &r, float4 A, 
     const bool neg = det < 0.0f;
     const float us = neg ? -un : un, vs = neg ? -vn : vn;
     const bool inside = (det != 0.0f) & (us >= 0.0f) & (vs >= 0.0f) & (us + vs <= fabsf(det));
+    if (DEFER) {
+        // one division per leaf step: a wave whose lanes hit different primitives of the leaf
+        // ran the division branch once per primitive, each lane needing it once
+        if (inside) {
+            if (H->idx >= 0) resolve_pending(T, tris, *H, tmin);  // rare: a second candidate of this lane
+            H->num = fdot(e2x, e2y, e2z, qvx, qvy, qvz);
+            H->det = det;
+            H->idx = i;
+        }
+        return;
+    }
     // (the division for every lane, without this branch: blob70k -1%, DESIGN_LOG.md §A.0)
     if (inside) take_hit(T, fdot(e2x, e2y, e2z, qvx, qvy, qvz) / det, true, i, __float_as_int(Cc.y), tmin);
 }
 
-template <bool STATS, bool FULL>
+template <bool STATS, bool FULL, bool DEFER = false>
 __device__ __forceinline__ void test_prim(Trav &T, const Ray &r, const float4 *tris, int i, unsigned long long &ntest,
-                                          unsigned *pc, float tmin = 0.001f) {
+                                          unsigned *pc, float tmin = 0.001f, PendingHit *H = nullptr) {
     const float4 *tp = tris + 3 * i;
-    test_prim_data<STATS, FULL>(T, r, tp[0], tp[1], tp[2], i, ntest, pc, tmin);
+    test_prim_data<STATS, FULL, DEFER>(T, r, tp[0], tp[1], tp[2], i, ntest, pc, tmin, tris, H);
 }
 
 // One leaf-loop iteration for this lane: the primitives of leaf T.leaf, then the next leaf if it
 // is next in line on the stack.  (Measured and rejected: one primitive per lane per iteration,
 // so that lanes with short leaves move on: Cornell -9%, blob70k -5%.)
-template <bool STATS, bool FULL, typename Pop, bool PAIRS = false>
+// DEFER (the one-primitive-per-iteration loop only): the leaf's triangle candidates pay one
+// division after the primitive loop (test_prim_data).
+template <bool STATS, bool FULL, typename Pop, bool PAIRS = false, bool DEFER = false>
 __device__ __forceinline__ void leaf_step(Trav &T, const Ray &r, const float4 *tris, unsigned long long &ntest,
                                           unsigned *pc, Pop pop, float tmin = 0.001f) {
+    static_assert(!(PAIRS && DEFER), "the deferred division: the single-primitive loop");
     const int code = ~T.leaf;
     const int first = code >> 4, last = first + (code & 15);
     if (PAIRS) {
@@ -1016,6 +1111,12 @@ __device__ __forceinline__ void leaf_step(Trav &T, const Ray &r, const float4 *t
             test_prim_data<STATS, FULL>(T, r, A0, B0, C0, i, ntest, pc, tmin);
             if (two) test_prim_data<STATS, FULL>(T, r, A1, B1, C1, i + 1, ntest, pc, tmin);
         }
+    } else if (DEFER) {
+        PendingHit H;
+        H.num = H.det = 0.0f;
+        H.idx = -1;
+        for (int i = first; i < last; ++i) test_prim<STATS, FULL, true>(T, r, tris, i, ntest, pc, tmin, &H);
+        if (H.idx >= 0) resolve_pending(T, tris, H, tmin);
     } else {
         for (int i = first; i < last; ++i) test_prim<STATS, FULL>(T, r, tris, i, ntest, pc, tmin);
     }
@@ -1236,7 +1337,7 @@ __device__ __forceinline__ void cas_key(unsigned &ka, unsigned &kb) {
 // half-precision planes, each axis's near and far planes one aligned 16-byte read (4 reads per
 // visit instead of 7 where the TA binds), the slab FMAs taking the halves directly (v_fma_mix_f32).
 template <int NODE_F4, bool STATS, bool FULL, bool QUANT = false, bool SPILL = true, bool LDS0 = false,
-          bool TOP = false, bool HYBRID = false, bool PACKED = false, bool HALF = false>
+          bool TOP = false, bool HYBRID = false, bool PACKED = false, bool HALF = false, bool DEFER = false>
 __device__ __forceinline__ void traverse_round_wide(Trav &T, const Ray &r, int *my, const float4 *nodes,
                                                     const float4 *tris, unsigned long long &nvis,
                                                     unsigned long long &ntest, unsigned *pc, unsigned leafExit,
@@ -1246,6 +1347,7 @@ __device__ __forceinline__ void traverse_round_wide(Trav &T, const Ray &r, int *
     static_assert(!HYBRID || (QUANT && TOP), "hybrid trees: 8-bit nodes below an LDS top");
     static_assert(!PACKED || (LDS0 && !QUANT), "packed keys: LDS-resident float trees");
     static_assert(!HALF || (TOP && !QUANT && !LDS0), "half planes: 4-wide trees in global memory");
+    static_assert(!DEFER || LDS0, "the deferred division: LDS-resident trees");
     const unsigned refMask = PACKED ? (1u << refBits) - 1u : 0u;
     // near-row byte offsets of this ray's octant within a node (x at 0/16, y at 32/48, z at 64/80)
     const unsigned sx = near_row(r.ix), sy = near_row(r.iy) | 32u, sz = near_row(r.iz) | 64u;
@@ -1391,7 +1493,7 @@ __device__ __forceinline__ void traverse_round_wide(Trav &T, const Ray &r, int *
     auto popw = [&] { return pop_wide<SPILL, PACKED>(T, my, S, refBits); };
     while (T.leaf != 0) {
         prof<STATS>(pc, 4);
-        leaf_step<STATS, FULL, decltype(popw), !LDS0>(T, r, tris, ntest, pc, popw, tmin);
+        leaf_step<STATS, FULL, decltype(popw), !LDS0, DEFER>(T, r, tris, ntest, pc, popw, tmin);
         if (nodeExit && __popcll(__ballot(T.leaf != 0)) <= nodeExit) break;
     }
 }

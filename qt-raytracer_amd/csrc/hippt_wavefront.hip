@@ -260,8 +260,8 @@ __global__ __launch_bounds__(kWfBlock) void wf_shade(WfParams W, int cur) {
             finished = true;
         } else if (++q.depth >= P.maxDepth) {
             finished = true;
-        } else if (scatter<FULL, false>(q.r, h.x, tri, P.shade, P.tris, P.mats, q.rng, q.tr, q.tg, q.tb, nullptr,
-                                        P.rngTable)) {
+        } else if (scatter<FULL, false, -1>(q.r, h.x, tri, P.shade, P.tris, P.mats, q.rng, q.tr, q.tg, q.tb, nullptr,
+                                            P.rngTable)) {  // (-1: rius's plain loop, measured equal here)
             again = true;
         } else {
             finished = true;  // absorbed: contributes 0

@@ -1,0 +1,13 @@
+# tests/native/draw.mk — the unit-sphere draw's GPU test helper (tests/test_gpu_unit_draw.py).
+HIPCC ?= /opt/rocm/bin/hipcc
+HERE := $(dir $(abspath $(lastword $(MAKEFILE_LIST))))
+CSRC := $(HERE)../../qt-raytracer_amd/csrc
+# the product's arithmetic flags (qt-raytracer_amd/Makefile)
+FLAGS := --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-slp-vectorize -I$(CSRC) -I$(HERE)../../include
+
+all: $(HERE)libdraw_selftest.so
+
+$(HERE)libdraw_selftest.so: $(HERE)draw_selftest.hip $(CSRC)/hippt_trace.h
+	$(HIPCC) $(FLAGS) -shared -o $@ $<
+
+.PHONY: all
