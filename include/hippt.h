@@ -362,6 +362,20 @@ enum {
                                        copy has caught up); otherwise, and for trees in global memory, the
                                        wavefront path and the ray queries, the builder's pad stays
                                        (HIPPT_INFO_RENDER_PAD: 0).  Same results either way */
+    , HIPPT_OPT_SKY_RECT = 35       /* camera-pool render megakernels: 1 (default) a sample whose pixel lies
+                                       outside the screen rectangle the scene's bounding box projects into
+                                       (widened by a pixel) is finished as a sky miss without a traversal,
+                                       where a wave's 64 new work items are all of that kind; 0: every sample
+                                       is traced.  The rectangle follows the camera (hipptSetCamera) and the
+                                       scene; none for a lens camera (aperture != 0), a camera inside or beside
+                                       the scene's box, a camera so far away for its focus distance that the
+                                       rounding of a ray's direction is more than a quarter of a pixel, the one
+                                       camera-pool kernel without the path (the unchained general kernel over an
+                                       LDS-resident tree whose stack spills), or while a hipptUpdateVertices is ahead of the host copy
+                                       (from device memory, or of a scene too large for the LDS copy;
+                                       HIPPT_INFO_SKY_RECT_PIXELS: 0).  Same results either way;
+                                       with HIPPT_OPT_COUNT_TRAVERSAL, nodeVisits counts only the traversals
+                                       made */
 };
 /* Records of the chained runs closed since the last call (HIPPT_OPT_CHAIN_AUDIT), as 32-bit words:
  * per run a 16-word header  [0] 0xC4A1D17 [1] run id [2] device [3] batch 0's first frame [4] frames
@@ -386,12 +400,15 @@ enum { HIPPT_PIXEL_ARGB = 0, HIPPT_PIXEL_RGBA8 = 1 };
 /* Read-only (hipptGetOption) facts of the last megakernel render: LDS bytes of the top of the tree,
  * persistent-grid blocks per CU, work items per claim (HIPPT_OPT_CHUNK as applied), batches a launch
  * may trace (HIPPT_OPT_CHAIN as applied: 0 = the batch was not chained), the node-box pad exponent of
- * the LDS scene copy (HIPPT_OPT_RENDER_PAD as applied: 0 = the builder's pad, no trim). */
+ * the LDS scene copy (HIPPT_OPT_RENDER_PAD as applied: 0 = the builder's pad, no trim), the image
+ * pixels outside the sky rectangle (HIPPT_OPT_SKY_RECT as applied: 0 = no rectangle, every sample
+ * traced). */
 enum { HIPPT_INFO_LDS_TOP_BYTES = 100, HIPPT_INFO_BLOCKS_PER_CU = 101, HIPPT_INFO_CHUNK = 102,
        HIPPT_INFO_CHAIN_CAP = 103,
        HIPPT_INFO_UPDATE_DROPPED = 104 /* triangles the last device-memory hipptUpdateVertices dropped
                                           for a non-finite coordinate; reading it synchronises */,
-       HIPPT_INFO_RENDER_PAD = 105 };
+       HIPPT_INFO_RENDER_PAD = 105,
+       HIPPT_INFO_SKY_RECT_PIXELS = 106 };
 bool hipptSetOption(int key, long long value);
 long long hipptGetOption(int key);
 /* BVH width (2 or 4) the last mesh render traversed (0 before any): what nodeVisits count. */

@@ -34,6 +34,7 @@
 #include "hippt_device.h"
 #include "hippt_query.h"
 #include "hippt_refit.h"
+#include "hippt_sky_rect.h"
 #include "hippt_slab.h"
 #include "hippt_wavefront.h"
 
@@ -323,6 +324,7 @@ struct State {
     int chainBatches = -1; // batches a chained launch may trace (HIPPT_OPT_CHAIN; 0 off, -1 automatic)
     bool chainAudit = false;            // HIPPT_OPT_CHAIN_AUDIT
     int renderPad = hippt::slab::kRenderPadDefault;  // HIPPT_OPT_RENDER_PAD (0: the builder's pad)
+    bool skyRect = true;                // HIPPT_OPT_SKY_RECT
     long long querySlice = 0;           // rays per staged slice of a host-memory query (HIPPT_OPT_QUERY_SLICE; 0 automatic)
     std::vector<unsigned> auditWords;   // closed runs' audit words not yet read (hipptChainAudit)
     std::vector<std::pair<int, uint32_t *>> rngTables;  // per device, built on first use
@@ -354,6 +356,7 @@ struct State {
     int activeBlocksPerCu = 0;
     int activeChunk = 0;     // the last megakernel batch's claim size
     int activeChainCap = 0;  // its run's chain cap (0: not chained)
+    long long activeSkyPixels = 0;  // its image pixels outside the sky rectangle (HIPPT_OPT_SKY_RECT as applied; 0: off)
     int activeRenderPad = 0; // its LDS scene copy's pad exponent (HIPPT_OPT_RENDER_PAD as applied; 0: no trim)
     int activeWidth = 0;  // BVH width of the last mesh render (hipptActiveBvhWidth)
     int blocksPerCu = 0;
@@ -860,6 +863,27 @@ bool render_pad_holds(const SceneHost &sc, bool hostStale, const CameraF &cam) {
     for (int k = 0; k < 3; ++k) o = std::max(o, std::fabs(cam.origin[k]));
     const float reach = o + 1.5f * std::fabs(cam.lens_radius);  // (a lens offset's component: at most sqrt(2) radii)
     return std::isfinite(reach) && reach <= M && sc.minEdgeSine >= kRenderPadMinSine;
+}
+
+// The sky rectangle of a batch (HIPPT_OPT_SKY_RECT; hippt_sky_rect.h): from the camera
+// the kernel gets and the host tree's root box (the 2-wide root's child boxes, as the builder or the
+// last host refit padded them; every 4-wide box lies inside).  The whole image when the bound does not
+// apply.  The caller leaves it off while a vertex update is not in the host copy yet.
+hippt::skyrect::Rect sky_rect_of(const SceneHost &sc, const CameraF &cam, int width, int height) {
+    const hippt::skyrect::Rect all = hippt::skyrect::whole(width, height);
+    if (sc.bvh2.nodes.size() < size_t(hippt::kNodeWords)) return all;
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    bool any = false;
+    for (int slot = 0; slot < 2; ++slot) {
+        if (int32_t(sc.bvh2.nodes[size_t(hippt::node_code_word(2, slot))]) == hippt::leaf_code(0, 0)) continue;
+        any = true;
+        for (int a = 0; a < 3; ++a) {
+            lo[a] = std::min(lo[a], as_float(int(sc.bvh2.nodes[size_t(hippt::node_lo_word(2, slot, a))])));
+            hi[a] = std::max(hi[a], as_float(int(sc.bvh2.nodes[size_t(hippt::node_hi_word(2, slot, a))])));
+        }
+    }
+    if (!any) return all;
+    return hippt::skyrect::sky_rect(cam, width, height, lo, hi, sc.pad, sc.numTris);
 }
 
 // Low bits of a packed child key (trace::child_key_p) that give an LDS-resident 4-wide tree's child
@@ -1507,7 +1531,8 @@ bool chain_same(const hippt::MeshParams &a, const hippt::MeshParams &b) {
            a.spill == b.spill && a.topBytes == b.topBytes && a.refBits == b.refBits && a.runOrder == b.runOrder &&
            a.runCount == b.runCount && a.runTileShift == b.runTileShift && a.rngTable == b.rngTable && a.poolOffset == b.poolOffset &&
            a.poolWords == b.poolWords && a.comb.format == b.comb.format && a.padWord == b.padWord &&
-           a.trimScale == b.trimScale;
+           a.trimScale == b.trimScale && a.skyRect.x0 == b.skyRect.x0 && a.skyRect.y0 == b.skyRect.y0 &&
+           a.skyRect.x1 == b.skyRect.x1 && a.skyRect.y1 == b.skyRect.y1;
 }
 
 // Enqueues the launch of chained batch p (its chain fields set by chain_batch but the epoch): the run's
@@ -1959,6 +1984,16 @@ bool enqueue_locked(int firstFrame, int count, int maxDepth, bool copy, const ch
                         p.stackCap = stackCap;
                         p.topBytes = topBytes;
                         p.refBits = ldsScene && wide ? packed_ref_bits(numNodes, numTris) : 0u;
+                        // The sky rectangle (below) needs the host copy's root box.  A host-memory vertex
+                        // update's vertices are on the host already: for a scene that fits the LDS copy the
+                        // host copy takes them here, a refit of a few hundred primitives, before anything of
+                        // this batch looks at it; a larger scene's waits for whatever next needs the host
+                        // copy (blob70k's host refit takes 10 ms).
+                        // (the one camera-pool kernel without the sky path, hippt_kernels.hip SKY: the timed
+                        // unchained general LDS kernel with the spilling stack)
+                        const bool skyWanted = s.pathMode == 0 && poolWords != 0 && s.skyRect &&
+                                               !(s.scene.full && ldsScene && spills && !chained && !cnt);
+                        if (skyWanted && ldsScene && s.upd.hostStale && !s.upd.staleEv) settle_scene();
                         // the LDS scene copy's node boxes trimmed to the render pad (HIPPT_OPT_RENDER_PAD;
                         // megakernel over an LDS-resident 4-wide float tree only)
                         const bool trims = s.pathMode == 0 && ldsScene && fmt == hippt::kWideFloat && s.renderPad != 0 &&
@@ -1966,6 +2001,14 @@ bool enqueue_locked(int firstFrame, int count, int maxDepth, bool copy, const ch
                         p.padWord = c.padDev;
                         p.trimScale = trims ? hippt::slab::trim_scale(s.renderPad) : 0.0f;
                         s.activeRenderPad = trims ? s.renderPad : 0;
+                        // camera-pool megakernels: samples of pixels that cannot see the scene skip the
+                        // traversal (HIPPT_OPT_SKY_RECT).  Not while a device-memory vertex update is
+                        // ahead of the host copy (the scene may have grown past the host's root box).
+                        const bool skyOn = skyWanted && !s.upd.hostStale;
+                        const hippt::skyrect::Rect sr = skyOn ? sky_rect_of(s.scene, cam, s.width, s.height)
+                                                              : hippt::skyrect::whole(s.width, s.height);
+                        p.skyRect = hippt::SkyRect{sr.x0, sr.y0, sr.x1, sr.y1};
+                        s.activeSkyPixels = hippt::skyrect::pixels_outside(sr, s.width, s.height);
                         p.rngTable = nullptr;
                         p.poolWords = poolWords;
                         // Pixel runs by estimated sample length, longest first, per XCD queue
@@ -3256,6 +3299,10 @@ extern "C" bool hipptSetOption(int key, long long value) try {
         if (value != 0 && (value < hippt::slab::kRenderPadMin || value > hippt::slab::kRenderPadMax)) return false;
         s.renderPad = int(value);
         return true;
+    case HIPPT_OPT_SKY_RECT:
+        if (value != 0 && value != 1) return false;
+        s.skyRect = value == 1;
+        return true;
     default: return false;
     }
 } catch (const std::exception &e) {
@@ -3310,11 +3357,13 @@ extern "C" long long hipptGetOption(int key) try {
     case HIPPT_OPT_PIXEL_TILE: return s.pixelTile;
     case HIPPT_OPT_QUERY_SLICE: return s.querySlice;
     case HIPPT_OPT_RENDER_PAD: return s.renderPad;
+    case HIPPT_OPT_SKY_RECT: return s.skyRect ? 1 : 0;
     case HIPPT_INFO_LDS_TOP_BYTES: return s.activeTopBytes;
     case HIPPT_INFO_BLOCKS_PER_CU: return s.activeBlocksPerCu;
     case HIPPT_INFO_CHUNK: return s.activeChunk;
     case HIPPT_INFO_CHAIN_CAP: return s.activeChainCap;
     case HIPPT_INFO_RENDER_PAD: return s.activeRenderPad;
+    case HIPPT_INFO_SKY_RECT_PIXELS: return s.activeSkyPixels;
     case HIPPT_INFO_UPDATE_DROPPED:
         // the last update's count, from the first context that ran it (every context counts the same)
         for (Ctx &c : s.ctxs) {

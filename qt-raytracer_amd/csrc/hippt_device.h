@@ -46,6 +46,11 @@ struct HostFrame {
     int width, y0, stride;
 };
 
+// Image pixels [x0, x1) x [y0, y1) (skyrect::Rect, hippt_sky_rect.h)
+struct SkyRect {
+    int x0, y0, x1, y1;
+};
+
 // Mesh megakernel: one persistent grid drains `totalItems` (pixel, frame) samples of the band's
 // rows and frames [firstFrame, firstFrame+frames).
 struct MeshParams {
@@ -144,6 +149,10 @@ struct MeshParams {
     // trimScale 0: no trim (padWord is not read).
     const float *padWord;
     float trimScale;
+    // HIPPT_OPT_SKY_RECT (camera-pool kernels; hippt_sky_rect.h): image pixels outside it cannot see
+    // the scene, and a pool refill whose 64 items all lie outside finishes them without a traversal.
+    // The whole image: nothing is skipped.
+    SkyRect skyRect;
 };
 
 // Chained batches: the control block (unsigned words).  Ring slot k's block at k * kChainBlockWords:

@@ -216,6 +216,13 @@ __device__ unsigned long long g_rate[kRateSlots * kRateBuckets * 5];
 #define HIPPT_PACKED_KEYS 1
 #endif
 
+// Sky rectangle (HIPPT_OPT_SKY_RECT): runs of 64 sky-certain items a wave finishes per trip through
+// the main loop before its busy lanes go on (sweep: DESIGN_LOG.md §A.S: 1 of 1, 2, 4, 8)
+#ifndef HIPPT_SKY_RUNS
+#define HIPPT_SKY_RUNS 1
+#endif
+constexpr unsigned kSkyRunsPerTrip = HIPPT_SKY_RUNS;
+
 // Build knob (experiment): the camera sample's and item order's arguments loaded where a wave
 // generates camera rays instead of held in registers across the kernel (trace::late_arg_at).
 #ifndef HIPPT_LATE_CAM
@@ -483,6 +490,10 @@ __global__ __launch_bounds__(kMeshBlock, (FULL || WIDE) ? HIPPT_WIDE_WAVES_PER_E
     // 3.36 -> 3.27 ms, full size unchanged; LDS scenes lose 1% on the share and keep the exit
     // (DESIGN_LOG.md §A.1)
     constexpr bool FINISH = POOL && !LDS_SCENE;
+    // Sky rectangle (HIPPT_OPT_SKY_RECT): every camera-pool kernel but the timed unchained general LDS
+    // kernel with the spilling stack, which can only take the path with 12 more bytes of VGPR spills
+    // (profiles/sky_rect/regs.txt) and keeps tracing every sample (the host gives it no rectangle)
+    constexpr bool SKY = POOL && !(FULL && LDS_SCENE && SPILL && !CHAIN && !STATS);
 #ifdef HIPPT_DEBUG_RATE
     const unsigned long long rtStart = __builtin_amdgcn_s_memrealtime();
     unsigned rtBucket = 0, rtSegs0 = 0, rtSamples0 = 0;
@@ -507,6 +518,7 @@ __global__ __launch_bounds__(kMeshBlock, (FULL || WIDE) ? HIPPT_WIDE_WAVES_PER_E
     };
 #endif
     unsigned waveThr = unsigned(P.waveThreshold);
+    unsigned skyRuns = 0;  // (wave-uniform) sky runs finished since the last traversal round
     bool combLeft = CHAIN ? int(__builtin_amdgcn_readfirstlane(cw->c1)) >= int(__builtin_amdgcn_readfirstlane(cw->c0))
                           : P.comb.bandPixels != 0;
     auto comb_step = [&]() { return CHAIN ? combine_chunk_chain(cw) : combine_chunk(P); };
@@ -526,6 +538,7 @@ __global__ __launch_bounds__(kMeshBlock, (FULL || WIDE) ? HIPPT_WIDE_WAVES_PER_E
         }
 #endif
         // ---- refill: every lane whose sample ended takes the next (pixel, frame) -------------
+        bool skyHeld = false;  // (wave-uniform) this trip finished a sky run: lanes are left without an item
         if (POOL) {
             const unsigned long long m = __ballot(need);
             if (m) {
@@ -542,6 +555,8 @@ __global__ __launch_bounds__(kMeshBlock, (FULL || WIDE) ? HIPPT_WIDE_WAVES_PER_E
                     unsigned it;
                     Ray c{};
                     uint32_t crng = 0;
+                    float cs = 0.0f, ct = 0.0f;  // the sample's image-plane point (camera_pixel)
+                    bool skyLane = false;        // the item's pixel is sky-certain (HIPPT_OPT_SKY_RECT)
                     if constexpr (CHAIN) {
                         // items of the wave's batch (ChainWave::t); a drained batch moves the wave into
                         // the run's next one (chain_next) and the lanes still without an item take its
@@ -570,7 +585,9 @@ __global__ __launch_bounds__(kMeshBlock, (FULL || WIDE) ? HIPPT_WIDE_WAVES_PER_E
                             // the item's frames: its batch's offset from the launch's own batch's
                             const int step = int(__builtin_amdgcn_readfirstlane(unsigned(cw->step)));
                             const unsigned fAdd = chain::frame_add(tItem, late_field(chainSeq), step);
-                            camera_sample(cam_args_late(), it, c, crng, fAdd);
+                            unsigned px, py;
+                            camera_pixel(cam_args_late(), it, crng, fAdd, px, py, cs, ct);
+                            if (SKY) skyLane = sky_certain(px, py);
                             if (unsigned *const audit = late_field(chainAudit))
                                 audit_trace(audit, tItem, it, unsigned(late_field(firstFrame)) + fAdd,
                                             late_field(chainEpoch));
@@ -580,10 +597,12 @@ __global__ __launch_bounds__(kMeshBlock, (FULL || WIDE) ? HIPPT_WIDE_WAVES_PER_E
                         it = HIPPT_LATE_CAM ? order_item_late(queue_fetch(true, Q, P.queue, P.totalItems, P.chunk, true, drained))
                                             : order_item(P, queue_fetch(true, Q, P.queue, P.totalItems, P.chunk, true, drained));
                         if (it != kNone) {
+                            unsigned px, py;
                             if (HIPPT_LATE_CAM)
-                                camera_sample(cam_args_late(), it, c, crng);
+                                camera_pixel(cam_args_late(), it, crng, 0u, px, py, cs, ct);
                             else
-                                camera_sample(P, it, c, crng);
+                                camera_pixel(P, it, crng, 0u, px, py, cs, ct);
+                            if (SKY) skyLane = sky_certain(px, py);
                         }
                     }
 #ifdef HIPPT_DEBUG_TIMELINE
@@ -591,21 +610,54 @@ __global__ __launch_bounds__(kMeshBlock, (FULL || WIDE) ? HIPPT_WIDE_WAVES_PER_E
                     tlItems += __popcll(__ballot(it != kNone));
 #endif
                     if (it != kNone) prof<STATS>(pc, 1);
-                    const unsigned k = __lane_id();
-                    pool[k] = __uint_as_float(it);
-                    pool[64 + k] = __uint_as_float(crng);
-                    pool[128 + k] = c.dx;
-                    pool[192 + k] = c.dy;
-                    pool[256 + k] = c.dz;
-                    if (P.poolWords == kPoolWordsFull) {
-                        pool[320 + k] = c.ox;
-                        pool[384 + k] = c.oy;
-                        pool[448 + k] = c.oz;
-                    }
-                    poolNext = n - avail;
-                    if (need) {
-                        need = false;
-                        pool_take<POOL>(P, pool, rank - avail, item, r, rng);
+                    // Sky rectangle: 64 items that are all valid and all of sky-certain
+                    // pixels are finished here, by the shading step's own miss arithmetic at depth 0, on
+                    // the pinhole's direction without the lens draw (the rectangle exists for a pinhole
+                    // only; the sample ends here, so its RNG state is not needed); nothing of them enters
+                    // the pool.  The lanes still without an item keep `need` and the wave comes back for
+                    // its next 64 (skyHeld, below).
+                    if (SKY && __ballot(skyLane) == ~0ull) {
+                        if (CHAIN || HIPPT_LATE_CAM)
+                            camera_dir_pinhole(late_field(cam), cs, ct, c);
+                        else
+                            camera_dir_pinhole(P.cam, cs, ct, c);
+                        float Lr, Lg, Lb;
+                        if (!FULL)
+                            sky_inv(c, rsqrt_rn(fdot(c.dx, c.dy, c.dz, c.dx, c.dy, c.dz)), 1.0f, 1.0f, 1.0f, Lr, Lg, Lb);
+                        else
+                            sky(c, 1.0f, 1.0f, 1.0f, Lr, Lg, Lb);
+                        store_radiance(P.scratch, it, Lr, Lg, Lb);
+                        if constexpr (CHAIN) {
+                            if (__lane_id() == 0) atomicAdd(&ww->segs, 64u);
+                        } else {
+                            ++segs;
+                            ++samples;
+                        }
+                        skyHeld = true;
+                        poolNext = 64;  // (the old pool is used up)
+                    } else {
+                        if (it != kNone) {
+                            if (CHAIN || HIPPT_LATE_CAM)
+                                camera_ray(late_field(cam), cs, ct, c, crng);
+                            else
+                                camera_ray(P.cam, cs, ct, c, crng);
+                        }
+                        const unsigned k = __lane_id();
+                        pool[k] = __uint_as_float(it);
+                        pool[64 + k] = __uint_as_float(crng);
+                        pool[128 + k] = c.dx;
+                        pool[192 + k] = c.dy;
+                        pool[256 + k] = c.dz;
+                        if (P.poolWords == kPoolWordsFull) {
+                            pool[320 + k] = c.ox;
+                            pool[384 + k] = c.oy;
+                            pool[448 + k] = c.oz;
+                        }
+                        poolNext = n - avail;
+                        if (need) {
+                            need = false;
+                            pool_take<POOL>(P, pool, rank - avail, item, r, rng);
+                        }
                     }
                 } else {
                     poolNext += n;
@@ -615,7 +667,8 @@ __global__ __launch_bounds__(kMeshBlock, (FULL || WIDE) ? HIPPT_WIDE_WAVES_PER_E
                     depth = 0;
                     fresh = true;
                 }
-                if (FINISH && __ballot(took && item == kNone)) waveThr = 0u;
+                // (a lane a held trip left without an item still has `need`: not a drained fetch)
+                if (FINISH && __ballot(took && !need && item == kNone)) waveThr = 0u;
             }
         } else if (__ballot(need)) {
             const unsigned it = HIPPT_LATE_CAM ? order_item_late(queue_fetch(need, Q, P.queue, P.totalItems, P.chunk))
@@ -646,6 +699,14 @@ __global__ __launch_bounds__(kMeshBlock, (FULL || WIDE) ? HIPPT_WIDE_WAVES_PER_E
             prepare(r);
             begin(T);
         }
+        // a sky run was finished and lanes still need an item: the wave fetches its next 64 first, up
+        // to kSkyRunsPerTrip runs while lanes with paths wait (a wave with three idle lanes must not eat
+        // a whole claim meanwhile) and for as long as no lane has one (the queues are not drained: the
+        // wave must not leave).  (At the shipped bound of 1 the counter folds away; written without it,
+        // `skyHeld && !__any(...)`, the chained Lambertian LDS kernel with the spilling stack gains 8
+        // bytes of scratch, profiles/sky_rect/regs.txt.)
+        if (SKY && skyHeld && (++skyRuns < kSkyRunsPerTrip || !__any(busy(T) || pend != 0u))) continue;
+        skyRuns = 0;
         if (!__any(busy(T) || pend != 0u)) break;
 
         // ---- traversal: while-while over the BVH; leave once few lanes remain -------------
@@ -919,6 +980,8 @@ hipError_t launch_mesh(const MeshParams &p, int blocks, bool countTraversal, hip
     if (lds && p.wide == kWideFloat && (p.refBits < 8 || p.refBits > 20)) return hipErrorInvalidValue;
     const bool pool = p.poolWords != 0;
     if (pool && ((p.wide != kWideFloat && p.wide != kWideHalf) || (p.poolWords != kPoolWordsPinhole && p.poolWords != kPoolWordsFull)))
+        return hipErrorInvalidValue;
+    if (p.skyRect.x0 < 0 || p.skyRect.y0 < 0 || p.skyRect.x1 < p.skyRect.x0 || p.skyRect.y1 < p.skyRect.y0)
         return hipErrorInvalidValue;
     const bool chain = p.chainCtl != nullptr;
     if (chain && (!p.chainBox || p.chainSlots < 2 || p.chainSlots > kChainSlotsMax || (p.chainSlots & (p.chainSlots - 1)) ||

@@ -668,15 +668,20 @@ __device__ __forceinline__ void audit_combine(unsigned *audit, int c0, int c1, u
 }
 
 // PP: MeshParams or CamArgs.  frameAdd: a chained batch's frame offset from the launch's own frames.
+// In two steps: camera_pixel (the item's image pixel x, y, the sample's RNG state and its image-plane
+// point s, t) and camera_ray (the lens draw, origin and direction).
 template <typename PP>
-__device__ __forceinline__ void camera_sample(const PP &P, unsigned it, Ray &r, uint32_t &rng, unsigned frameAdd = 0u) {
-    unsigned fl, p, yb, x;
+__device__ __forceinline__ void camera_pixel(const PP &P, unsigned it, uint32_t &rng, unsigned frameAdd, unsigned &x,
+                                             unsigned &y, float &s, float &t) {
+    unsigned fl, p, yb;
     divmod(it, P.bandPixels, P.rcpBandPixels, fl, p);
     divmod(p, unsigned(P.width), P.rcpWidth, yb, x);
-    const unsigned y = unsigned(P.y0) + yb * unsigned(P.rowStride);
+    y = unsigned(P.y0) + yb * unsigned(P.rowStride);
     rng = pixel_seed(x, y, unsigned(P.width), unsigned(P.firstFrame) + fl + frameAdd);
-    const float s = (float(x) + rand01(rng)) * P.invW;
-    const float t = (float(y) + rand01(rng)) * P.invH;
+    s = (float(x) + rand01(rng)) * P.invW;
+    t = (float(y) + rand01(rng)) * P.invH;
+}
+__device__ __forceinline__ void camera_ray(const CameraF &C, float s, float t, Ray &r, uint32_t &rng) {
     float qx, qy;
     for (unsigned tries = 1;; ++tries) {  // random_in_unit_disk, RayTracer.h:163-169
         qx = rand_pm1(rng);
@@ -684,7 +689,6 @@ __device__ __forceinline__ void camera_sample(const PP &P, unsigned it, Ray &r, 
         if (fmaf(qx, qx, qy * qy) < 1.0f) break;
         escape_cycle(rng, tries);
     }
-    const CameraF &C = P.cam;
     const float rx = C.lens_radius * qx, ry = C.lens_radius * qy;
     const float fx = fmaf(C.v[0], ry, C.u[0] * rx);
     const float fy = fmaf(C.v[1], ry, C.u[1] * rx);
@@ -695,6 +699,28 @@ __device__ __forceinline__ void camera_sample(const PP &P, unsigned it, Ray &r, 
     r.dx = (fmaf(t, C.vertical[0], fmaf(s, C.horizontal[0], C.llc[0])) - C.origin[0]) - fx;
     r.dy = (fmaf(t, C.vertical[1], fmaf(s, C.horizontal[1], C.llc[1])) - C.origin[1]) - fy;
     r.dz = (fmaf(t, C.vertical[2], fmaf(s, C.horizontal[2], C.llc[2])) - C.origin[2]) - fz;
+}
+// camera_ray's direction for a pinhole (lens_radius == 0, u and v finite) without the lens draw: the
+// lens offset is then +-0 whatever the draw gives, and x - (+-0) = x (a zero may differ in sign).  For
+// a sample that ends on this ray: the RNG state is not advanced.
+__device__ __forceinline__ void camera_dir_pinhole(const CameraF &C, float s, float t, Ray &r) {
+    r.dx = fmaf(t, C.vertical[0], fmaf(s, C.horizontal[0], C.llc[0])) - C.origin[0];
+    r.dy = fmaf(t, C.vertical[1], fmaf(s, C.horizontal[1], C.llc[1])) - C.origin[1];
+    r.dz = fmaf(t, C.vertical[2], fmaf(s, C.horizontal[2], C.llc[2])) - C.origin[2];
+}
+template <typename PP>
+__device__ __forceinline__ void camera_sample(const PP &P, unsigned it, Ray &r, uint32_t &rng, unsigned frameAdd = 0u) {
+    unsigned x, y;
+    float s, t;
+    camera_pixel(P, it, rng, frameAdd, x, y, s, t);
+    camera_ray(P.cam, s, t, r, rng);
+}
+
+// HIPPT_OPT_SKY_RECT (hippt_sky_rect.h): pixel (x, y) lies outside the launch's sky
+// rectangle (MeshParams::skyRect, loaded where it is used), so its camera rays cannot reach the scene.
+__device__ __forceinline__ bool sky_certain(unsigned x, unsigned y) {
+    const SkyRect R = late_field(skyRect);
+    return x - unsigned(R.x0) >= unsigned(R.x1 - R.x0) || y - unsigned(R.y0) >= unsigned(R.y1 - R.y0);
 }
 
 // A finished sample's radiance: one 12-byte store (one vector-memory instruction; three planes

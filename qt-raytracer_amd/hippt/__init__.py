@@ -58,6 +58,7 @@ OPT_CHAIN_AUDIT = 31
 OPT_PIXEL_TILE = 32
 OPT_QUERY_SLICE = 33
 OPT_RENDER_PAD = 34
+OPT_SKY_RECT = 35
 OPT_PIXEL_FORMAT = 25
 PIXEL_ARGB = 0
 PIXEL_RGBA8 = 1
@@ -67,6 +68,7 @@ INFO_CHUNK = 102
 INFO_CHAIN_CAP = 103
 INFO_UPDATE_DROPPED = 104
 INFO_RENDER_PAD = 105
+INFO_SKY_RECT_PIXELS = 106
 RAYS_DEVICE = 1
 HIT_SPHERE = 1 << 30
 HIT_BACKFACE = -(1 << 31)  # the int's sign bit
