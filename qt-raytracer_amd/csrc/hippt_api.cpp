@@ -8,6 +8,9 @@
 //     thread and the QSG render thread without a lock, RayTracerFboItem.cpp:261,521,529);
 //   * triangle-mesh scenes with a host-built SAH BVH in addition to the reference's
 //     built-in 4-sphere scene.
+// What a render batch or a ray query launches with (tree width, LDS residency, stack, node format,
+// camera pool, top of the tree, loop exits, claim size) is decided in hippt_plan.h, a pure header;
+// this file gathers its inputs, allocates what the plan needs and enqueues the launches.
 #include "../../include/hippt.h"
 #include "item_order.h"
 
@@ -32,6 +35,7 @@
 #include "bvh_builder.h"
 #include "mesh_io.h"
 #include "hippt_device.h"
+#include "hippt_plan.h"
 #include "hippt_query.h"
 #include "hippt_refit.h"
 #include "hippt_sky_rect.h"
@@ -47,22 +51,12 @@ struct hipptBvh {
 namespace {
 
 using hippt::CameraF;
+namespace plan = hippt::plan;
 
 using hippt::kStatSlots;
 using hippt::kStatWords;
 constexpr size_t kStatBytes = size_t(kStatSlots) * kStatWords * sizeof(unsigned long long);
 
-
-// 4-wide traversal: LDS stack content capacity for scenes outside LDS (19 + 3 spare entries =
-// 22 KB per 256-lane block: 7 blocks per CU in 160 KB).
-constexpr int kWideStackCap = 19;
-// a tree that spills anyway keeps 10 entries and gives the rest to the top of the tree (r3al,
-// alternating on leaf-2 trees: blob70k 1080p +0.5%, 4K +0.6% over 13; r3q before: +0.6%)
-constexpr int kSpillStackCap = 10;
-// 4-wide trees are numbered breadth-first for their first kTopOrderNodes nodes, so that a prefix
-// of the node array is the top of the tree; trees read from global memory keep such a prefix in
-// LDS (HIPPT_OPT_LDS_TOP_NODES)
-constexpr int kTopOrderNodes = 1365;  // 6 complete levels
 // hippt_trace.h kQueues x kQueueStride work counters, then (its own line) the fused combine's
 // chunk counter (MeshParams::combCtr)
 constexpr size_t kCombCtrWord = 8 * 32;
@@ -95,6 +89,22 @@ bool same_key(const OrderKey &a, const OrderKey &b) {
             a.cam.u[k] != b.cam.u[k] || a.cam.v[k] != b.cam.v[k])
             return false;
     return true;
+}
+
+// The key of a context's cached occupancy queries (resident blocks per CU of the megakernel, the
+// wavefront extend kernel or the query kernel): the scene and what selects the kernel variant and
+// sizes its LDS.
+struct OccKey {
+    int version = -1, stackDepth = 0, fmt = 0, poolWords = 0;
+    unsigned topBytes = 0;
+    bool ldsScene = false, full = false, spills = false;
+    int variant = 0;  // queries: any | camera << 1 | records << 2
+};
+
+bool same_key(const OccKey &a, const OccKey &b) {
+    return a.version == b.version && a.stackDepth == b.stackDepth && a.fmt == b.fmt && a.poolWords == b.poolWords &&
+           a.topBytes == b.topBytes && a.ldsScene == b.ldsScene && a.full == b.full && a.spills == b.spills &&
+           a.variant == b.variant;
 }
 
 // Run costs computed on a detached host thread (HIPPT_OPT_ITEM_ORDER automatic).  The thread owns a
@@ -182,10 +192,10 @@ struct Ctx {
     unsigned *wfCtr = nullptr;
     unsigned *wfHost = nullptr;  // pinned: two snapshots of the ray-queue shard counters
     hipEvent_t wfPoll[2] = {nullptr, nullptr};
-    long long wfOccKey = -1;  // occupancy cached per (scene version, depth, lds, full)
+    OccKey wfOccKey;  // of wfBlocksPerCu
     int wfBlocksPerCu[2] = {0, 0};
     int cus = 0;
-    long long occKey = -1;  // occupancy cached per (scene version, depth, lds, full)
+    OccKey occKey;  // of meshBlocksPerCu, meshBlocksPerCuChain
     int meshBlocksPerCu[2] = {0, 0};
     int meshBlocksPerCuChain = 0;  // the chained-batch kernel's
     // Chained batches (HIPPT_OPT_CHAIN; MeshParams::chain*, hippt_trace.h): the open run.  Its launches
@@ -245,7 +255,7 @@ struct Ctx {
     void *qStage = nullptr;
     size_t qStageBytes = 0;
     hipEvent_t qDone = nullptr;
-    long long qOccKey = -1;  // occupancy cached per (scene version, layout, kernel variant)
+    OccKey qOccKey;  // of qBlocksPerCu
     int qBlocksPerCu = 0;
 };
 
@@ -303,28 +313,19 @@ struct State {
     int latest = -1;                     // newest completed buffer
     SceneHost scene;
     char error[256] = {0};
-    // options
-    bool countTraversal = false;
-    int waveThreshold = -1;  // -1: automatic (24 for LDS scenes and the general kernel, 40 for Lambertian scenes over trees in global memory)
+    // options: those the traversal plan reads (hippt_plan.h), then the others
+    plan::Knobs knobs = [] {
+        plan::Knobs k;
+        k.renderPad = hippt::slab::kRenderPadDefault;
+        return k;
+    }();
     // one batch (and one end-of-batch tail) per call up to 4K/256 spp: 2.12G samples x 12 B
     long long scratchMB = 32768;
-    unsigned chunk = 0;  // work items per claim (0: automatic, see enqueue_locked)
-    int leafExit = -1;  // -1: automatic from the tree depth and LDS residency
-    int nodeExit = -1;  // -1: automatic
-    int bvhWidth = 0;   // megakernel traversal over the 2- or 4-wide BVH; 0: 4-wide if it fits in LDS
-    int stackCap = 0;   // 4-wide LDS stack entries (0: automatic)
-    int bvhQuant = -1;  // 4-wide global-memory traversal over 8-bit child boxes (-1: automatic)
-    int ldsTopNodes = -1;  // top-of-tree nodes copied into LDS for global-memory trees (-1: automatic)
     bool rngTable = false;  // memoized random_in_unit_sphere (HIPPT_OPT_RNG_TABLE)
     int pixelFormat = HIPPT_PIXEL_ARGB;  // output frame words (HIPPT_OPT_PIXEL_FORMAT)
-    int cameraPool = -1;  // megakernel camera-ray pool (HIPPT_OPT_CAMERA_POOL; -1: automatic)
-    int fuseCombine = -1;  // combine inside the next megakernel launch (HIPPT_OPT_FUSE_COMBINE)
     int itemOrder = -1;    // scene-hitting pixel runs first (HIPPT_OPT_ITEM_ORDER; -1: automatic)
     int pixelTile = -1;    // the item order's runs: tile columns (HIPPT_OPT_PIXEL_TILE; 0 rows, -1 automatic)
-    int chainBatches = -1; // batches a chained launch may trace (HIPPT_OPT_CHAIN; 0 off, -1 automatic)
     bool chainAudit = false;            // HIPPT_OPT_CHAIN_AUDIT
-    int renderPad = hippt::slab::kRenderPadDefault;  // HIPPT_OPT_RENDER_PAD (0: the builder's pad)
-    bool skyRect = true;                // HIPPT_OPT_SKY_RECT
     long long querySlice = 0;           // rays per staged slice of a host-memory query (HIPPT_OPT_QUERY_SLICE; 0 automatic)
     std::vector<unsigned> auditWords;   // closed runs' audit words not yet read (hipptChainAudit)
     std::vector<std::pair<int, uint32_t *>> rngTables;  // per device, built on first use
@@ -360,8 +361,6 @@ struct State {
     int activeRenderPad = 0; // its LDS scene copy's pad exponent (HIPPT_OPT_RENDER_PAD as applied; 0: no trim)
     int activeWidth = 0;  // BVH width of the last mesh render (hipptActiveBvhWidth)
     int blocksPerCu = 0;
-    bool ldsScene = true;
-    int pathMode = 0;             // 0 megakernel, 1 wavefront
     // wavefront path-state slots per device: 2^27 holds a whole 1080p/64-spp step in flight (one
     // generation, no regenerate rounds; 8.6 GB of 64-byte records): blob70k 6.8 -> 7.4+ G vs 2^24
     unsigned wfSlots = 1u << 27;
@@ -886,20 +885,6 @@ hippt::skyrect::Rect sky_rect_of(const SceneHost &sc, const CameraF &cam, int wi
     return hippt::skyrect::sky_rect(cam, width, height, lo, hi, sc.pad, sc.numTris);
 }
 
-// Low bits of a packed child key (trace::child_key_p) that give an LDS-resident 4-wide tree's child
-// codes back when sign-extended: interior codes are node byte offsets < numNodes*128, leaf codes
-// ~(first<<4 | count) with first + count <= numPrims; one more bit for the sign.  At most 16 for a
-// scene that fits the LDS copy (24 KB: < 192 nodes, < 384 primitives), which leaves the entry
-// distance 7 or more mantissa bits (Cornell-34: 12 bits, 11 mantissa bits) to order children by.
-unsigned packed_ref_bits(int numNodes, int numPrims) {
-    const unsigned long long maxMag =
-        std::max<unsigned long long>((unsigned long long)std::max(numNodes, 1) * 128ull,
-                                     ((unsigned long long)numPrims << 4) + 16ull);
-    unsigned bits = 1;
-    while ((1ull << (bits - 1)) < maxMag) ++bits;  // magnitude < 2^(bits-1)
-    return std::max(bits, 8u);
-}
-
 // The queues' item table of a context's rows (item_order.h) for a batch of `frames` frames: run cost
 // estimates per key (scene, camera, image, rows, depth), tables per batch size (kOrderTables of
 // them, so a call's full batches and its remainder batch both stay cached).  With `forced`
@@ -1140,12 +1125,6 @@ bool init_locked(int width, int height, const char **err) {
     return false;
 }
 
-long long occupancy_key(int version, int stackDepth, bool lds, bool full, bool wide = false, bool quant = false,
-                        bool spills = true) {
-    return ((long long)version << 11) | ((long long)stackDepth << 5) | (spills ? 16 : 0) | (quant ? 8 : 0) |
-           (wide ? 4 : 0) | (lds ? 2 : 0) | (full ? 1 : 0);
-}
-
 // 4-wide traversal of a tree whose stack bound exceeds the LDS capacity: a per-lane spill
 // area of spillCap entries for every lane of a `blocks`-block persistent grid.
 bool ensure_spill(Ctx &c, hippt::MeshParams &p, long long blocks, bool spills, int spillCap, const char **err) {
@@ -1261,9 +1240,10 @@ bool run_wavefront(Ctx &c, hippt::MeshParams p, bool cnt, bool spills, int spill
         }
     }
     const bool wide = p.wide != 0, quant = p.wide == 2;
-    const long long occKey = occupancy_key(s.scene.version, p.stackDepth, p.ldsScene != 0, p.full != 0, wide, quant) ^
-                             ((long long)p.topBytes << 40) ^ ((long long)(p.wide == hippt::kWideHalf) << 34);
-    if (c.wfOccKey != occKey) {
+    OccKey occKey;
+    occKey.version = s.scene.version, occKey.stackDepth = p.stackDepth, occKey.fmt = p.wide, occKey.topBytes = p.topBytes;
+    occKey.ldsScene = p.ldsScene != 0, occKey.full = p.full != 0;
+    if (!same_key(c.wfOccKey, occKey)) {
         const int ln = p.ldsScene ? p.numNodes : 0, lt = p.ldsScene ? p.numTris : 0;
         c.wfBlocksPerCu[0] =
             hippt::wf_extend_blocks_per_cu(false, p.full != 0, wide, quant, p.stackDepth, ln, lt, p.topBytes);
@@ -1328,7 +1308,6 @@ CameraF current_camera() {
     return cam;
 }
 
-// Enqueues `count` frames on every context (no host wait).
 // Copies a context's compact rows (c.rows rows of W pixels of `bytes` each) to their image rows
 // c.y0, c.y0 + c.stride, ... of a full-frame host buffer, on the context's stream.
 bool copy_rows_async(Ctx &c, void *dstFrame, const void *src, size_t bytes, const char **err) {
@@ -1443,7 +1422,7 @@ constexpr bool kChainHoldRunning = HIPPT_CHAIN_HOLD_RUNNING != 0;
 // lower or equal); the ring (16 slots) stays within the scratch budget (ring_plan) or the cap shrinks.
 unsigned chain_cap(long long option, unsigned total, bool ldsScene) {
     if (option > 0) return unsigned(std::min<long long>(option, 16));
-    const double c = total > (1u << 26) ? 8.0 : std::round(4e8 / double(std::max(1u, total)));
+    const double c = total > plan::kWholeImageItems ? 8.0 : std::round(4e8 / double(std::max(1u, total)));
     return unsigned(std::clamp(c, 2.0, ldsScene ? 8.0 : 16.0));
 }
 
@@ -1722,6 +1701,288 @@ uint32_t *host_frame_on_device(unsigned *frame) {
     return static_cast<uint32_t *>(d);
 }
 
+// The planner's inputs (hippt_plan.h): the LDS limits of the kernels as built, and the uploaded scene's
+// facts (halfTree: render_layout, which builds that tree on use).
+plan::Limits lds_limits() { return plan::Limits{hippt::mesh_lds_scene_limit(), hippt::mesh_lds_block_budget()}; }
+
+plan::Facts scene_facts(const SceneHost &sc) {
+    plan::Facts f;
+    f.numNodes = sc.numNodes;
+    f.numNodes4 = sc.numNodes4;
+    f.numTris = sc.numTris;
+    f.numMats = int(sc.mats.size() / 2);
+    f.levels = sc.levels;
+    f.stackBound4 = sc.stackBound4;
+    f.full = sc.full;
+    f.quantTree = !sc.nodes4q.empty();
+    return f;
+}
+
+// A render's layout plan under the options as set.  The half-precision tree is built here, the first
+// time a plan reads it (and never for a plan that does not).
+plan::Layout render_layout(plan::Facts &f, const CameraF &cam) {
+    State &s = S();
+    const plan::Limits lim = lds_limits();
+    f.halfTree = plan::wants_half(f, s.knobs, lim) && half_tree_ok(s.scene);
+    const bool pinhole = cam.lens_radius == 0.0f && cam.origin[0] != 0.0f && cam.origin[1] != 0.0f &&
+                         cam.origin[2] != 0.0f;
+    return plan::layout(f, s.knobs, lim, pinhole);
+}
+
+// The legacy 4-sphere scene's frames on context c: one launch.  *copied: the kernel wrote the frame's
+// rows into the pinned host frame `dst` itself (legacy zero copy).
+bool enqueue_sphere4(Ctx &c, int firstFrame, int count, int maxDepth, bool copy, unsigned *dst, bool *copied,
+                     const char **err) {
+    State &s = S();
+    // the legacy kernel writes accum/out itself: a mesh batch's pending combine goes first
+    if (!flush_deferred(c, err)) return false;
+    hippt::Sphere4Params p{c.accum, c.out, c.stats, s.width, s.height, c.y0, c.rows, c.stride, firstFrame, count,
+                           maxDepth, s.pixelFormat, nullptr};
+    // A blocking frame (the app's cudaPathTracerRender): the kernel writes the words into
+    // the pinned host frame itself, overlapping the PCIe transfer with the trace, instead
+    // of a D2H copy after it (1080p: 0.17 ms of copy behind 0.13 ms of kernel)
+    if (copy && kLegacyZeroCopy) {
+        p.hostOut = host_frame_on_device(dst);
+        *copied = p.hostOut != nullptr;  // else the copy after the kernel
+    }
+    EventPair ev;
+    if (!next_events(c, ev, err)) return false;
+    HIP_TRY(hipEventRecord(ev.a, c.stream));
+    HIP_TRY(hippt::launch_sphere4(p, c.stream));
+    HIP_TRY(hipEventRecord(ev.b, c.stream));
+    c.pending.push_back({0, ev});
+    return true;
+}
+
+// A mesh call's batches on a context: as many frames per batch as the sample scratch budget
+// (HIPPT_OPT_SCRATCH_MB) and the 2^31 work items of a launch hold.
+struct BatchSize {
+    int frames;
+    size_t need;    // scratch bytes of a full batch
+    size_t budget;  // the scratch budget (also the chain ring's, ring_plan)
+};
+BatchSize frames_per_batch(unsigned bandPixels, int count) {
+    const size_t perFrame = size_t(bandPixels) * 3 * sizeof(float);
+    const size_t cap = size_t(std::max<long long>(1, S().scratchMB)) << 20;
+    int fpb = int(std::max<size_t>(1, cap / perFrame));
+    fpb = std::min(fpb, count);
+    fpb = int(std::min<long long>(fpb, (1LL << 31) / std::max<unsigned>(1, bandPixels)));
+    fpb = std::max(fpb, 1);
+    return BatchSize{fpb, perFrame * size_t(fpb), cap};
+}
+
+// Resident blocks per CU of the plan's megakernel variants on context c (cached per OccKey).
+void mesh_occupancy(Ctx &c, const plan::Facts &f, const plan::Layout &L) {
+    State &s = S();
+    OccKey key;
+    key.version = s.scene.version, key.stackDepth = L.stackDepth, key.fmt = L.fmt, key.poolWords = L.poolWords;
+    key.topBytes = L.topBytes, key.ldsScene = L.ldsScene, key.full = f.full, key.spills = L.spills;
+    if (same_key(c.occKey, key)) return;
+    const int ln = L.ldsScene ? L.numNodes : 0, lt = L.ldsScene ? f.numTris : 0, lm = L.ldsScene ? f.numMats : 0;
+    c.meshBlocksPerCu[0] =
+        hippt::mesh_blocks_per_cu(false, f.full, L.fmt, L.stackDepth, ln, lt, L.spills, L.topBytes, lm, L.poolWords);
+    c.meshBlocksPerCu[1] =
+        hippt::mesh_blocks_per_cu(true, f.full, L.fmt, L.stackDepth, ln, lt, L.spills, L.topBytes, lm, L.poolWords);
+    c.meshBlocksPerCuChain = L.poolWords && L.fmt == hippt::kWideFloat
+                                 ? hippt::mesh_blocks_per_cu(false, f.full, L.fmt, L.stackDepth, ln, lt, L.spills,
+                                                             L.topBytes, lm, L.poolWords, true)
+                                 : 0;
+    c.occKey = key;
+}
+
+// One batch's launch parameters from (context, plan, batch): frames [firstFrame, firstFrame + frames)
+// of the context's rows.  The chain fields, the spill area and the combine are the launch's (chain_batch,
+// ensure_spill, enqueue_mesh).
+bool fill_mesh_params(Ctx &c, const plan::Facts &f, const plan::Layout &L, const plan::Batch &B, bool chained,
+                      const CameraF &cam, int firstFrame, int frames, int maxDepth, float *scratch, hippt::MeshParams &p,
+                      const char **err) {
+    State &s = S();
+    const unsigned bandPixels = unsigned(c.rows) * unsigned(s.width);
+    switch (L.fmt) {
+    case hippt::kWideHybrid: p.nodes = c.nodes4h; break;
+    case hippt::kWideQuant: p.nodes = c.nodes4q; break;
+    case hippt::kWideHalf: p.nodes = c.nodes4f; break;
+    case hippt::kWideFloat: p.nodes = c.nodes4; break;
+    default: p.nodes = c.nodes; break;
+    }
+    p.tris = c.tris;
+    p.shade = c.shade;
+    p.mats = c.mats;
+    p.scratch = scratch;
+    p.queue = c.queue;
+    p.stats = c.stats;
+    p.cam = cam;
+    p.invW = 1.0f / float(std::max(1, s.width - 1));
+    p.invH = 1.0f / float(std::max(1, s.height - 1));
+    p.width = s.width;
+    p.height = s.height;
+    p.y0 = c.y0;
+    p.bandRows = c.rows;
+    p.rowStride = c.stride;
+    p.firstFrame = firstFrame;
+    p.frames = frames;
+    p.maxDepth = maxDepth;
+    p.bandPixels = bandPixels;
+    p.totalItems = bandPixels * unsigned(frames);
+    p.rcpBandPixels = 1.0f / float(bandPixels);
+    p.rcpWidth = 1.0f / float(s.width);
+    p.stackDepth = L.stackDepth;
+    p.numNodes = L.numNodes;
+    p.numTris = f.numTris;
+    p.numMats = f.numMats;
+    p.ldsScene = L.ldsScene ? 1 : 0;
+    p.full = f.full ? 1 : 0;
+    p.waveThreshold = L.waveThreshold;
+    p.chunk = B.chunk[chained ? 1 : 0];
+    p.leafExit = L.leafExit;
+    p.nodeExit = L.nodeExit;
+    p.wide = L.fmt;
+    p.stackCap = L.stackCap;
+    p.topBytes = L.topBytes;
+    p.refBits = L.refBits;
+    // The sky rectangle (below) needs the host copy's root box.  A host-memory vertex
+    // update's vertices are on the host already: for a scene that fits the LDS copy the
+    // host copy takes them here, a refit of a few hundred primitives, before anything of
+    // this batch looks at it; a larger scene's waits for whatever next needs the host
+    // copy (blob70k's host refit takes 10 ms).
+    const bool skyWanted = B.skyWanted[chained ? 1 : 0];
+    if (skyWanted && L.ldsScene && s.upd.hostStale && !s.upd.staleEv) settle_scene();
+    const bool trims = B.trimWanted && render_pad_holds(s.scene, s.upd.hostStale, cam);
+    p.padWord = c.padDev;
+    p.trimScale = trims ? hippt::slab::trim_scale(s.knobs.renderPad) : 0.0f;
+    s.activeRenderPad = trims ? s.knobs.renderPad : 0;
+    // the sky rectangle (HIPPT_OPT_SKY_RECT): not while a device-memory vertex update is ahead of the
+    // host copy (the scene may have grown past the host's root box)
+    const bool skyOn = skyWanted && !s.upd.hostStale;
+    const hippt::skyrect::Rect sr = skyOn ? sky_rect_of(s.scene, cam, s.width, s.height)
+                                          : hippt::skyrect::whole(s.width, s.height);
+    p.skyRect = hippt::SkyRect{sr.x0, sr.y0, sr.x1, sr.y1};
+    s.activeSkyPixels = hippt::skyrect::pixels_outside(sr, s.width, s.height);
+    p.rngTable = nullptr;
+    p.poolWords = L.poolWords;
+    // Pixel runs by estimated sample length, longest first, per XCD queue
+    // (megakernel; item_order.h): Cornell +2.4%, cornell_mixed +3%, blob70k
+    // +0.8% at full size; the slowest 1/8 Cornell share -2% (r5w)
+    if (s.knobs.pathMode == 0 && s.itemOrder != 0) {
+        const unsigned *table = nullptr;
+        // the runs' shape: HIPPT_OPT_PIXEL_TILE columns.  Automatic: 8x8 tiles for
+        // a band of consecutive rows (blob70k 1080p +0.45%, Cornell +0.6%, two
+        // alternating passes, r6d), row runs for an interleaved share (the tile's
+        // rows are `stride` image rows apart: the 1/8 shares neutral to -0.9%, r6f)
+        const int tile = s.pixelTile >= 0 ? s.pixelTile : c.stride == 1 ? 8 : 0;
+        const unsigned tileShift = tile == 8 ? 3u : tile == 16 ? 4u : tile == 32 ? 5u : 6u;
+        if (!ensure_order(c, cam, frames, maxDepth, s.itemOrder == 1, tileShift, &table, err)) return false;
+        if (table) {
+            p.runOrder = table;
+            p.runCount = unsigned(c.runCosts.size());
+            p.runTileShift = c.orderKey.tileShift;
+        }
+    }
+    p.poolOffset = L.poolOffset;
+    if (s.rngTable && !rng_table(c, &p.rngTable, err)) return false;
+    return true;
+}
+
+// A mesh scene's frames on context c, in batches: each a megakernel launch (on its own, or a batch of
+// the context's chained run), or the wavefront's launches; its combine deferred into the next batch's
+// launch, or flushed.
+bool enqueue_mesh(Ctx &c, const CameraF &cam, int firstFrame, int count, int maxDepth, bool copy, const char **err) {
+    State &s = S();
+    if (!ensure_scene(c, err)) return false;
+    const unsigned bandPixels = unsigned(c.rows) * unsigned(s.width);
+    const BatchSize size = frames_per_batch(bandPixels, count);
+    const bool cnt = s.knobs.countTraversal;
+    plan::Facts facts = scene_facts(s.scene);
+    const plan::Layout L = render_layout(facts, cam);
+    s.activeWidth = L.wide ? 4 : 2;
+    if (L.fmt == hippt::kWideHybrid && !ensure_hybrid(c, int(L.topBytes / 128), err)) return false;
+    if (L.fmt == hippt::kWideHalf && !ensure_half(c, err)) return false;
+    mesh_occupancy(c, facts, L);
+    s.activeTopBytes = L.topBytes;
+    s.activeBlocksPerCu = c.meshBlocksPerCu[cnt ? 1 : 0];
+    const int bpc = s.blocksPerCu > 0 ? s.blocksPerCu : c.meshBlocksPerCu[cnt ? 1 : 0];
+    for (int b = 0; b < count; b += size.frames) {
+        const int nf = std::min(size.frames, count - b);
+        const unsigned total = bandPixels * unsigned(nf);
+        const plan::Batch B = plan::batch(facts, s.knobs, L, copy, maxDepth, total);
+        const bool fuse = B.fuse;
+        bool chained = B.mayChain && c.meshBlocksPerCuChain > 0;
+        RingPlan ring;
+        if (chained) {
+            ring = ring_plan(total, s.knobs.chainBatches, L.ldsScene, size.budget);
+            bool ok = ring.bytes != 0;
+            if (ok && !ensure_ring(c, ring, &ok, err)) return false;
+            chained = ok;
+        }
+        if ((!fuse || !chained) && !flush_chain(c, err)) return false;
+        if (!fuse && !flush_deferred(c, err)) return false;
+        float *scratch = nullptr;
+        if (!chained && !batch_scratch(c, size.need, &scratch, err)) return false;
+        if (maxDepth <= 0) {
+            // ray_color with depth <= 0 returns black without tracing (RayTracer.h:582-583)
+            HIP_TRY(hipMemsetAsync(scratch, 0, size_t(total) * 3 * sizeof(float), c.stream));
+        } else {
+            hippt::MeshParams p{};
+            if (!fill_mesh_params(c, facts, L, B, chained, cam, firstFrame + b, nf, maxDepth, scratch, p, err)) return false;
+            if (s.knobs.pathMode == 1) {
+                if (!run_wavefront(c, p, cnt, L.spills, L.spillCap, err)) return false;
+            } else {
+                long long blocks = (long long)c.cus * (chained && s.blocksPerCu <= 0 ? c.meshBlocksPerCuChain : bpc);
+                blocks = std::min<long long>(blocks, (total + hippt::kMeshBlock - 1) / hippt::kMeshBlock);
+                blocks = std::max<long long>(blocks, 1);
+                if (!ensure_spill(c, p, blocks, L.spills, L.spillCap, err)) return false;
+                s.activeChunk = int(p.chunk);
+                s.activeChainCap = 0;
+                if (chained) {
+                    p.comb.format = s.pixelFormat;
+                    if (!chain_batch(c, p, blocks, ring, err)) return false;
+                    s.activeChainCap = int(c.chain.cap);
+                    continue;  // launched or taken by the run's last launch; its combine
+                               // belongs to the run (Ctx::chain)
+                } else {
+                    HIP_TRY(hipMemsetAsync(c.queue, 0, kQueueBytes, c.stream));
+                    if (c.hasDeferred) {
+                        p.comb = c.deferred;
+                        c.hasDeferred = false;
+                    }
+                    p.combCtr = c.queue + kCombCtrWord;
+                }
+                EventPair ev;
+                if (!next_events(c, ev, err)) return false;
+                HIP_TRY(hipEventRecord(ev.a, c.stream));
+                HIP_TRY(hippt::launch_mesh(p, int(blocks), cnt, c.stream));
+                HIP_TRY(hipEventRecord(ev.b, c.stream));
+                c.pending.push_back({0, ev});
+            }
+        }
+        if (chained && maxDepth > 0) continue;  // its combine belongs to the run (Ctx::chain)
+        c.deferred = hippt::CombineParams{c.accum, c.out, scratch, bandPixels, total, firstFrame + b, nf, s.pixelFormat};
+        c.hasDeferred = true;
+        if (!fuse && !flush_deferred(c, err)) return false;
+    }
+    return true;
+}
+
+// The end of a blocking call on context c: the frame's words into the pinned host frame `dst`, by the
+// deferred combine itself where the frame can be mapped, else by a copy after the flush.  copied: the
+// legacy kernel wrote them already.
+bool finish_blocking_frame(Ctx &c, unsigned *dst, bool copied, const char **err) {
+    State &s = S();
+    if (c.rows > 0 && c.hasDeferred && kLegacyZeroCopy) {
+        // a blocking mesh frame: its combine writes the words into the pinned host frame too
+        if (uint32_t *d = host_frame_on_device(dst)) {
+            c.deferredHost = hippt::HostFrame{d, s.width, c.y0, c.stride};
+            copied = true;
+        }
+    }
+    if (!flush_deferred(c, err)) return false;
+    if (c.rows > 0 && !copied) {
+        if (!copy_rows_async(c, dst, c.out, sizeof(uint32_t), err)) return false;
+    }
+    return true;
+}
+
+// Enqueues `count` frames on every context (no host wait).
 // copy: the frame's words end in the full-frame pinned host buffer `dst` (State::host when null),
 // written by the kernel that makes them (legacy kernel or combine) or copied after it.
 bool enqueue_locked(int firstFrame, int count, int maxDepth, bool copy, const char **err, unsigned *dst = nullptr) {
@@ -1733,358 +1994,13 @@ bool enqueue_locked(int firstFrame, int count, int maxDepth, bool copy, const ch
     const CameraF cam = mesh ? current_camera() : CameraF{};
     for (Ctx &c : s.ctxs) {
         HIP_TRY(hipSetDevice(c.device));
-        const int rows = c.rows;
-        const unsigned bandPixels = unsigned(rows) * unsigned(s.width);
-        bool copied = false;  // the kernel wrote the frame's rows into s.host (legacy zero copy)
-        if (rows > 0 && count > 0) {
-            if (!mesh) {
-                // the legacy kernel writes accum/out itself: a mesh batch's pending combine goes first
-                if (!flush_deferred(c, err)) return false;
-                hippt::Sphere4Params p{c.accum, c.out, c.stats, s.width, s.height, c.y0, rows, c.stride, firstFrame, count,
-                                       maxDepth, s.pixelFormat, nullptr};
-                // A blocking frame (the app's cudaPathTracerRender): the kernel writes the words into
-                // the pinned host frame itself, overlapping the PCIe transfer with the trace, instead
-                // of a D2H copy after it (1080p: 0.17 ms of copy behind 0.13 ms of kernel)
-                if (copy && kLegacyZeroCopy) {
-                    p.hostOut = host_frame_on_device(dst);
-                    copied = p.hostOut != nullptr;  // else the copy after the kernel
-                }
-                EventPair ev;
-                if (!next_events(c, ev, err)) return false;
-                HIP_TRY(hipEventRecord(ev.a, c.stream));
-                HIP_TRY(hippt::launch_sphere4(p, c.stream));
-                HIP_TRY(hipEventRecord(ev.b, c.stream));
-                c.pending.push_back({0, ev});
-            } else {
-                if (!ensure_scene(c, err)) return false;
-                const size_t perFrame = size_t(bandPixels) * 3 * sizeof(float);
-                const size_t cap = size_t(std::max<long long>(1, s.scratchMB)) << 20;
-                int fpb = int(std::max<size_t>(1, cap / perFrame));
-                fpb = std::min(fpb, count);
-                fpb = int(std::min<long long>(fpb, (1LL << 31) / std::max<unsigned>(1, bandPixels)));
-                fpb = std::max(fpb, 1);
-                const size_t need = perFrame * size_t(fpb);
-                const bool cnt = s.countTraversal;
-                // Traversal over the 4-wide tree (HIPPT_OPT_BVH_WIDTH), megakernel and wavefront.
-                // Automatic: 4-wide.  With near/far rows read by the ray's octant, 4-wide beats
-                // 2-wide on LDS scenes (Cornell 31.7 -> 35.3 G) and on global-memory trees (blob70k
-                // 14.2 -> 15.4 G: half the dependent node fetches, 18% fewer load instructions);
-                // random_scene (spheres, general kernel) 20.6 vs 20.5 G.
-                const bool wide = s.scene.numNodes4 > 0 && s.bvhWidth != 2;
-                s.activeWidth = wide ? 4 : 2;
-                const int numNodes = wide ? s.scene.numNodes4 : s.scene.numNodes, numTris = s.scene.numTris;
-                // small scenes live in LDS (scene bytes beyond the stack under the limit)
-                const int numMats = int(s.scene.mats.size() / 2);
-                const bool ldsScene = s.ldsScene && hippt::mesh_lds_bytes(0, numNodes, numTris, wide, 0, numMats) <=
-                                                        hippt::mesh_lds_scene_limit();
-                // LDS stack entries per lane: 2-wide = interior levels (+1 spare); 4-wide = the
-                // builder's exact bound up to kWideStackCap (+3 spare; deeper stacks spill their
-                // bottom half to global memory), so that 7 blocks of a big scene fit in LDS.  A
-                // traversal of a tree in global memory whose bound exceeds kWideStackCap (it
-                // spills anyway) keeps kSpillStackCap entries and gives the rest of its LDS to the
-                // top of the tree (blob70k, float nodes: cap 19 + 4 top nodes 17.8 G, cap 13 + 52
-                // top nodes 20.4 G; caps 9-15 within 1%, 7: -3%; r2w; cap 10 + 76 nodes +0.5%, r3al)
-                const bool topTree = wide && !ldsScene;
-                const int capLimit = s.stackCap > 0 ? s.stackCap
-                                     : ldsScene     ? 30
-                                     : topTree && s.scene.stackBound4 > kWideStackCap ? kSpillStackCap
-                                                                                       : kWideStackCap;
-                const int stackCap = wide ? std::max(1, std::min(s.scene.stackBound4, capLimit)) : 0;
-                const int stackDepth = wide ? stackCap + 2 : std::max(1, s.scene.levels);
-                const bool spills = wide && s.scene.stackBound4 > stackCap;
-                // 8-bit child boxes for trees read from global memory: 64-byte nodes, 4 vector loads
-                // instead of 7 where the texture addresser bounds the traversal (blob70k: TA busy
-                // 84%, 15.6 -> 17.7 G).  Automatic for the wavefront's Lambertian-triangle kernel
-                // only: the megakernel reads the top of the tree (62-70% of the visits) from LDS,
-                // where the float nodes need no decode (blob70k 19.0 G 8-bit, 20.4 G float, r2v).
-                // (scenes with boxes near +-FLT_MAX have no 8-bit tree: quantize_bvh4 failed)
-                // Hybrid (HIPPT_OPT_BVH_QUANT 2, megakernel): the top of the tree as float nodes in LDS
-                // (no decode where most visits are) and 8-bit nodes below it (4 loads instead of 7
-                // where the texture addresser binds); falls back to 8-bit nodes without a top.
-                bool hybrid = wide && !ldsScene && !s.scene.nodes4q.empty() && s.pathMode == 0 && s.bvhQuant == 2 &&
-                              s.ldsTopNodes != 0;
-                bool quant = wide && !ldsScene && !s.scene.nodes4q.empty() &&
-                             (s.bvhQuant == 1 || s.bvhQuant == 2 ||
-                              (s.bvhQuant == -1 && !s.scene.full && s.pathMode == 1));
-                // Half-precision planes (HIPPT_OPT_BVH_QUANT 3, megakernel and wavefront extend): the
-                // float nodes' size and codes, 4 reads per visit instead of 7
-                // half planes unless the scene's planes leave the half range (then float nodes)
-                const bool half = wide && !ldsScene && s.bvhQuant == 3 && half_tree_ok(s.scene);
-                // The top of a global-memory tree in LDS (megakernel and wavefront extend): the
-                // breadth-first prefix of the node array that the LDS budget of the resident blocks
-                // leaves beside the stack (automatic), or HIPPT_OPT_LDS_TOP_NODES nodes.  The
-                // wavefront keeps its 8-bit nodes (blob70k: 8.28 G 8-bit, 7.53 G float, r2za).
-                // Camera-ray pool (megakernel, 4-wide float nodes): on by default for LDS-resident
-                // scenes and for the Lambertian kernel over a tree in global memory (its pool's LDS
-                // comes out of the top of the tree).
-                // Pinhole cameras at a nonzero origin start every ray at cam.origin exactly
-                // (origin + 0*offset), so their pool entries carry no origin.
-                // (round 3, r6j: also for the Lambertian kernel over a tree in global memory,
-                // blob70k +1.8% though the pool's LDS comes out of the top; the general kernel
-                // there loses 10%, random_scene)
-                const bool pool = s.pathMode == 0 && wide && !quant &&
-                                  (s.cameraPool == 1 || (s.cameraPool == -1 && (ldsScene || !s.scene.full)));
-                if (hybrid) quant = false;  // (pool: off, as for 8-bit nodes)
-                const bool pinhole = cam.lens_radius == 0.0f && cam.origin[0] != 0.0f && cam.origin[1] != 0.0f &&
-                                     cam.origin[2] != 0.0f;
-                const int poolWords = pool ? (pinhole ? hippt::kPoolWordsPinhole : hippt::kPoolWordsFull) : 0;
-                unsigned topBytes = 0;
-                if (topTree && s.ldsTopNodes != 0) {
-                    const size_t nodeBytes = quant ? 64 : 128;  // hybrid: a float top
-                    size_t n = size_t(std::min(numNodes, kTopOrderNodes));
-                    if (s.ldsTopNodes > 0) {
-                        n = std::min(n, size_t(s.ldsTopNodes));
-                    } else {
-                        const size_t stackBytes = hippt::mesh_lds_bytes(stackDepth, 0, 0, true, 0, 0, poolWords);
-                        const size_t budget = hippt::mesh_lds_block_budget();
-                        n = std::min(n, budget > stackBytes ? (budget - stackBytes) / nodeBytes : 0);
-                    }
-                    topBytes = unsigned(n * nodeBytes);
-                }
-                if (hybrid && topBytes == 0) {  // no LDS left for a top: plain 8-bit nodes
-                    hybrid = false;
-                    quant = true;
-                }
-                const int fmt = !wide    ? hippt::kWide2
-                                : hybrid ? hippt::kWideHybrid
-                                : quant  ? hippt::kWideQuant
-                                : half   ? hippt::kWideHalf
-                                         : hippt::kWideFloat;
-                if (hybrid && !ensure_hybrid(c, int(topBytes / 128), err)) return false;
-                if (half && !ensure_half(c, err)) return false;
-                const long long occKey =
-                    occupancy_key(s.scene.version, stackDepth, ldsScene, s.scene.full, wide, quant, spills) ^
-                    ((long long)topBytes << 40) ^ ((long long)poolWords << 36) ^ ((long long)hybrid << 35) ^
-                    ((long long)half << 34);
-                if (c.occKey != occKey) {
-                    const int ln = ldsScene ? numNodes : 0, lt = ldsScene ? numTris : 0, lm = ldsScene ? numMats : 0;
-                    c.meshBlocksPerCu[0] = hippt::mesh_blocks_per_cu(false, s.scene.full, fmt, stackDepth, ln, lt,
-                                                                     spills, topBytes, lm, poolWords);
-                    c.meshBlocksPerCu[1] = hippt::mesh_blocks_per_cu(true, s.scene.full, fmt, stackDepth, ln, lt,
-                                                                     spills, topBytes, lm, poolWords);
-                    c.meshBlocksPerCuChain = poolWords && fmt == hippt::kWideFloat
-                                                 ? hippt::mesh_blocks_per_cu(false, s.scene.full, fmt, stackDepth, ln,
-                                                                             lt, spills, topBytes, lm, poolWords, true)
-                                                 : 0;
-                    c.occKey = occKey;
-                }
-                s.activeTopBytes = topBytes;
-                s.activeBlocksPerCu = c.meshBlocksPerCu[cnt ? 1 : 0];
-                int bpc = s.blocksPerCu > 0 ? s.blocksPerCu : c.meshBlocksPerCu[cnt ? 1 : 0];
-                for (int b = 0; b < count; b += fpb) {
-                    const int nf = std::min(fpb, count - b);
-                    const unsigned total = bandPixels * unsigned(nf);
-                    // the megakernel takes the previous batch's combine along; other batches flush it
-                    const bool fuse = maxDepth > 0 && s.pathMode == 0 && s.fuseCombine != 0;
-                    // chained batches (Ctx::chain): asynchronous camera-pool megakernel batches over
-                    // 4-wide float nodes whose items fit the ring's slot bits
-                    bool chained = fuse && !copy && !cnt && s.chainBatches != 0 &&
-                                   poolWords != 0 &&
-                                   fmt == hippt::kWideFloat && c.meshBlocksPerCuChain > 0 &&
-                                   total <= (1u << hippt::kChainMaxShift);
-                    RingPlan ring;
-                    if (chained) {
-                        ring = ring_plan(total, s.chainBatches, ldsScene, cap);
-                        bool ok = ring.bytes != 0;
-                        if (ok && !ensure_ring(c, ring, &ok, err)) return false;
-                        chained = ok;
-                    }
-                    if ((!fuse || !chained) && !flush_chain(c, err)) return false;
-                    if (!fuse && !flush_deferred(c, err)) return false;
-                    float *scratch = nullptr;
-                    if (!chained && !batch_scratch(c, need, &scratch, err)) return false;
-                    if (maxDepth <= 0) {
-                        // ray_color with depth <= 0 returns black without tracing (RayTracer.h:582-583)
-                        HIP_TRY(hipMemsetAsync(scratch, 0, size_t(total) * 3 * sizeof(float), c.stream));
-                    } else {
-                        hippt::MeshParams p{};
-                        p.nodes = hybrid ? c.nodes4h : quant ? c.nodes4q : half ? c.nodes4f : wide ? c.nodes4 : c.nodes;
-                        p.tris = c.tris;
-                        p.shade = c.shade;
-                        p.mats = c.mats;
-                        p.scratch = scratch;
-                        p.queue = c.queue;
-                        p.stats = c.stats;
-                        p.cam = cam;
-                        p.invW = 1.0f / float(std::max(1, s.width - 1));
-                        p.invH = 1.0f / float(std::max(1, s.height - 1));
-                        p.width = s.width;
-                        p.height = s.height;
-                        p.y0 = c.y0;
-                        p.bandRows = rows;
-                        p.rowStride = c.stride;
-                        p.firstFrame = firstFrame + b;
-                        p.frames = nf;
-                        p.maxDepth = maxDepth;
-                        p.bandPixels = bandPixels;
-                        p.totalItems = total;
-                        p.rcpBandPixels = 1.0f / float(bandPixels);
-                        p.rcpWidth = 1.0f / float(s.width);
-                        p.stackDepth = stackDepth;
-                        p.numNodes = numNodes;
-                        p.numTris = numTris;
-                        p.numMats = numMats;
-                        p.ldsScene = ldsScene ? 1 : 0;
-                        p.full = s.scene.full ? 1 : 0;
-                        // shade once fewer than this many lanes still traverse (re-swept in round 3
-                        // under the sample-length item order, r5y-r6a: LDS scenes 24 with the exits
-                        // below, Cornell 48.4 -> 53.7 G; global-memory trees 32, blob70k 24 and 40
-                        // lower)
-                        // (the general megakernel over a tree in global memory: 24, random_scene
-                        // +5.8% over 32 with the exits below, r6c)
-                        // Re-swept on round 6's kernels (r6aj/r6ak, alternating passes): a whole
-                        // blob70k image 40 over 32 +0.5-0.7% (21,882 -> 22,031 M/s; 36 +0.5%, 44 and 48
-                        // slower), configs[3]'s 4K image +0.6%, but its 1/8 shares 2.433 -> 2.471 ms:
-                        // 40 with the loop exits 22 / 56 below (alone, 40 slowed the shares: r6ak);
-                        // Cornell 28/32 within 0.2% of 24.
-                        const bool fullMega = s.pathMode == 0 && s.scene.full;
-                        // Lambertian batches over a tree in global memory, megakernel or wavefront (this
-                        // wave threshold and the loop exits below; the wavefront's configs[4] 14,243 ->
-                        // 14,436 M/s with 40 / 22 / 56, r6aq; blob70k's 1/4 and 1/8 row shares 4.705 ->
-                        // 4.612 and 2.433 -> 2.391 ms, r6at)
-                        const bool lambertGlobal = !ldsScene && !s.scene.full;
-                        p.waveThreshold = s.waveThreshold >= 0    ? s.waveThreshold
-                                          : ldsScene || fullMega ? 24
-                                          : lambertGlobal        ? 40
-                                                                 : 32;
-                        // claim size: 512 items for the Lambertian kernels' chained and whole-image
-                        // batches (Cornell 1080p/64 spp 7.255 -> 7.199 ms, blob70k 18.94 -> 18.91,
-                        // r5s; chained 1/8 shares Cornell 1.062 -> 1.041, blob70k 2.546 -> 2.547,
-                        // r5ab); 256 for small unchained batches (1/8 shares: Cornell 1.112 -> 1.137
-                        // and blob70k 3.00 -> 3.22 with 512) and the general kernel (cornell_mixed
-                        // 12.06 -> 12.22)
-                        p.chunk = s.chunk > 0 ? s.chunk
-                                  : s.pathMode == 0 && !s.scene.full && (chained || total >= (1u << 26)) ? 512u
-                                                                                                         : 256u;
-                        // Loop exits of the traversal round (measured): trees in global
-                        // memory leave the node loop once <= 17 lanes still search for a leaf (r2
-                        // sweep of the 4-wide kernels: blob70k, 21 levels, best at 17-18; blob64x34
-                        // and random_scene, 16 and 12 levels, best at 15) and the leaf loop once
-                        // <= 48 lanes hold a leaf; LDS scenes at 12 and 8 (round 3, with the item
-                        // order: node exit 4-16 x leaf exit 8-16 within 0.6% of the best, Cornell
-                        // 53.8 G; the round-2 values 4 and 48 gave 48.4 G), except that the general
-                        // kernel and the wavefront keep leaf exit 4 (cornell_mixed +1.4%, Cornell
-                        // wavefront +6% over 12; r6b)
-                        // The general megakernel over a tree in global memory: 12 and 16 (random_scene,
-                        // r6c).  The Lambertian kernels over a tree in global memory, with the wave
-                        // threshold 40: 22 and 56 (blob70k whole image, alternating passes: 22,057 ->
-                        // 22,372 M/s, +1.4%; 20-26 x 48-64 within 0.3% of it, 28 lower, r6ao/r6ap).
-                        const bool lambertMega = s.pathMode == 0 && !s.scene.full;
-                        p.leafExit = unsigned(s.leafExit >= 0 ? s.leafExit
-                                              : ldsScene          ? (lambertMega ? 12 : 4)
-                                              : fullMega          ? 12
-                                              : lambertGlobal     ? 22
-                                                                  : 17);
-                        p.nodeExit = unsigned(s.nodeExit >= 0 ? s.nodeExit
-                                              : ldsScene  ? 8
-                                              : fullMega  ? 16
-                                              : lambertGlobal ? 56
-                                                              : 48);
-                        p.wide = fmt;
-                        p.stackCap = stackCap;
-                        p.topBytes = topBytes;
-                        p.refBits = ldsScene && wide ? packed_ref_bits(numNodes, numTris) : 0u;
-                        // The sky rectangle (below) needs the host copy's root box.  A host-memory vertex
-                        // update's vertices are on the host already: for a scene that fits the LDS copy the
-                        // host copy takes them here, a refit of a few hundred primitives, before anything of
-                        // this batch looks at it; a larger scene's waits for whatever next needs the host
-                        // copy (blob70k's host refit takes 10 ms).
-                        // (the one camera-pool kernel without the sky path, hippt_kernels.hip SKY: the timed
-                        // unchained general LDS kernel with the spilling stack)
-                        const bool skyWanted = s.pathMode == 0 && poolWords != 0 && s.skyRect &&
-                                               !(s.scene.full && ldsScene && spills && !chained && !cnt);
-                        if (skyWanted && ldsScene && s.upd.hostStale && !s.upd.staleEv) settle_scene();
-                        // the LDS scene copy's node boxes trimmed to the render pad (HIPPT_OPT_RENDER_PAD;
-                        // megakernel over an LDS-resident 4-wide float tree only)
-                        const bool trims = s.pathMode == 0 && ldsScene && fmt == hippt::kWideFloat && s.renderPad != 0 &&
-                                           render_pad_holds(s.scene, s.upd.hostStale, cam);
-                        p.padWord = c.padDev;
-                        p.trimScale = trims ? hippt::slab::trim_scale(s.renderPad) : 0.0f;
-                        s.activeRenderPad = trims ? s.renderPad : 0;
-                        // camera-pool megakernels: samples of pixels that cannot see the scene skip the
-                        // traversal (HIPPT_OPT_SKY_RECT).  Not while a device-memory vertex update is
-                        // ahead of the host copy (the scene may have grown past the host's root box).
-                        const bool skyOn = skyWanted && !s.upd.hostStale;
-                        const hippt::skyrect::Rect sr = skyOn ? sky_rect_of(s.scene, cam, s.width, s.height)
-                                                              : hippt::skyrect::whole(s.width, s.height);
-                        p.skyRect = hippt::SkyRect{sr.x0, sr.y0, sr.x1, sr.y1};
-                        s.activeSkyPixels = hippt::skyrect::pixels_outside(sr, s.width, s.height);
-                        p.rngTable = nullptr;
-                        p.poolWords = poolWords;
-                        // Pixel runs by estimated sample length, longest first, per XCD queue
-                        // (megakernel; item_order.h): Cornell +2.4%, cornell_mixed +3%, blob70k
-                        // +0.8% at full size; the slowest 1/8 Cornell share -2% (r5w)
-                        if (s.pathMode == 0 && s.itemOrder != 0) {
-                            const unsigned *table = nullptr;
-                            // the runs' shape: HIPPT_OPT_PIXEL_TILE columns.  Automatic: 8x8 tiles for
-                            // a band of consecutive rows (blob70k 1080p +0.45%, Cornell +0.6%, two
-                            // alternating passes, r6d), row runs for an interleaved share (the tile's
-                            // rows are `stride` image rows apart: the 1/8 shares neutral to -0.9%, r6f)
-                            const int tile = s.pixelTile >= 0 ? s.pixelTile : c.stride == 1 ? 8 : 0;
-                            const unsigned tileShift = tile == 8 ? 3u : tile == 16 ? 4u : tile == 32 ? 5u : 6u;
-                            if (!ensure_order(c, cam, nf, maxDepth, s.itemOrder == 1, tileShift, &table, err))
-                                return false;
-                            if (table) {
-                                p.runOrder = table;
-                                p.runCount = unsigned(c.runCosts.size());
-                                p.runTileShift = c.orderKey.tileShift;
-                            }
-                        }
-                        p.poolOffset = unsigned(hippt::mesh_lds_bytes(stackDepth, ldsScene ? numNodes : 0,
-                                                                      ldsScene ? numTris : 0, wide, topBytes,
-                                                                      ldsScene ? numMats : 0));
-                        if (s.rngTable && !rng_table(c, &p.rngTable, err)) return false;
-                        if (s.pathMode == 1) {
-                            if (!run_wavefront(c, p, cnt, spills, s.scene.stackBound4 + 3, err)) return false;
-                        } else {
-                            long long blocks =
-                                (long long)c.cus * (chained && s.blocksPerCu <= 0 ? c.meshBlocksPerCuChain : bpc);
-                            blocks = std::min<long long>(blocks, (total + hippt::kMeshBlock - 1) / hippt::kMeshBlock);
-                            blocks = std::max<long long>(blocks, 1);
-                            if (!ensure_spill(c, p, blocks, spills, s.scene.stackBound4 + 3, err)) return false;
-                            s.activeChunk = int(p.chunk);
-                            s.activeChainCap = 0;
-                            if (chained) {
-                                p.comb.format = s.pixelFormat;
-                                if (!chain_batch(c, p, blocks, ring, err)) return false;
-                                s.activeChainCap = int(c.chain.cap);
-                                continue;  // launched or taken by the run's last launch; its combine
-                                           // belongs to the run (Ctx::chain)
-                            } else {
-                                HIP_TRY(hipMemsetAsync(c.queue, 0, kQueueBytes, c.stream));
-                                if (c.hasDeferred) {
-                                    p.comb = c.deferred;
-                                    c.hasDeferred = false;
-                                }
-                                p.combCtr = c.queue + kCombCtrWord;
-                            }
-                            EventPair ev;
-                            if (!next_events(c, ev, err)) return false;
-                            HIP_TRY(hipEventRecord(ev.a, c.stream));
-                            HIP_TRY(hippt::launch_mesh(p, int(blocks), cnt, c.stream));
-                            HIP_TRY(hipEventRecord(ev.b, c.stream));
-                            c.pending.push_back({0, ev});
-                        }
-                    }
-                    if (chained && maxDepth > 0) continue;  // its combine belongs to the run (Ctx::chain)
-                    c.deferred = hippt::CombineParams{c.accum, c.out, scratch, bandPixels, total, firstFrame + b, nf,
-                                                      s.pixelFormat};
-                    c.hasDeferred = true;
-                    if (!fuse && !flush_deferred(c, err)) return false;
-                }
-            }
+        bool copied = false;  // the kernel wrote the frame's rows into the host frame (legacy zero copy)
+        if (c.rows > 0 && count > 0) {
+            if (!(mesh ? enqueue_mesh(c, cam, firstFrame, count, maxDepth, copy, err)
+                       : enqueue_sphere4(c, firstFrame, count, maxDepth, copy, dst, &copied, err)))
+                return false;
         }
-        if (copy && rows > 0 && c.hasDeferred && kLegacyZeroCopy) {
-            // a blocking mesh frame: its combine writes the words into the pinned host frame too
-            if (uint32_t *d = host_frame_on_device(dst)) {
-                c.deferredHost = hippt::HostFrame{d, s.width, c.y0, c.stride};
-                copied = true;
-            }
-        }
-        if (copy && !flush_deferred(c, err)) return false;
-        if (copy && rows > 0 && !copied) {
-            if (!copy_rows_async(c, dst, c.out, sizeof(uint32_t), err)) return false;
-        }
+        if (copy && !finish_blocking_frame(c, dst, copied, err)) return false;
     }
     return true;
 }
@@ -2128,52 +2044,30 @@ struct QueryCall {
     int frame = 0;
 };
 
-// The traversal's layout and parameters for the current scene on context c: enqueue_locked's choices
-// (tree width, LDS residency, stack capacity, the top of the tree in LDS) with the wavefront extend
-// kernel's loop exits, over float nodes.
+// The traversal's layout and parameters for the current scene on context c: the render's plan under
+// the queries' profile (hippt_plan.h query_knobs: the wavefront extend kernel's loop parameters, float
+// nodes, no camera pool).  Unlike a render, whose launches take a spill area only when the stack bound
+// exceeds the LDS capacity, the query kernel takes one for every 4-wide tree.
 bool query_setup(Ctx &c, const QueryCall &call, hippt::QueryParams &q, const char **err) {
     State &s = S();
-    const bool wide = s.scene.numNodes4 > 0 && s.bvhWidth != 2;
-    const int numNodes = wide ? s.scene.numNodes4 : s.scene.numNodes, numTris = s.scene.numTris;
-    const int numMats = int(s.scene.mats.size() / 2);
-    const bool ldsScene = s.ldsScene && hippt::mesh_lds_bytes(0, numNodes, numTris, wide, 0, numMats) <=
-                                            hippt::mesh_lds_scene_limit();
-    const bool topTree = wide && !ldsScene;
-    const int capLimit = s.stackCap > 0 ? s.stackCap
-                         : ldsScene     ? 30
-                         : topTree && s.scene.stackBound4 > kWideStackCap ? kSpillStackCap
-                                                                           : kWideStackCap;
-    const int stackCap = wide ? std::max(1, std::min(s.scene.stackBound4, capLimit)) : 0;
-    const int stackDepth = wide ? stackCap + 2 : std::max(1, s.scene.levels);
-    unsigned topBytes = 0;
-    if (topTree && s.ldsTopNodes != 0) {
-        size_t n = size_t(std::min(numNodes, kTopOrderNodes));
-        if (s.ldsTopNodes > 0) {
-            n = std::min(n, size_t(s.ldsTopNodes));
-        } else {
-            const size_t stackBytes = hippt::mesh_lds_bytes(stackDepth, 0, 0, true);
-            const size_t budget = hippt::mesh_lds_block_budget();
-            n = std::min(n, budget > stackBytes ? (budget - stackBytes) / 128 : 0);
-        }
-        topBytes = unsigned(n * 128);
-    }
+    const plan::Facts f = scene_facts(s.scene);
+    const plan::Layout L = plan::layout(f, plan::query_knobs(s.knobs), lds_limits(), false);
     q = hippt::QueryParams{};
-    q.nodes = wide ? c.nodes4 : c.nodes;
+    q.nodes = L.wide ? c.nodes4 : c.nodes;
     q.tris = c.tris;
     q.shade = c.shade;
-    q.stackDepth = stackDepth;
-    q.numNodes = numNodes;
-    q.numTris = numTris;
-    q.ldsScene = ldsScene ? 1 : 0;
-    q.full = s.scene.full ? 1 : 0;
-    q.wide = wide ? 1 : 0;
-    q.stackCap = stackCap;
-    q.spillCap = wide ? s.scene.stackBound4 + 3 : 0;
-    q.topBytes = topBytes;
-    const bool lambertGlobal = !ldsScene && !s.scene.full;
-    q.waveThreshold = s.waveThreshold >= 0 ? s.waveThreshold : ldsScene ? 24 : lambertGlobal ? 40 : 32;
-    q.leafExit = unsigned(s.leafExit >= 0 ? s.leafExit : ldsScene ? 4 : lambertGlobal ? 22 : 17);
-    q.nodeExit = unsigned(s.nodeExit >= 0 ? s.nodeExit : ldsScene ? 8 : lambertGlobal ? 56 : 48);
+    q.stackDepth = L.stackDepth;
+    q.numNodes = L.numNodes;
+    q.numTris = f.numTris;
+    q.ldsScene = L.ldsScene ? 1 : 0;
+    q.full = f.full ? 1 : 0;
+    q.wide = L.wide ? 1 : 0;
+    q.stackCap = L.stackCap;
+    q.spillCap = L.spillCap;
+    q.topBytes = L.topBytes;
+    q.waveThreshold = L.waveThreshold;
+    q.leafExit = L.leafExit;
+    q.nodeExit = L.nodeExit;
     if (call.camera) {
         hippt::QueryCam &k = q.cam;
         k.cam = current_camera();
@@ -2188,16 +2082,17 @@ bool query_setup(Ctx &c, const QueryCall &call, hippt::QueryParams &q, const cha
         k.rcpWidth = 1.0f / float(s.width);
     }
     HIP_TRY(hipSetDevice(c.device));
-    const long long occKey = ((long long)s.scene.version << 24) ^ ((long long)topBytes << 40) ^ (stackDepth << 8) ^
-                             (ldsScene ? 16 : 0) ^ (wide ? 8 : 0) ^ (s.scene.full ? 4 : 0) ^ (call.any ? 2 : 0) ^
-                             (call.camera ? 1 : 0) ^ (call.records ? 32 : 0);
-    if (c.qOccKey != occKey) {
+    OccKey occKey;
+    occKey.version = s.scene.version, occKey.stackDepth = L.stackDepth, occKey.fmt = L.fmt, occKey.topBytes = L.topBytes;
+    occKey.ldsScene = L.ldsScene, occKey.full = f.full;
+    occKey.variant = (call.any ? 1 : 0) | (call.camera ? 2 : 0) | (call.records ? 4 : 0);
+    if (!same_key(c.qOccKey, occKey)) {
         c.qBlocksPerCu = hippt::query_blocks_per_cu(q, call.any, call.camera, call.records);
         c.qOccKey = occKey;
     }
     if (!c.qCtr) HIP_TRY(hipMalloc(&c.qCtr, hippt::kQueryCtrBytes));
     if (!c.qDone) HIP_TRY(hipEventCreateWithFlags(&c.qDone, hipEventDisableTiming));
-    if (wide) {
+    if (L.wide) {
         const size_t bytes = size_t(c.cus) * size_t(c.qBlocksPerCu) * hippt::kMeshBlock * size_t(q.spillCap) * sizeof(int);
         if (c.qSpillBytes < bytes) {  // (no query is in flight: every call waits for its own)
             (void)hipFree(c.qSpill);
@@ -2217,7 +2112,7 @@ bool query_setup(Ctx &c, const QueryCall &call, hippt::QueryParams &q, const cha
 bool query_enqueue(Ctx &c, hippt::QueryParams q, unsigned first, unsigned m, const QueryCall &call, const char **err) {
     q.numRays = m;
     q.firstItem = first;
-    q.chunk = m >= (1u << 20) ? 256u : 64u;
+    q.chunk = plan::query_chunk(m);
     const long long blocks =
         std::max(1LL, std::min<long long>((long long)c.cus * c.qBlocksPerCu, (m + hippt::kMeshBlock - 1) / hippt::kMeshBlock));
     HIP_TRY(hipMemsetAsync(c.qCtr, 0, hippt::kQueryCtrBytes, c.stream));
@@ -2478,8 +2373,8 @@ extern "C" bool hipptUploadScene(const float *verts, const int *triMaterial, int
         // (leaves of <= 2 primitives: Cornell +1.6-1.9%, cornell_mixed +1.0%, r3ap/r3aq), the
         // greedy one for trees read from global memory (SAH-optimal: blob70k -9%, random_scene -4%)
         auto fits = [&](const hippt::Bvh4 &b) {
-            return hippt::mesh_lds_bytes(0, int(b.nodes.size() / hippt::kNode4Words), numPrims, true, 0,
-                                         numMaterials) <= hippt::mesh_lds_scene_limit();
+            return plan::fits_lds_scene(int(b.nodes.size() / hippt::kNode4Words), numPrims, true, numMaterials,
+                                        lds_limits().scene);
         };
         if (fits(bvh4)) {
             hippt::BvhParams p = s.bvh;
@@ -2489,7 +2384,7 @@ extern "C" bool hipptUploadScene(const float *verts, const int *triMaterial, int
             if (fits(sah)) bvh4 = std::move(sah);
         }
     }
-    hippt::order_bvh4_top(bvh4, kTopOrderNodes);
+    hippt::order_bvh4_top(bvh4, plan::kTopOrderNodes);
     sc.nodes4.assign(bvh4.nodes.size() / 4, float4{});
     std::memcpy(sc.nodes4.data(), bvh4.nodes.data(), bvh4.nodes.size() * sizeof(uint32_t));
     sc.numNodes4 = int(bvh4.nodes.size() / hippt::kNode4Words);
@@ -3173,10 +3068,10 @@ extern "C" bool hipptSetOption(int key, long long value) try {
     std::lock_guard<std::mutex> g(S().mu);
     State &s = S();
     switch (key) {
-    case HIPPT_OPT_COUNT_TRAVERSAL: s.countTraversal = value != 0; return true;
+    case HIPPT_OPT_COUNT_TRAVERSAL: s.knobs.countTraversal = value != 0; return true;
     case HIPPT_OPT_WAVE_THRESHOLD:
         if (value < -1 || value > 64) return false;
-        s.waveThreshold = int(value);
+        s.knobs.waveThreshold = int(value);
         return true;
     case HIPPT_OPT_SCRATCH_MB:
         if (value < 1) return false;
@@ -3184,16 +3079,16 @@ extern "C" bool hipptSetOption(int key, long long value) try {
         return true;
     case HIPPT_OPT_CHUNK:
         if (value != 0 && (value < 64 || value > (1 << 20) || value % 64)) return false;
-        s.chunk = unsigned(value);
+        s.knobs.chunk = unsigned(value);
         return true;
     case HIPPT_OPT_BLOCKS_PER_CU:
         if (value < 0 || value > 8) return false;
         s.blocksPerCu = int(value);
         return true;
-    case HIPPT_OPT_LDS_SCENE: s.ldsScene = value != 0; return true;
+    case HIPPT_OPT_LDS_SCENE: s.knobs.ldsScene = value != 0; return true;
     case HIPPT_OPT_PATH_MODE:
         if (value != 0 && value != 1) return false;
-        s.pathMode = int(value);
+        s.knobs.pathMode = int(value);
         return true;
     case HIPPT_OPT_WAVEFRONT_SLOTS:
         if (value < 64 || value > (1LL << 28)) return false;
@@ -3217,11 +3112,11 @@ extern "C" bool hipptSetOption(int key, long long value) try {
         return true;
     case HIPPT_OPT_LEAF_EXIT:
         if (value < -1 || value > 64) return false;
-        s.leafExit = int(value);
+        s.knobs.leafExit = int(value);
         return true;
     case HIPPT_OPT_NODE_EXIT:
         if (value < -1 || value > 64) return false;
-        s.nodeExit = int(value);
+        s.knobs.nodeExit = int(value);
         return true;
     case HIPPT_OPT_BVH_SAH:
         if (value != 0 && value != 1) return false;
@@ -3229,19 +3124,19 @@ extern "C" bool hipptSetOption(int key, long long value) try {
         return true;
     case HIPPT_OPT_BVH_WIDTH:
         if (value != 0 && value != 2 && value != 4) return false;
-        s.bvhWidth = int(value);
+        s.knobs.bvhWidth = int(value);
         return true;
     case HIPPT_OPT_STACK_CAP:
-        if (value != 0 && (value < 4 || value > 30)) return false;
-        s.stackCap = int(value);
+        if (value != 0 && (value < 4 || value > plan::kLdsStackCap)) return false;
+        s.knobs.stackCap = int(value);
         return true;
     case HIPPT_OPT_BVH_QUANT:
         if (value < -1 || value > 3) return false;
-        s.bvhQuant = int(value);
+        s.knobs.bvhQuant = int(value);
         return true;
     case HIPPT_OPT_LDS_TOP_NODES:
-        if (value < -1 || value > kTopOrderNodes) return false;
-        s.ldsTopNodes = int(value);
+        if (value < -1 || value > plan::kTopOrderNodes) return false;
+        s.knobs.ldsTopNodes = int(value);
         return true;
     case HIPPT_OPT_BVH_COLLAPSE:
         if (value < -1 || value > 1) return false;
@@ -3265,11 +3160,11 @@ extern "C" bool hipptSetOption(int key, long long value) try {
         return true;
     case HIPPT_OPT_CAMERA_POOL:
         if (value < -1 || value > 1) return false;
-        s.cameraPool = int(value);
+        s.knobs.cameraPool = int(value);
         return true;
     case HIPPT_OPT_FUSE_COMBINE:
         if (value < -1 || value > 1) return false;
-        s.fuseCombine = int(value);
+        s.knobs.fuseCombine = int(value);
         return true;
     case HIPPT_OPT_ITEM_ORDER:
         if (value < -1 || value > 1) return false;
@@ -3281,7 +3176,7 @@ extern "C" bool hipptSetOption(int key, long long value) try {
         return true;
     case HIPPT_OPT_CHAIN:
         if (value < -1 || value > 16) return false;
-        s.chainBatches = int(value);
+        s.knobs.chainBatches = int(value);
         return true;
     case HIPPT_OPT_CHAIN_AUDIT:
         if (value != 0 && value != 1) return false;
@@ -3297,11 +3192,11 @@ extern "C" bool hipptSetOption(int key, long long value) try {
         return true;
     case HIPPT_OPT_RENDER_PAD:
         if (value != 0 && (value < hippt::slab::kRenderPadMin || value > hippt::slab::kRenderPadMax)) return false;
-        s.renderPad = int(value);
+        s.knobs.renderPad = int(value);
         return true;
     case HIPPT_OPT_SKY_RECT:
         if (value != 0 && value != 1) return false;
-        s.skyRect = value == 1;
+        s.knobs.skyRect = value == 1;
         return true;
     default: return false;
     }
@@ -3324,40 +3219,40 @@ extern "C" long long hipptGetOption(int key) try {
     std::lock_guard<std::mutex> g(S().mu);
     State &s = S();
     switch (key) {
-    case HIPPT_OPT_COUNT_TRAVERSAL: return s.countTraversal ? 1 : 0;
-    case HIPPT_OPT_WAVE_THRESHOLD: return s.waveThreshold;
+    case HIPPT_OPT_COUNT_TRAVERSAL: return s.knobs.countTraversal ? 1 : 0;
+    case HIPPT_OPT_WAVE_THRESHOLD: return s.knobs.waveThreshold;
     case HIPPT_OPT_SCRATCH_MB: return s.scratchMB;
-    case HIPPT_OPT_CHUNK: return s.chunk;
+    case HIPPT_OPT_CHUNK: return s.knobs.chunk;
     case HIPPT_OPT_BLOCKS_PER_CU: return s.blocksPerCu;
-    case HIPPT_OPT_LDS_SCENE: return s.ldsScene ? 1 : 0;
-    case HIPPT_OPT_PATH_MODE: return s.pathMode;
+    case HIPPT_OPT_LDS_SCENE: return s.knobs.ldsScene ? 1 : 0;
+    case HIPPT_OPT_PATH_MODE: return s.knobs.pathMode;
     case HIPPT_OPT_WAVEFRONT_SLOTS: return s.wfSlots;
     case HIPPT_OPT_BVH_LEAF: return s.bvh.maxLeaf;
     case HIPPT_OPT_BVH_TRAVERSAL_COST: return (long long)std::lround(s.bvh.traversalCost * 100.0f);
     case HIPPT_OPT_BVH_MAX_DEPTH: return s.bvh.maxDepth;
     case HIPPT_OPT_DEVICE_ROWS: return s.deviceInterleave ? 1 : 0;
-    case HIPPT_OPT_LEAF_EXIT: return s.leafExit;
-    case HIPPT_OPT_NODE_EXIT: return s.nodeExit;
+    case HIPPT_OPT_LEAF_EXIT: return s.knobs.leafExit;
+    case HIPPT_OPT_NODE_EXIT: return s.knobs.nodeExit;
     case HIPPT_OPT_BVH_SAH: return s.bvh.sahMode;
-    case HIPPT_OPT_BVH_WIDTH: return s.bvhWidth;
-    case HIPPT_OPT_STACK_CAP: return s.stackCap;
-    case HIPPT_OPT_BVH_QUANT: return s.bvhQuant;
-    case HIPPT_OPT_LDS_TOP_NODES: return s.ldsTopNodes;
+    case HIPPT_OPT_BVH_WIDTH: return s.knobs.bvhWidth;
+    case HIPPT_OPT_STACK_CAP: return s.knobs.stackCap;
+    case HIPPT_OPT_BVH_QUANT: return s.knobs.bvhQuant;
+    case HIPPT_OPT_LDS_TOP_NODES: return s.knobs.ldsTopNodes;
     case HIPPT_OPT_BVH_COLLAPSE: return s.bvh.collapse;
     case HIPPT_OPT_BVH_NODE_COST: return (long long)std::lround(s.bvh.nodeCost * 100.0f);
     case HIPPT_OPT_BVH_LEAF4: return s.bvh.maxLeaf4;
     case HIPPT_OPT_RNG_TABLE: return s.rngTable ? 1 : 0;
     case HIPPT_OPT_PIXEL_FORMAT: return s.pixelFormat;
-    case HIPPT_OPT_CAMERA_POOL: return s.cameraPool;
-    case HIPPT_OPT_FUSE_COMBINE: return s.fuseCombine;
+    case HIPPT_OPT_CAMERA_POOL: return s.knobs.cameraPool;
+    case HIPPT_OPT_FUSE_COMBINE: return s.knobs.fuseCombine;
     case HIPPT_OPT_ITEM_ORDER: return s.itemOrder;
     case HIPPT_OPT_WAVEFRONT_SORT: return s.wfSort;
-    case HIPPT_OPT_CHAIN: return s.chainBatches;
+    case HIPPT_OPT_CHAIN: return s.knobs.chainBatches;
     case HIPPT_OPT_CHAIN_AUDIT: return s.chainAudit ? 1 : 0;
     case HIPPT_OPT_PIXEL_TILE: return s.pixelTile;
     case HIPPT_OPT_QUERY_SLICE: return s.querySlice;
-    case HIPPT_OPT_RENDER_PAD: return s.renderPad;
-    case HIPPT_OPT_SKY_RECT: return s.skyRect ? 1 : 0;
+    case HIPPT_OPT_RENDER_PAD: return s.knobs.renderPad;
+    case HIPPT_OPT_SKY_RECT: return s.knobs.skyRect ? 1 : 0;
     case HIPPT_INFO_LDS_TOP_BYTES: return s.activeTopBytes;
     case HIPPT_INFO_BLOCKS_PER_CU: return s.activeBlocksPerCu;
     case HIPPT_INFO_CHUNK: return s.activeChunk;
@@ -3423,7 +3318,7 @@ extern "C" hipptBvh *hipptBvhBuild(const float *verts, int numTris, float extent
         return nullptr;
     }
     hippt::collapse_bvh4(b->bvh, b->bvh4, params);
-    hippt::order_bvh4_top(b->bvh4, kTopOrderNodes);
+    hippt::order_bvh4_top(b->bvh4, plan::kTopOrderNodes);
     (void)hippt::quantize_bvh4(b->bvh4, b->bvh4q);  // empty for boxes near +-FLT_MAX
     return b.release();
 } catch (const std::exception &e) {

@@ -6,6 +6,8 @@
 
 #include <cstdint>
 
+#include "hippt_plan.h"
+
 namespace hippt {
 
 struct CameraF {  // layout == hipptCamera (include/hippt.h)
@@ -94,7 +96,7 @@ struct MeshParams {
     // breadth-first, bvh_builder.h order_bvh4_top) copied to LDS address 0 and read from there
     unsigned topBytes;
     // LDS-resident 4-wide trees: low bits of a packed child key that carry the child's code
-    // (trace::child_key_p; hippt_api.cpp packed_ref_bits)
+    // (trace::child_key_p; hippt_plan.h packed_ref_bits)
     unsigned refBits;
     // The queues' order of the batch's items (item_order.h build_item_table): queue position
     // fl*bandPixels + 64*j + k is item k of the run at runOrder[fl*runCount + j] for j < runCount
@@ -166,10 +168,6 @@ constexpr unsigned kChainCtlWord = kChainSlotsMax * kChainBlockWords;
 // XCD: the copy (64-bit), the realtime stamp of its last completed refresh, the stamp of the last
 // claimed refresh)
 constexpr unsigned kChainBoxWord = kChainCtlWord + 128, kChainCtlWords = kChainBoxWord + 8 * 32;
-// batches of at most 2^kChainMaxShift items chain (the slot bits above them, kNone above all)
-constexpr unsigned kChainMaxShift = 27;
-// camera-pool kernels: per-wave state words in LDS before each wave's pool (trace::WaveWords)
-constexpr unsigned kWaveWords = 22;
 
 // The chain's final combine (launch_chain_flush): every batch of the run that no launch combined,
 // [first uncombined (from the control block, launch epoch `epoch`), lastSeq], in order per pixel.
@@ -188,9 +186,6 @@ struct ChainFlushParams {
 constexpr unsigned kAuditBatches = 256, kAuditWords = 16, kAuditRuns = 64;
 constexpr unsigned kAuditRunWords = (kAuditBatches + 1) * kAuditWords;
 
-
-// MeshParams::wide
-enum { kWide2 = 0, kWideFloat = 1, kWideQuant = 2, kWideHybrid = 3, kWideHalf = 4 };
 
 // Material kinds (RayTracer.h:473-540) and the sphere flag of a shading record.
 enum { kLambertian = 0, kMetal = 1, kDielectric = 2 };
@@ -217,16 +212,11 @@ hipError_t launch_rng_table(uint32_t *table, hipStream_t s);
 // Resident mesh-kernel blocks per CU for a given LDS stack depth and LDS scene size.
 int mesh_blocks_per_cu(bool countTraversal, bool full, int fmt, int stackDepth, int ldsNodes, int ldsTris, bool spill,
                        unsigned topBytes = 0, int ldsMats = 0, int poolWords = 0, bool chain = false);
-// (poolWords != 0: each wave's pool block also holds its kWaveWords state words)
-size_t mesh_lds_bytes(int stackDepth, int ldsNodes, int ldsTris, bool wide, unsigned topBytes = 0, int ldsMats = 0,
-                      int poolWords = 0);
-// camera-ray pool words per ray: item, rng, direction (+ origin unless every ray starts at the
-// camera origin)
-constexpr int kPoolWordsPinhole = 5, kPoolWordsFull = 8;
+// The LDS layout's bytes (mesh_lds_bytes), the node formats (kWide*), kMeshBlock and the pool's words
+// per ray: hippt_plan.h.  The limits its planner takes as numbers:
 // LDS bytes per block that keep the persistent grid's resident blocks within a CU's LDS
 size_t mesh_lds_block_budget();
 size_t mesh_lds_scene_limit();
-constexpr int kMeshBlock = 256;
 // Launch counters (MeshParams::stats, Sphere4Params::stats): kStatSlots copies of kStatWords
 // words ([0..3] hipptStats counters, [4..19] phase profile, [20..24] hit-children histogram),
 // block b adding into copy b % kStatSlots; the host sums the copies.  One shared copy took every
@@ -235,11 +225,5 @@ constexpr int kMeshBlock = 256;
 constexpr int kStatWords = 32, kStatSlots = 64;
 // megakernel work queues (one per XCD; hippt_trace.h queue_start splits the items evenly)
 constexpr unsigned kMeshQueues = 8;
-// LDS-resident scene copies: 2-wide nodes at an 80-byte stride, 4-wide nodes in the 128-byte
-// global layout (the octant row addressing by or/xor needs 128-byte alignment; a 144- or
-// 160-byte stride cut the LDS bank conflicts of node rows by 40% but not the kernel time, and
-// the add-based addressing it needs costs registers: spills in the general kernels).
-constexpr int kLdsNodeF4 = 5;
-constexpr int kLdsNode4F4 = 8;
 
 }  // namespace hippt

@@ -910,16 +910,6 @@ hipError_t launch_sphere4(const Sphere4Params &p, hipStream_t s) {
     return hipGetLastError();
 }
 
-// Stack: one spare slot per lane above the deepest level for the speculative far-child
-// write; then (LDS_SCENE) the scene copy.
-size_t mesh_lds_bytes(int stackDepth, int ldsNodes, int ldsTris, bool wide, unsigned topBytes, int ldsMats,
-                      int poolWords) {
-    return size_t(stackDepth + 1) * kMeshBlock * sizeof(int) +
-           size_t(ldsNodes) * (wide ? kLdsNode4F4 : kLdsNodeF4) * 16 + size_t(ldsTris) * (3 + 1) * 16 + topBytes +
-           size_t(ldsMats) * 2 * 16 +
-           (poolWords ? (size_t(poolWords) * 64 + kWaveWords) * (kMeshBlock / 64) * sizeof(float) : 0);
-}
-
 size_t mesh_lds_scene_limit() { return 24u << 10; }
 
 // waves a SIMD holds under the SGPR budget: 800 SGPRs per SIMD, 16 of them reserved per wave

@@ -1323,7 +1323,7 @@ __device__ __forceinline__ void cas(unsigned &ka, int &ca, unsigned &kb, int &cb
 // LDS copy of the nodes holds the codes already masked (mesh_kernel's scene copy).  An interior code (a
 // node byte offset) and a leaf code (~(first<<4 | count)) of a scene that fits the LDS copy are
 // small enough in magnitude that their low refBits bits, sign-extended, give them back
-// (hippt_api.cpp packed_ref_bits): the sorted keys ARE the sorted codes, so the sorting network
+// (hippt_plan.h packed_ref_bits): the sorted keys ARE the sorted codes, so the sorting network
 // is 5 unsigned min/max pairs (no compare + 4 selects per exchange moving the codes along), and the
 // stack holds keys.  Truncating the distance to its high bits only reorders near-equal children,
 // and the closest hit is argmin (t, primitive id): no result bit depends on the visiting order.
