@@ -228,6 +228,46 @@ bool hipptTraceHits(const float *rays, long long numRays, int flags, hipptHit *h
 /* hipptTraceCamera with a record per pixel: width*height records, row 0 = v = 0. */
 bool hipptTraceCameraHits(int frame, int flags, hipptHit *hits, const char **errorMessage);
 
+/* ---- denoiser ---------------------------------------------------------------------------- */
+/* An edge-avoiding A-trous wavelet filter (Dammertz et al. 2010) over the accumulation buffer, on the
+ * device, guided by the hit records of one camera sample (what hipptTraceCameraHits returns) and the
+ * uploaded materials.  Per pixel p, with c(p) the accumulation's rgb, in IEEE float32 + - * / only:
+ *   albedo'(p)  per channel the material's albedo where p is a hit of a HIPPT_MAT_LAMBERTIAN material
+ *               and that channel is >= 2^-6, else 1;  i_0(p) = c(p) / albedo'(p)
+ *   pass k      (k = 0 .. passes - 1, s = 2^k): a sky pixel keeps i_k(p); a hit pixel takes the 25 taps
+ *               q = p + s * (dx, dy), dy = -2..2 outside, dx = -2..2 inside, skipping q outside the
+ *               image or over the sky, each with the weight
+ *                 w = ((K[|dy|] K[|dx|] * wn) * wz) * wc,   K = {3/8, 1/4, 1/16}
+ *                 wn = max(0, n_p . n_q) squared normalPower times
+ *                 wz = 1 / (1 + xz^2), xz = |t_p - t_q| / (sigmaDepth * (t_p * s))
+ *               wc = 1 / (1 + |i_k(p) - i_k(q)|^2 / (sigmaColor / s)^2)
+ *               and i_{k+1}(p) = sum(w i_k(q)) / sum(w), summed in tap order
+ *   output      rgba(p) = (i_passes(p) * albedo'(p), 1); the pixel word is the renderer's own of it.
+ * DESIGN.md section 13 has the order of every operation; the result is reproducible bit for bit.
+ * The call flushes what readers of the image flush (as hipptReadback), reads the accumulation and writes
+ * buffers of its own and the caller's outputs only: the accumulation, the image, the frame count, the
+ * counters of hipptGetStats and the chain audit are as if it had not been made.  It needs an uploaded
+ * scene (the built-in scene has no records) and one context that holds every row of the image: with
+ * more than one device, a row range or a row interleave it fails. */
+enum { HIPPT_DENOISE_NO_DEMODULATE = 1,   /* albedo' = 1 everywhere */
+       HIPPT_DENOISE_DEVICE = 2 };        /* pixels / rgba are device memory of the context's device
+                                             (rgba 16-byte aligned), checked as hipptTraceHits checks */
+typedef struct hipptDenoiseParams {       /* 32 bytes, part of the ABI */
+    int   passes;       /* 0..8; pass k uses tap spacing 2^k.  default 5 */
+    int   guideFrame;   /* camera sample whose hit records guide the filter (>= 0).  default 0 */
+    int   normalPower;  /* 0..10: normal weight = max(0, n_p.n_q)^(2^normalPower), by repeated squaring.  default 6 */
+    int   flags;
+    float sigmaColor;   /* > 0, finite.  default 1.0 */
+    float sigmaDepth;   /* > 0, finite.  default 0.05 */
+    float reserved[2];  /* must be 0 */
+} hipptDenoiseParams;
+void hipptDenoiseDefaults(hipptDenoiseParams *out);
+/* params null = defaults.  pixels: W*H output words (current HIPPT_OPT_PIXEL_FORMAT), rgba: W*H*4 floats
+ * (linear, alpha 1), row 0 = v = 0; either may be null, not both.  Blocking: runs after the work
+ * already queued and waits for its own.  Every argument error returns false with a message before any
+ * device call. */
+bool hipptDenoise(const hipptDenoiseParams *params, unsigned int *pixels, float *rgba, const char **errorMessage);
+
 /* ---- counters and options ---------------------------------------------------------- */
 typedef struct hipptStats {
     unsigned long long segments;      /* closest-hit queries traced (rays x bounces) */
@@ -376,6 +416,9 @@ enum {
                                        HIPPT_INFO_SKY_RECT_PIXELS: 0).  Same results either way;
                                        with HIPPT_OPT_COUNT_TRAVERSAL, nodeVisits counts only the traversals
                                        made */
+    , HIPPT_OPT_DENOISE_TIMING = 36 /* 1: hipptDenoise brackets each of its stages with timing events and keeps
+                                       their device times (HIPPT_INFO_DENOISE_NS); 0 (default): no events.
+                                       Same results either way (a measuring aid) */
 };
 /* Records of the chained runs closed since the last call (HIPPT_OPT_CHAIN_AUDIT), as 32-bit words:
  * per run a 16-word header  [0] 0xC4A1D17 [1] run id [2] device [3] batch 0's first frame [4] frames
@@ -408,7 +451,11 @@ enum { HIPPT_INFO_LDS_TOP_BYTES = 100, HIPPT_INFO_BLOCKS_PER_CU = 101, HIPPT_INF
        HIPPT_INFO_UPDATE_DROPPED = 104 /* triangles the last device-memory hipptUpdateVertices dropped
                                           for a non-finite coordinate; reading it synchronises */,
        HIPPT_INFO_RENDER_PAD = 105,
-       HIPPT_INFO_SKY_RECT_PIXELS = 106 };
+       HIPPT_INFO_SKY_RECT_PIXELS = 106,
+       /* device time in nanoseconds of stage k of the last hipptDenoise made under
+          HIPPT_OPT_DENOISE_TIMING, key HIPPT_INFO_DENOISE_NS + k: 0 the guide query, 1 prepare,
+          2..9 passes 0..7, 10 finish (0: the stage did not run) */
+       HIPPT_INFO_DENOISE_NS = 200 };
 bool hipptSetOption(int key, long long value);
 long long hipptGetOption(int key);
 /* BVH width (2 or 4) the last mesh render traversed (0 before any): what nodeVisits count. */

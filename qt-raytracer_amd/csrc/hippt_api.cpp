@@ -34,6 +34,7 @@
 
 #include "bvh_builder.h"
 #include "mesh_io.h"
+#include "hippt_denoise.h"
 #include "hippt_device.h"
 #include "hippt_plan.h"
 #include "hippt_query.h"
@@ -257,6 +258,12 @@ struct Ctx {
     hipEvent_t qDone = nullptr;
     OccKey qOccKey;  // of qBlocksPerCu
     int qBlocksPerCu = 0;
+    // Denoiser (hipptDenoise, hippt_denoise.h): one buffer of 80 bytes per pixel (the guide sample's hit
+    // records, two colour buffers, the guide), allocated at first use, reused while large enough and
+    // freed with the context; the stages' timing events (HIPPT_OPT_DENOISE_TIMING), created on use.
+    void *dnBuf = nullptr;
+    size_t dnBytes = 0;
+    std::vector<hipEvent_t> dnEv;
 };
 
 struct SceneHost {
@@ -327,6 +334,8 @@ struct State {
     int pixelTile = -1;    // the item order's runs: tile columns (HIPPT_OPT_PIXEL_TILE; 0 rows, -1 automatic)
     bool chainAudit = false;            // HIPPT_OPT_CHAIN_AUDIT
     long long querySlice = 0;           // rays per staged slice of a host-memory query (HIPPT_OPT_QUERY_SLICE; 0 automatic)
+    bool denoiseTiming = false;         // HIPPT_OPT_DENOISE_TIMING
+    long long denoiseNs[hippt::kDenoiseStages] = {};  // HIPPT_INFO_DENOISE_NS + k of the last timed hipptDenoise
     std::vector<unsigned> auditWords;   // closed runs' audit words not yet read (hipptChainAudit)
     std::vector<std::pair<int, uint32_t *>> rngTables;  // per device, built on first use
     // The big work buffers (sample scratch, chain ring, spill area) of the contexts a re-initialization
@@ -738,6 +747,8 @@ void destroy_ctx(Ctx &c, bool keep) {
     (void)hipFree(c.qSpill);
     (void)hipFree(c.qStage);
     if (c.qDone) (void)hipEventDestroy(c.qDone);
+    (void)hipFree(c.dnBuf);
+    for (hipEvent_t e : c.dnEv) (void)hipEventDestroy(e);
     (void)hipHostFree(c.wfHost);
     for (hipEvent_t e : c.wfPoll)
         if (e) (void)hipEventDestroy(e);
@@ -2243,6 +2254,135 @@ bool query_locked(const QueryCall &call, const char **err) {
     return true;
 }
 
+// ---- denoiser (hippt_denoise.hip; include/hippt.h hipptDenoise) ----
+// Input side as hipptReadback: the image's readers' flush, then the accumulation.  Everything after
+// that goes on the context's stream and writes the context's denoiser buffer and the caller's outputs
+// only: the guide sample's camera hit records (the ray queries' own launch, into the buffer), prepare,
+// the passes between two colour buffers, finish; the call waits for its own event, as queries do.
+bool denoise_locked(const hipptDenoiseParams *params, unsigned int *pixels, float *rgba, const char **err) {
+    State &s = S();
+    hipptDenoiseParams P;
+    hipptDenoiseDefaults(&P);
+    if (params) P = *params;
+    // argument and state checks first: none of them touches the GPU
+    if (P.passes < 0 || P.passes > hippt::kDenoiseMaxPasses) return fail(err, "denoise: passes out of range (0..8)");
+    if (P.guideFrame < 0) return fail(err, "denoise: negative guide frame");
+    if (P.normalPower < 0 || P.normalPower > hippt::kDenoiseMaxNormalPower)
+        return fail(err, "denoise: normal power out of range (0..10)");
+    if (!(P.sigmaColor > 0.0f) || !std::isfinite(P.sigmaColor)) return fail(err, "denoise: sigmaColor must be positive and finite");
+    if (!(P.sigmaDepth > 0.0f) || !std::isfinite(P.sigmaDepth)) return fail(err, "denoise: sigmaDepth must be positive and finite");
+    if (P.flags & ~(HIPPT_DENOISE_NO_DEMODULATE | HIPPT_DENOISE_DEVICE)) return fail(err, "denoise: unknown flags");
+    if (P.reserved[0] != 0.0f || P.reserved[1] != 0.0f) return fail(err, "denoise: reserved fields must be 0");
+    if (!pixels && !rgba) return fail(err, "denoise: no output buffer");
+    if (s.scene.kind != HIPPT_SCENE_MESH)
+        return fail(err, "denoise: needs a scene from hipptUploadMesh or hipptUploadScene (the built-in scene has no hit records)");
+    if (!s.ready || s.ctxs.empty()) return fail(err, "denoise: HIP path tracer not initialized");
+    if (s.ctxs.size() != 1) return fail(err, "denoise: needs the whole image on one device (more than one device is set)");
+    Ctx &c = s.ctxs[0];
+    if (c.y0 != 0 || c.stride != 1 || c.rows != s.height)
+        return fail(err, "denoise: needs every row of the image (a row range or a row interleave is set)");
+    const long long n = (long long)s.width * (long long)s.height;
+    if (n > (1LL << 31) - 1) return fail(err, "denoise: image too large");
+    const bool device = (P.flags & HIPPT_DENOISE_DEVICE) != 0;
+    if (device) {
+        const void *ptrs[2] = {pixels, rgba};
+        const size_t align[2] = {4, 16};
+        for (int k = 0; k < 2; ++k) {
+            if (!ptrs[k]) continue;
+            hipPointerAttribute_t a{};
+            if (hipPointerGetAttributes(&a, ptrs[k]) != hipSuccess || a.type != hipMemoryTypeDevice) {
+                (void)hipGetLastError();
+                return fail(err, "denoise: HIPPT_DENOISE_DEVICE needs device memory pointers");
+            }
+            if (a.device != c.device) return fail(err, "denoise: the pointers are not on the context's device");
+            if (reinterpret_cast<uintptr_t>(ptrs[k]) % align[k]) return fail(err, "denoise: misaligned device pointer");
+        }
+    }
+    if (!sync_locked(err)) return false;
+    HIP_TRY(hipSetDevice(c.device));
+    if (!ensure_scene(c, err)) return false;
+    const size_t px = size_t(n);
+    const size_t bytes = px * 80;
+    if (c.dnBytes < bytes) {  // (no denoise is in flight: every call waits for its own)
+        (void)hipFree(c.dnBuf);
+        c.dnBuf = nullptr;
+        c.dnBytes = 0;
+        HIP_TRY(hipMalloc(&c.dnBuf, bytes));
+        c.dnBytes = bytes;
+    }
+    float4 *const hits = static_cast<float4 *>(c.dnBuf);  // 2 per pixel
+    float4 *col[2] = {hits + 2 * px, hits + 3 * px};
+    float4 *const guide = hits + 4 * px;
+    const bool timing = s.denoiseTiming;
+    if (timing)
+        while (c.dnEv.size() < size_t(hippt::kDenoiseStages) + 1) {
+            hipEvent_t e;
+            HIP_TRY(hipEventCreate(&e));
+            c.dnEv.push_back(e);
+        }
+    int marks = 0;  // events recorded so far: stageOf[m] ran between events m and m + 1
+    int stageOf[hippt::kDenoiseStages] = {};
+    auto mark = [&](int stage) -> bool {  // closes `stage` (-1: opens the first)
+        if (!timing) return true;
+        HIP_TRY(hipEventRecord(c.dnEv[size_t(marks)], c.stream));
+        if (stage >= 0) stageOf[marks - 1] = stage;
+        ++marks;
+        return true;
+    };
+    if (!mark(-1)) return false;
+    // the guides: sample guideFrame's camera hit records
+    QueryCall call;
+    call.camera = true;
+    call.records = true;
+    call.frame = P.guideFrame;
+    call.hits = reinterpret_cast<hipptHit *>(hits);
+    hippt::QueryParams q;
+    if (!query_setup(c, call, q, err)) return false;
+    constexpr long long kLaunchRays = 1LL << 30;
+    for (long long at = 0; at < n; at += kLaunchRays) {
+        q.hits = hits + 2 * at;
+        if (!query_enqueue(c, q, unsigned(at), unsigned(std::min(kLaunchRays, n - at)), call, err)) return false;
+    }
+    if (!mark(0)) return false;
+    const int demodulate = (P.flags & HIPPT_DENOISE_NO_DEMODULATE) ? 0 : 1;
+    HIP_TRY(hippt::launch_denoise_prepare(
+        hippt::DenoisePrepareParams{c.accum, hits, c.mats, col[0], guide, unsigned(n), demodulate}, c.stream));
+    if (!mark(1)) return false;
+    int cur = 0;
+    for (int k = 0; k < P.passes; ++k) {
+        const float fs = float(1 << k);
+        const float sigma = P.sigmaColor * (1.0f / fs);
+        hippt::DenoisePassParams pp{col[cur], guide, col[cur ^ 1], s.width, s.height, k, P.normalPower,
+                                    sigma * sigma, fs, P.sigmaDepth};
+        HIP_TRY(hippt::launch_denoise_pass(pp, c.stream));
+        cur ^= 1;
+        if (!mark(2 + k)) return false;
+    }
+    // host outputs are staged in what the passes no longer need: rgba in the other colour buffer, the
+    // words in the guide
+    float4 *const drgba = rgba ? (device ? reinterpret_cast<float4 *>(rgba) : col[cur ^ 1]) : nullptr;
+    uint32_t *const dwords = pixels ? (device ? pixels : reinterpret_cast<uint32_t *>(guide)) : nullptr;
+    HIP_TRY(hippt::launch_denoise_finish(
+        hippt::DenoiseFinishParams{col[cur], hits, c.mats, drgba, dwords, unsigned(n), demodulate, s.pixelFormat}, c.stream));
+    if (!mark(2 + hippt::kDenoiseMaxPasses)) return false;
+    if (!device) {
+        if (rgba) HIP_TRY(hipMemcpyAsync(rgba, drgba, px * sizeof(float4), hipMemcpyDeviceToHost, c.stream));
+        if (pixels) HIP_TRY(hipMemcpyAsync(pixels, dwords, px * sizeof(uint32_t), hipMemcpyDeviceToHost, c.stream));
+    }
+    if (!c.qDone) HIP_TRY(hipEventCreateWithFlags(&c.qDone, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(c.qDone, c.stream));
+    HIP_TRY(hipEventSynchronize(c.qDone));
+    if (timing) {
+        for (long long &v : s.denoiseNs) v = 0;
+        for (int m = 0; m + 1 < marks; ++m) {
+            float ms = 0.0f;
+            HIP_TRY(hipEventElapsedTime(&ms, c.dnEv[size_t(m)], c.dnEv[size_t(m) + 1]));
+            s.denoiseNs[stageOf[m]] = (long long)std::llround(double(ms) * 1e6);
+        }
+    }
+    return true;
+}
+
 }  // namespace
 
 // ---- reference ABI ----------------------------------------------------------------------------
@@ -2757,6 +2897,27 @@ extern "C" bool hipptTraceCameraHits(int frame, int flags, hipptHit *hits, const
     return fail_free(err, "unknown exception");
 }
 
+extern "C" void hipptDenoiseDefaults(hipptDenoiseParams *out) try {
+    if (!out) return;
+    std::memset(out, 0, sizeof(*out));
+    out->passes = 5;
+    out->guideFrame = 0;
+    out->normalPower = 6;
+    out->sigmaColor = 1.0f;
+    out->sigmaDepth = 0.05f;
+} catch (...) {
+    // an exception must not cross the C ABI (the caller is C or Qt code)
+}
+
+extern "C" bool hipptDenoise(const hipptDenoiseParams *params, unsigned int *pixels, float *rgba, const char **err) try {
+    std::lock_guard<std::mutex> g(S().mu);
+    return denoise_locked(params, pixels, rgba, err);
+} catch (const std::exception &e) {
+    return fail_free(err, e.what());
+} catch (...) {
+    return fail_free(err, "unknown exception");
+}
+
 namespace {
 struct MeshOwner {
     hippt::MeshData data;
@@ -3198,6 +3359,10 @@ extern "C" bool hipptSetOption(int key, long long value) try {
         if (value != 0 && value != 1) return false;
         s.knobs.skyRect = value == 1;
         return true;
+    case HIPPT_OPT_DENOISE_TIMING:
+        if (value != 0 && value != 1) return false;
+        s.denoiseTiming = value == 1;
+        return true;
     default: return false;
     }
 } catch (const std::exception &e) {
@@ -3258,6 +3423,7 @@ extern "C" long long hipptGetOption(int key) try {
     case HIPPT_INFO_CHUNK: return s.activeChunk;
     case HIPPT_INFO_CHAIN_CAP: return s.activeChainCap;
     case HIPPT_INFO_RENDER_PAD: return s.activeRenderPad;
+    case HIPPT_OPT_DENOISE_TIMING: return s.denoiseTiming ? 1 : 0;
     case HIPPT_INFO_SKY_RECT_PIXELS: return s.activeSkyPixels;
     case HIPPT_INFO_UPDATE_DROPPED:
         // the last update's count, from the first context that ran it (every context counts the same)
@@ -3272,7 +3438,10 @@ extern "C" long long hipptGetOption(int key) try {
             return w[1];
         }
         return 0;
-    default: return -1;
+    default:
+        if (key >= HIPPT_INFO_DENOISE_NS && key < HIPPT_INFO_DENOISE_NS + hippt::kDenoiseStages)
+            return s.denoiseNs[key - HIPPT_INFO_DENOISE_NS];
+        return -1;
     }
 } catch (const std::exception &e) {
     return -1;

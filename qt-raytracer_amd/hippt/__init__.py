@@ -59,6 +59,7 @@ OPT_PIXEL_TILE = 32
 OPT_QUERY_SLICE = 33
 OPT_RENDER_PAD = 34
 OPT_SKY_RECT = 35
+OPT_DENOISE_TIMING = 36
 OPT_PIXEL_FORMAT = 25
 PIXEL_ARGB = 0
 PIXEL_RGBA8 = 1
@@ -69,10 +70,14 @@ INFO_CHAIN_CAP = 103
 INFO_UPDATE_DROPPED = 104
 INFO_RENDER_PAD = 105
 INFO_SKY_RECT_PIXELS = 106
+INFO_DENOISE_NS = 200
 RAYS_DEVICE = 1
 HIT_SPHERE = 1 << 30
 HIT_BACKFACE = -(1 << 31)  # the int's sign bit
 HIT_MATERIAL_MASK = (1 << 30) - 1
+DENOISE_NO_DEMODULATE = 1
+DENOISE_DEVICE = 2
+DENOISE_STAGES = ("guides", "prepare", "pass0", "pass1", "pass2", "pass3", "pass4", "pass5", "pass6", "pass7", "finish")
 VERTS_DEVICE = 1
 SCENE_NODES2 = 0
 SCENE_NODES4 = 1
@@ -95,6 +100,7 @@ EXPORTS = (
     "hipptActiveBvhWidth", "hipptChainAudit",
     "hipptTraceRays", "hipptOccluded", "hipptTraceCamera", "hipptTraceHits", "hipptTraceCameraHits",
     "hipptUpdateVertices", "hipptSceneDownload", "hipptBvhRefit",
+    "hipptDenoiseDefaults", "hipptDenoise",
 )
 
 
@@ -137,6 +143,13 @@ def split_hits(hits) -> dict:
     import torch
     return {"t": hits[..., 0], "prim": hits[..., 1].view(torch.int32), "normal": hits[..., 2:5],
             "u": hits[..., 5], "v": hits[..., 6], "matFlags": hits[..., 7].view(torch.int32)}
+
+
+class DenoiseParams(ctypes.Structure):
+    """hipptDenoiseParams (include/hippt.h), 32 bytes."""
+    _fields_ = [("passes", ctypes.c_int), ("guideFrame", ctypes.c_int), ("normalPower", ctypes.c_int),
+                ("flags", ctypes.c_int), ("sigmaColor", ctypes.c_float), ("sigmaDepth", ctypes.c_float),
+                ("reserved", ctypes.c_float * 2)]
 
 
 class Stats(ctypes.Structure):
@@ -236,6 +249,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     sig("hipptUpdateVertices", c_bool, c_void_p, c_int, c_int, pp_char)
     sig("hipptSceneDownload", ctypes.c_longlong, c_int, c_void_p, ctypes.c_longlong, pp_char)
     sig("hipptBvhRefit", c_bool, c_void_p, p_float, c_int, c_float, pp_char)
+    sig("hipptDenoiseDefaults", None, ctypes.POINTER(DenoiseParams))
+    sig("hipptDenoise", c_bool, ctypes.POINTER(DenoiseParams), c_void_p, c_void_p, pp_char)
     _lib = lib
     return lib
 
@@ -416,6 +431,7 @@ class PathTracer:
         self._pixels: Optional[ctypes.POINTER] = None
         self._last_error = ""
         self._albedo: Optional[np.ndarray] = None  # (materials, 3) of the scene uploaded last (gbuffer)
+        self._devices: list = []  # of the last setDevices (denoise: where its tensors go)
 
     def __del__(self):  # ~CudaPathTracer -> cudaPathTracerShutdown (CudaPathTracer.cpp:14-18)
         try:
@@ -594,6 +610,7 @@ class PathTracer:
         e = ctypes.c_char_p()
         if not self._lib.hipptSetDevices(arr, len(device_ids), ctypes.byref(e)):
             raise HipptError(_err(e, "bad devices"))
+        self._devices = [int(d) for d in device_ids]
 
     def setRowRange(self, y0: int, y1: int) -> None:  # noqa: N802
         e = ctypes.c_char_p()
@@ -740,6 +757,44 @@ class PathTracer:
         albedo[hit] = self._albedo[material[hit]]
         return {"depth": hits["t"].copy(), "prim": hits["prim"].copy(), "normal": hits["normal"].copy(),
                 "albedo": albedo, "material": material}
+
+    # --- denoiser (include/hippt.h "denoiser") ----------------------------------------------------------
+    def denoise(self, passes: int = 5, sigma_color: float = 1.0, sigma_depth: float = 0.05, normal_power: int = 6,
+                guide_frame: int = 0, demodulate: bool = True, tensors: bool = False):
+        """hipptDenoise: the accumulation filtered on the device by the edge-avoiding A-trous wavelet of
+        include/hippt.h, guided by sample `guide_frame`'s hit records: (pixels (H, W) uint32 in the current
+        pixel format, rgba (H, W, 4) float32, linear, alpha 1), row 0 = v = 0.  The accumulation, the image
+        and the counters stay as they are.  tensors=True: both are torch tensors on the context's device,
+        written there (see traceRays on sharing one HIP runtime with torch)."""
+        p = DenoiseParams()
+        self._lib.hipptDenoiseDefaults(ctypes.byref(p))
+        p.passes, p.guideFrame, p.normalPower = int(passes), int(guide_frame), int(normal_power)
+        p.sigmaColor, p.sigmaDepth = float(sigma_color), float(sigma_depth)
+        p.flags = 0 if demodulate else DENOISE_NO_DEMODULATE
+        h, w = self._height, self._width
+        e = ctypes.c_char_p()
+        if tensors:
+            import torch
+            dev = torch.device("cuda", self._devices[0] if self._devices else torch.cuda.current_device())
+            pixels = torch.empty((h, w), dtype=torch.int32, device=dev)
+            rgba = torch.empty((h, w, 4), dtype=torch.float32, device=dev)
+            torch.cuda.current_stream(dev).synchronize()
+            p.flags |= DENOISE_DEVICE
+            ok = self._lib.hipptDenoise(ctypes.byref(p), pixels.data_ptr(), rgba.data_ptr(), ctypes.byref(e))
+            pixels = pixels.view(torch.uint32) if hasattr(torch, "uint32") else pixels
+        else:
+            pixels = np.empty((h, w), np.uint32)
+            rgba = np.empty((h, w, 4), np.float32)
+            ok = self._lib.hipptDenoise(ctypes.byref(p), pixels.ctypes.data, rgba.ctypes.data, ctypes.byref(e))
+        if not ok:
+            raise HipptError(_err(e, "denoise failed"))
+        return pixels, rgba
+
+    def denoiseTimes(self) -> dict:  # noqa: N802
+        """Device milliseconds per stage of the last denoise() made under OPT_DENOISE_TIMING (stages that
+        did not run are left out)."""
+        ns = {name: int(self._lib.hipptGetOption(INFO_DENOISE_NS + k)) for k, name in enumerate(DENOISE_STAGES)}
+        return {name: v / 1e6 for name, v in ns.items() if v > 0}
 
     def pickHit(self, x: int, y: int, frame: int = 0) -> dict:  # noqa: N802
         """The hit record under pixel (x, y) (row y = 0 is v = 0) for sample `frame`'s camera ray, as a

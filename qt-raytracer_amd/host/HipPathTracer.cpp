@@ -128,6 +128,13 @@ bool HipPathTracer::traceHits(const std::vector<float> &rays, std::vector<hipptH
     return true;
 }
 
+bool HipPathTracer::denoise(const hipptDenoiseParams *params, std::vector<unsigned> &pixels) {
+    pixels.resize(size_t(m_width > 0 ? m_width : 0) * size_t(m_height > 0 ? m_height : 0));
+    const char *err = nullptr;
+    if (!hipptDenoise(params, pixels.data(), nullptr, &err)) return fail(err, "denoise failed");
+    return true;
+}
+
 bool HipPathTracer::pick(int x, int y, int *prim, float *t, int frame) {
     if (x < 0 || y < 0 || x >= m_width || y >= m_height || !prim) {
         m_lastError = "pick outside the image";

@@ -58,6 +58,11 @@ public:
     // as hostPixels() does (row 0 = v = 0, the bottom row: a viewport click at yTop is height - 1 - yTop).
     // *prim = -1 and *t = +inf over the sky.
     bool pick(int x, int y, int *prim, float *t = nullptr, int frame = 0);
+    // The accumulated image denoised on the device (hipptDenoise: an edge-avoiding A-trous wavelet guided
+    // by the first hits' normals, depths and albedos): width * height frame words as hostPixels() has
+    // them.  params null: the defaults (hipptDenoiseDefaults).  Needs an uploaded scene; the
+    // accumulation and hostPixels() stay as they are.
+    bool denoise(const hipptDenoiseParams *params, std::vector<unsigned> &pixels);
 
 private:
     bool fail(const char *err, const char *fallback);

@@ -4,7 +4,7 @@
 //
 //   hippt_render [--backend cuda|vulkan|gl] [--mesh FILE.obj|.ply] [--albedo r,g,b[;r,g,b...]]
 //                [--width W] [--height H] [--spp N] [--depth D] [--per-frame] [--present]
-//                [--out FILE] [--ppm FILE.ppm] [--pick X,Y]
+//                [--out FILE] [--ppm FILE.ppm] [--pick X,Y] [--denoise PASSES]
 //
 // --backend cuda (default): HipPathTracer, the CudaPathTracer interface.  Without --mesh: the
 // reference kernel's built-in 4-sphere scene, one renderFrame per frame (the CUDA backend's
@@ -18,7 +18,9 @@
 // --ppm an image (top row first).  --pick X,Y (cuda backend, with --mesh): after the render,
 // HipPathTracer::pick at that pixel (row 0 = bottom) and the pixel centre's pinhole ray through
 // HipPathTracer::traceRays and HipPathTracer::traceHits, reported as "pick": {x, y, prim, t_bits,
-// ray_prim, ray_t_bits, ray_hit_words (the hipptHit's 8 words)}.
+// ray_prim, ray_t_bits, ray_hit_words (the hipptHit's 8 words)}.  --denoise PASSES (cuda backend, with
+// --mesh): --out and --ppm get HipPathTracer::denoise's image (that many passes, the other parameters
+// at their defaults) in place of the rendered one.
 // Prints one JSON line.
 #include <chrono>
 #include <cstdio>
@@ -38,7 +40,7 @@ int usage() {
     std::fprintf(stderr,
                  "usage: hippt_render [--backend cuda|vulkan|gl] [--mesh FILE] [--albedo r,g,b[;...]] [--width W]\n"
                  "                    [--height H] [--spp N] [--depth D] [--per-frame] [--present] [--out FILE]\n"
-                 "                    [--ppm FILE.ppm] [--pick X,Y] [--update-mesh FILE]\n");
+                 "                    [--ppm FILE.ppm] [--pick X,Y] [--update-mesh FILE] [--denoise PASSES]\n");
     return 2;
 }
 
@@ -60,7 +62,7 @@ std::vector<float> parse_floats(const std::string &s) {
 
 int main(int argc, char **argv) {
     std::string mesh, out, ppm, albedoArg, pickArg, updateMesh, backend = "cuda";
-    int width = 320, height = 180, spp = 16, depth = 8;
+    int width = 320, height = 180, spp = 16, depth = 8, denoise = -1;
     bool perFrame = false, present = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -80,6 +82,7 @@ int main(int argc, char **argv) {
         else if (a == "--ppm") ppm = v;
         else if (a == "--pick") pickArg = v;
         else if (a == "--update-mesh") updateMesh = v;
+        else if (a == "--denoise") denoise = std::atoi(v);
         else return usage();
     }
     if (backend != "cuda" && backend != "vulkan" && backend != "gl") return usage();
@@ -193,6 +196,17 @@ int main(int argc, char **argv) {
     if (!ok || !pixels) {
         std::fprintf(stderr, "hippt_render: %s\n", tracer.lastError().c_str());
         return 1;
+    }
+    std::vector<unsigned> clean;
+    if (denoise >= 0) {
+        hipptDenoiseParams dp;
+        hipptDenoiseDefaults(&dp);
+        dp.passes = denoise;
+        if (!tracer.denoise(&dp, clean)) {
+            std::fprintf(stderr, "hippt_render: denoise: %s\n", tracer.lastError().c_str());
+            return 1;
+        }
+        pixels = clean.data();
     }
     if (!out.empty()) {
         FILE *f = std::fopen(out.c_str(), "wb");
