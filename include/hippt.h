@@ -228,6 +228,37 @@ bool hipptTraceHits(const float *rays, long long numRays, int flags, hipptHit *h
 /* hipptTraceCamera with a record per pixel: width*height records, row 0 = v = 0. */
 bool hipptTraceCameraHits(int frame, int flags, hipptHit *hits, const char **errorMessage);
 
+/* ---- path queries -------------------------------------------------------------------------- */
+/* Radiance along caller-supplied rays: the renderer's path started from ray i with
+ * RNG state seeds[i] instead of from a camera sample: what a fisheye or orthographic camera, a light
+ * probe or a lightmap texel sees, with the renderer's own bounce loop, materials, RNG chain and sky.
+ * rays: as hipptTraceRays (layout, validity, tmin / tmax).  Segment 0 is the closest hit of ray i with
+ * the ray's own tmin and exclusive tmax; every later segment uses tmin 0.001 and no tmax, as the
+ * renderer does.  On a miss L = throughput x sky of the segment's direction; a hit on the segment with
+ * depth + 1 >= maxDepth gives L = 0; otherwise the path scatters as the renderer's materials do, and an
+ * absorbed path gives L = 0.
+ * radiance[4i..4i+3] = (L.r, L.g, L.b, a), a = 1.0f if segment 0 hit something, else 0.0f;
+ * segments[i] (segments may be null) = the closest-hit queries the path made.  An invalid ray (as
+ * hipptTraceRays: non-finite origin, direction or tmin, NaN tmax, zero direction, tmin < 0,
+ * tmax <= tmin) gives (0, 0, 0, 0) and 0 segments.
+ * Every word is the renderer's arithmetic and the BVH only culls: no bit depends on the tree, its
+ * width, where it lives, the slice size or the device split.
+ * maxDepth < 1, a null rays, seeds or radiance with numRays > 0, a negative count, unknown flags, the
+ * built-in scene or no Init return false with a message before any device call; numRays == 0 succeeds.
+ * flags: HIPPT_RAYS_DEVICE as the ray queries (every pointer memory of one context's device; rays and
+ * radiance 16-byte aligned, seeds and segments 4-byte aligned); host memory is shared over the devices
+ * and staged in slices (HIPPT_OPT_QUERY_SLICE).  Blocking: runs behind the queued work, waits for its
+ * own event only, and leaves pending frames, the image, hipptGetStats and the chain audit as if it had
+ * not been made.  One sample per ray and call: repeat rays with different seeds and average. */
+bool hipptTraceRadiance(const float *rays, const unsigned int *seeds, long long numRays, int maxDepth,
+                        int flags, float *radiance, int *segments, const char **errorMessage);
+/* The rays hipptRenderFrames starts sample `frame` of every pixel of the current Init with, and the RNG
+ * state each is left with after the camera sample (jitter and lens draw): width*height rays (origin,
+ * 0.001, direction, +inf) and seeds, row 0 = v = 0; either output may be null, not both.  Arguments,
+ * state checks and flags as hipptTraceCamera.  hipptTraceRadiance of these rays and seeds is exactly
+ * sample `frame` of hipptRenderFrames; callers can also bend the rays before tracing them. */
+bool hipptCameraRays(int frame, int flags, float *rays, unsigned int *seeds, const char **errorMessage);
+
 /* ---- denoiser ---------------------------------------------------------------------------- */
 /* An edge-avoiding A-trous wavelet filter (Dammertz et al. 2010) over the accumulation buffer, on the
  * device, guided by the hit records of one camera sample (what hipptTraceCameraHits returns) and the

@@ -36,6 +36,7 @@
 #include "mesh_io.h"
 #include "hippt_denoise.h"
 #include "hippt_device.h"
+#include "hippt_path.h"
 #include "hippt_plan.h"
 #include "hippt_query.h"
 #include "hippt_refit.h"
@@ -99,7 +100,7 @@ struct OccKey {
     int version = -1, stackDepth = 0, fmt = 0, poolWords = 0;
     unsigned topBytes = 0;
     bool ldsScene = false, full = false, spills = false;
-    int variant = 0;  // queries: any | camera << 1 | records << 2
+    int variant = 0;  // queries: any | camera << 1 | records << 2 | path << 3
 };
 
 bool same_key(const OccKey &a, const OccKey &b) {
@@ -2038,7 +2039,8 @@ bool render_locked(int frameIndex, int count, int maxDepth, const unsigned int *
 }
 
 // ---- ray queries (hippt_query.hip; include/hippt.h hipptTraceRays, hipptOccluded, hipptTraceCamera,
-// hipptTraceHits, hipptTraceCameraHits) ----
+// hipptTraceHits, hipptTraceCameraHits) and path queries (hippt_path.hip; hipptTraceRadiance,
+// hipptCameraRays) ----
 // A query is one or more launches of the query kernel on a context's stream, after whatever the stream
 // already holds, followed by a wait for the query's own event.  It reads the scene buffers only: it
 // does not flush the deferred combine or the chain, launches no held batch, and leaves the stats and
@@ -2053,6 +2055,25 @@ struct QueryCall {
     hipptHit *hits = nullptr;  // hit records (hipptTraceHits, hipptTraceCameraHits): these, not t / prim
     bool any = false, camera = false, records = false;
     int frame = 0;
+    // path queries (hipptTraceRadiance): the renderer's path per ray, these in place of t / prim
+    bool path = false;
+    const unsigned *seeds = nullptr;
+    float *radiance = nullptr;  // numRays x 4 floats
+    int *segments = nullptr;    // may be null
+    int maxDepth = 0;
+    // the camera's rays (hipptCameraRays; with `camera`): no traversal, these outputs alone
+    bool camRays = false;
+    float *outRays = nullptr;  // width * height x 8 floats
+    unsigned *outSeeds = nullptr;
+};
+
+// The device pointers of one launch of a path query or of the camera's rays (those QueryParams lacks).
+struct PathPtrs {
+    const unsigned *seeds = nullptr;
+    float4 *radiance = nullptr;
+    int *segments = nullptr;
+    float4 *outRays = nullptr;
+    unsigned *outSeeds = nullptr;
 };
 
 // The traversal's layout and parameters for the current scene on context c: the render's plan under
@@ -2093,16 +2114,18 @@ bool query_setup(Ctx &c, const QueryCall &call, hippt::QueryParams &q, const cha
         k.rcpWidth = 1.0f / float(s.width);
     }
     HIP_TRY(hipSetDevice(c.device));
+    if (!c.qDone) HIP_TRY(hipEventCreateWithFlags(&c.qDone, hipEventDisableTiming));
+    if (call.camRays) return true;  // no traversal: the camera alone
     OccKey occKey;
     occKey.version = s.scene.version, occKey.stackDepth = L.stackDepth, occKey.fmt = L.fmt, occKey.topBytes = L.topBytes;
     occKey.ldsScene = L.ldsScene, occKey.full = f.full;
-    occKey.variant = (call.any ? 1 : 0) | (call.camera ? 2 : 0) | (call.records ? 4 : 0);
+    occKey.variant = (call.any ? 1 : 0) | (call.camera ? 2 : 0) | (call.records ? 4 : 0) | (call.path ? 8 : 0);
     if (!same_key(c.qOccKey, occKey)) {
-        c.qBlocksPerCu = hippt::query_blocks_per_cu(q, call.any, call.camera, call.records);
+        c.qBlocksPerCu = call.path ? hippt::path_blocks_per_cu(hippt::PathParams{q, c.mats, nullptr, nullptr, nullptr, 1})
+                                   : hippt::query_blocks_per_cu(q, call.any, call.camera, call.records);
         c.qOccKey = occKey;
     }
     if (!c.qCtr) HIP_TRY(hipMalloc(&c.qCtr, hippt::kQueryCtrBytes));
-    if (!c.qDone) HIP_TRY(hipEventCreateWithFlags(&c.qDone, hipEventDisableTiming));
     if (L.wide) {
         const size_t bytes = size_t(c.cus) * size_t(c.qBlocksPerCu) * hippt::kMeshBlock * size_t(q.spillCap) * sizeof(int);
         if (c.qSpillBytes < bytes) {  // (no query is in flight: every call waits for its own)
@@ -2120,57 +2143,76 @@ bool query_setup(Ctx &c, const QueryCall &call, hippt::QueryParams &q, const cha
 
 // Enqueues rays [first, first + m) of a query whose pointers (q.rays, q.t, ...) are already those of
 // ray `first`.
-bool query_enqueue(Ctx &c, hippt::QueryParams q, unsigned first, unsigned m, const QueryCall &call, const char **err) {
+bool query_enqueue(Ctx &c, hippt::QueryParams q, unsigned first, unsigned m, const QueryCall &call, const char **err,
+                   const PathPtrs &pp = PathPtrs{}) {
+    if (call.camRays) {
+        HIP_TRY(hippt::launch_camera_rays(hippt::CameraRaysParams{q.cam, pp.outRays, pp.outSeeds, m, first}, c.stream));
+        return true;
+    }
     q.numRays = m;
     q.firstItem = first;
     q.chunk = plan::query_chunk(m);
     const long long blocks =
         std::max(1LL, std::min<long long>((long long)c.cus * c.qBlocksPerCu, (m + hippt::kMeshBlock - 1) / hippt::kMeshBlock));
     HIP_TRY(hipMemsetAsync(c.qCtr, 0, hippt::kQueryCtrBytes, c.stream));
-    HIP_TRY(hippt::launch_query(q, int(blocks), call.any, call.camera, call.records, c.stream));
+    if (call.path)
+        HIP_TRY(hippt::launch_path(hippt::PathParams{q, c.mats, pp.seeds, pp.radiance, pp.segments, call.maxDepth}, int(blocks),
+                                   c.stream));
+    else
+        HIP_TRY(hippt::launch_query(q, int(blocks), call.any, call.camera, call.records, c.stream));
     return true;
 }
 
 bool query_locked(const QueryCall &call, const char **err) {
     State &s = S();
     // argument and state checks first: none of them touches the GPU
-    if (call.n < 0) return fail(err, "ray query: negative ray count");
-    if (!call.camera && !call.rays && call.n > 0) return fail(err, "ray query: null ray buffer");
-    if (call.records ? !call.hits : call.any ? !call.occ : (!call.t && !call.prim))
-        return fail(err, "ray query: no output buffer");
-    if (call.camera && call.frame < 0) return fail(err, "ray query: negative frame");
+    const bool pathApi = call.path || call.camRays;  // (their messages name them)
+    const std::string who = pathApi ? "path query" : "ray query";
+    if (call.path && call.maxDepth < 1) return fail(err, who + ": maxDepth must be at least 1");
+    if (call.n < 0) return fail(err, who + ": negative ray count");
+    if (!call.camera && !call.rays && call.n > 0) return fail(err, who + ": null ray buffer");
+    if (call.path && !call.seeds && call.n > 0) return fail(err, who + ": null seed buffer");
+    if (call.path ? (!call.radiance && call.n > 0)
+        : call.camRays ? (!call.outRays && !call.outSeeds)
+        : call.records ? !call.hits
+        : call.any     ? !call.occ
+                       : (!call.t && !call.prim))
+        return fail(err, who + ": no output buffer");
+    if (call.camera && call.frame < 0) return fail(err, who + ": negative frame");
+    if (pathApi && (call.flags & ~HIPPT_RAYS_DEVICE)) return fail(err, who + ": unknown flags");
     if (s.scene.kind != HIPPT_SCENE_MESH)
-        return fail(err, "ray query: needs a scene from hipptUploadMesh or hipptUploadScene (the built-in scene has none)");
-    if (!s.ready || s.ctxs.empty()) return fail(err, "ray query: HIP path tracer not initialized");
+        return fail(err, who + ": needs a scene from hipptUploadMesh or hipptUploadScene (the built-in scene has none)");
+    if (!s.ready || s.ctxs.empty()) return fail(err, who + ": HIP path tracer not initialized");
     long long n = call.n;
     if (call.camera) {
         n = (long long)s.width * (long long)s.height;
-        if (n > (1LL << 31) - 1) return fail(err, "ray query: image too large");
+        if (n > (1LL << 31) - 1) return fail(err, who + ": image too large");
     }
     if (n == 0) return true;
     const bool device = (call.flags & HIPPT_RAYS_DEVICE) != 0;
-    if (call.flags & ~HIPPT_RAYS_DEVICE) return fail(err, "ray query: unknown flags");
+    if (call.flags & ~HIPPT_RAYS_DEVICE) return fail(err, who + ": unknown flags");
     constexpr long long kLaunchRays = 1LL << 30;
     if (device) {
         // every pointer on the device of one context: the whole batch runs there, unstaged
         int dev = -1;
-        const void *ptrs[5] = {call.rays, call.t, call.prim, call.occ, call.hits};
-        const size_t align[5] = {16, 4, 4, 1, 32};
-        for (int k = 0; k < 5; ++k) {
+        const void *ptrs[10] = {call.rays, call.t,        call.prim,     call.occ,     call.hits,
+                                call.seeds, call.radiance, call.segments, call.outRays, call.outSeeds};
+        const size_t align[10] = {16, 4, 4, 1, 32, 4, 16, 4, 16, 4};
+        for (int k = 0; k < 10; ++k) {
             if (!ptrs[k]) continue;
             hipPointerAttribute_t a{};
             if (hipPointerGetAttributes(&a, ptrs[k]) != hipSuccess || a.type != hipMemoryTypeDevice) {
                 (void)hipGetLastError();
-                return fail(err, "ray query: HIPPT_RAYS_DEVICE needs device memory pointers");
+                return fail(err, who + ": HIPPT_RAYS_DEVICE needs device memory pointers");
             }
-            if (dev >= 0 && a.device != dev) return fail(err, "ray query: pointers on different devices");
+            if (dev >= 0 && a.device != dev) return fail(err, who + ": pointers on different devices");
             dev = a.device;
-            if (reinterpret_cast<uintptr_t>(ptrs[k]) % align[k]) return fail(err, "ray query: misaligned device pointer");
+            if (reinterpret_cast<uintptr_t>(ptrs[k]) % align[k]) return fail(err, who + ": misaligned device pointer");
         }
         Ctx *cp = nullptr;
         for (Ctx &c : s.ctxs)
             if (c.device == dev && !cp) cp = &c;
-        if (!cp) return fail(err, "ray query: the pointers are on a device that is none of hipptSetDevices'");
+        if (!cp) return fail(err, who + ": the pointers are on a device that is none of hipptSetDevices'");
         Ctx &c = *cp;
         HIP_TRY(hipSetDevice(c.device));
         if (!ensure_scene(c, err)) return false;
@@ -2183,7 +2225,13 @@ bool query_locked(const QueryCall &call, const char **err) {
             q.prim = call.prim ? call.prim + at : nullptr;
             q.occluded = call.occ ? call.occ + at : nullptr;
             q.hits = call.hits ? reinterpret_cast<float4 *>(call.hits + at) : nullptr;
-            if (!query_enqueue(c, q, unsigned(at), m, call, err)) return false;
+            PathPtrs pp;
+            pp.seeds = call.seeds ? call.seeds + at : nullptr;
+            pp.radiance = call.radiance ? reinterpret_cast<float4 *>(call.radiance + 4 * at) : nullptr;
+            pp.segments = call.segments ? call.segments + at : nullptr;
+            pp.outRays = call.outRays ? reinterpret_cast<float4 *>(call.outRays + 8 * at) : nullptr;
+            pp.outSeeds = call.outSeeds ? call.outSeeds + at : nullptr;
+            if (!query_enqueue(c, q, unsigned(at), m, call, err, pp)) return false;
         }
         HIP_TRY(hipEventRecord(c.qDone, c.stream));
         HIP_TRY(hipEventSynchronize(c.qDone));
@@ -2196,9 +2244,13 @@ bool query_locked(const QueryCall &call, const char **err) {
     std::vector<hippt::QueryParams> qs(K);
     std::vector<char *> stage(K, nullptr);
     const size_t cap = size_t(std::min(slice, n));
-    // (rays, then the results: hit records, or t, prim and the occlusion bytes)
+    // (rays, then the results: hit records, or t, prim and the occlusion bytes; a path query: rays,
+    // seeds, then radiance and segments; the camera's rays: rays and seeds, both results)
     const size_t offT = cap * 32, offP = offT + cap * 4, offO = offP + cap * 4, offH = offT;
-    const size_t stageBytes = call.records ? offH + cap * sizeof(hipptHit) : offO + ((cap + 15) & ~size_t(15));
+    const size_t offS = cap * 32, offR = offS + ((cap * 4 + 15) & ~size_t(15)), offG = offR + cap * 16;
+    const size_t stageBytes = pathApi        ? offG + cap * 4
+                              : call.records ? offH + cap * sizeof(hipptHit)
+                                             : offO + ((cap + 15) & ~size_t(15));
     for (size_t k = 0; k < K; ++k) {
         Ctx &c = s.ctxs[k];
         if (n * (long long)(k + 1) / (long long)K == n * (long long)k / (long long)K) continue;  // an empty share
@@ -2235,7 +2287,27 @@ bool query_locked(const QueryCall &call, const char **err) {
             q.prim = call.prim ? reinterpret_cast<int *>(st + offP) : nullptr;
             q.occluded = call.occ ? reinterpret_cast<unsigned char *>(st + offO) : nullptr;
             q.hits = call.hits ? reinterpret_cast<float4 *>(st + offH) : nullptr;
-            if (!query_enqueue(c, q, unsigned(at), m, call, err)) return false;
+            PathPtrs pp;
+            if (call.path) {
+                HIP_TRY(hipMemcpyAsync(st + offS, call.seeds + at, size_t(m) * 4, hipMemcpyHostToDevice, c.stream));
+                pp.seeds = reinterpret_cast<const unsigned *>(st + offS);
+                pp.radiance = reinterpret_cast<float4 *>(st + offR);
+                pp.segments = call.segments ? reinterpret_cast<int *>(st + offG) : nullptr;
+            }
+            if (call.camRays) {
+                pp.outRays = call.outRays ? reinterpret_cast<float4 *>(st) : nullptr;
+                pp.outSeeds = call.outSeeds ? reinterpret_cast<unsigned *>(st + offS) : nullptr;
+            }
+            if (!query_enqueue(c, q, unsigned(at), m, call, err, pp)) return false;
+            if (call.path) {
+                HIP_TRY(hipMemcpyAsync(call.radiance + 4 * at, pp.radiance, size_t(m) * 16, hipMemcpyDeviceToHost, c.stream));
+                if (call.segments)
+                    HIP_TRY(hipMemcpyAsync(call.segments + at, pp.segments, size_t(m) * 4, hipMemcpyDeviceToHost, c.stream));
+            }
+            if (call.outRays)
+                HIP_TRY(hipMemcpyAsync(call.outRays + 8 * at, pp.outRays, size_t(m) * 32, hipMemcpyDeviceToHost, c.stream));
+            if (call.outSeeds)
+                HIP_TRY(hipMemcpyAsync(call.outSeeds + at, pp.outSeeds, size_t(m) * 4, hipMemcpyDeviceToHost, c.stream));
             if (call.hits)
                 HIP_TRY(hipMemcpyAsync(call.hits + at, q.hits, size_t(m) * sizeof(hipptHit), hipMemcpyDeviceToHost, c.stream));
             if (call.t) HIP_TRY(hipMemcpyAsync(call.t + at, q.t, size_t(m) * 4, hipMemcpyDeviceToHost, c.stream));
@@ -2890,6 +2962,42 @@ extern "C" bool hipptTraceCameraHits(int frame, int flags, hipptHit *hits, const
     q.flags = flags;
     q.hits = hits;
     q.records = true;
+    return query_locked(q, err);
+} catch (const std::exception &e) {
+    return fail_free(err, e.what());
+} catch (...) {
+    return fail_free(err, "unknown exception");
+}
+
+// ---- path queries --------------------------------------------------------------------------------
+extern "C" bool hipptTraceRadiance(const float *rays, const unsigned int *seeds, long long numRays, int maxDepth, int flags,
+                                   float *radiance, int *segments, const char **err) try {
+    std::lock_guard<std::mutex> g(S().mu);
+    QueryCall q;
+    q.path = true;
+    q.rays = rays;
+    q.seeds = seeds;
+    q.n = numRays;
+    q.maxDepth = maxDepth;
+    q.flags = flags;
+    q.radiance = radiance;
+    q.segments = segments;
+    return query_locked(q, err);
+} catch (const std::exception &e) {
+    return fail_free(err, e.what());
+} catch (...) {
+    return fail_free(err, "unknown exception");
+}
+
+extern "C" bool hipptCameraRays(int frame, int flags, float *rays, unsigned int *seeds, const char **err) try {
+    std::lock_guard<std::mutex> g(S().mu);
+    QueryCall q;
+    q.camera = true;
+    q.camRays = true;
+    q.frame = frame;
+    q.flags = flags;
+    q.outRays = rays;
+    q.outSeeds = seeds;
     return query_locked(q, err);
 } catch (const std::exception &e) {
     return fail_free(err, e.what());

@@ -1,0 +1,38 @@
+// hippt_path.h — launch interface of the path queries (hippt_path.hip): radiance along caller-supplied
+// rays and the camera's own rays (include/hippt.h hipptTraceRadiance, hipptCameraRays).
+#pragma once
+
+#include "hippt_query.h"
+
+namespace hippt {
+
+// One launch runs the renderer's path from ray i of q.rays with RNG state seeds[i], i in [0, q.numRays),
+// and writes radiance[i] = (L.r, L.g, L.b, a) and segments[i] (may be null).  `q` is a ray query's
+// launch (hippt_query.h: scene, rays, claim counters, spill area, layout, shade records) whose result
+// pointers (t, prim, occluded, hits) and camera are not used.  Every pointer is device memory of the
+// launch's device.
+struct PathParams {
+    QueryParams q;
+    const float4 *mats;     // MeshParams::mats
+    const unsigned *seeds;  // RNG state per ray
+    float4 *radiance;
+    int *segments;
+    int maxDepth;
+};
+
+hipError_t launch_path(const PathParams &p, int blocks, hipStream_t s);
+int path_blocks_per_cu(const PathParams &p);
+
+// Writes camera_sample's ray of pixels firstItem .. firstItem + numRays - 1 of the image (cam: one frame,
+// the whole image as one band) as (origin, 0.001) (direction, +inf) to rays[2 i], rays[2 i + 1] and the
+// RNG state it leaves to seeds[i]; either output may be null.
+struct CameraRaysParams {
+    QueryCam cam;
+    float4 *rays;
+    unsigned *seeds;
+    unsigned numRays, firstItem;
+};
+
+hipError_t launch_camera_rays(const CameraRaysParams &p, hipStream_t s);
+
+}  // namespace hippt

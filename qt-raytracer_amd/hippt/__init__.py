@@ -101,6 +101,7 @@ EXPORTS = (
     "hipptTraceRays", "hipptOccluded", "hipptTraceCamera", "hipptTraceHits", "hipptTraceCameraHits",
     "hipptUpdateVertices", "hipptSceneDownload", "hipptBvhRefit",
     "hipptDenoiseDefaults", "hipptDenoise",
+    "hipptTraceRadiance", "hipptCameraRays",
 )
 
 
@@ -246,6 +247,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     sig("hipptTraceCamera", c_bool, c_int, c_int, c_void_p, c_void_p, pp_char)
     sig("hipptTraceHits", c_bool, c_void_p, ctypes.c_longlong, c_int, c_void_p, pp_char)
     sig("hipptTraceCameraHits", c_bool, c_int, c_int, c_void_p, pp_char)
+    sig("hipptTraceRadiance", c_bool, c_void_p, c_void_p, ctypes.c_longlong, c_int, c_int, c_void_p, c_void_p, pp_char)
+    sig("hipptCameraRays", c_bool, c_int, c_int, c_void_p, c_void_p, pp_char)
     sig("hipptUpdateVertices", c_bool, c_void_p, c_int, c_int, pp_char)
     sig("hipptSceneDownload", ctypes.c_longlong, c_int, c_void_p, ctypes.c_longlong, pp_char)
     sig("hipptBvhRefit", c_bool, c_void_p, p_float, c_int, c_float, pp_char)
@@ -297,6 +300,46 @@ def _query_rays(rays):
     if not rays.flags["C_CONTIGUOUS"]:
         raise HipptError("rays must be contiguous")
     return rays, False
+
+
+def path_seeds(n: int, frame: int = 0, like=None):
+    """The renderer's pixel_seed of items 0..n-1 for sample `frame`: i * 9781 + (frame + 1) * 6271 mod
+    2^32, the RNG state traceRadiance starts path i with by default.  numpy uint32 (n,); with a tensor
+    `like` on the ROCm device, an int32 tensor of the same bits on that device."""
+    seeds = (np.arange(int(n), dtype=np.uint64) * 9781 + (int(frame) + 1) * 6271).astype(np.uint32)
+    if like is not None and _is_tensor(like) and like.device.type != "cpu":
+        import torch
+        return torch.from_numpy(seeds.view(np.int32)).to(like.device)
+    return seeds
+
+
+def _path_seeds_arg(seeds, n: int, rays, dev: bool):
+    """Validates the seeds of a path query against its rays: (N,) int32 or uint32 state bits, where the
+    rays are.  Returns the array or tensor to pass."""
+    if seeds is None:
+        return path_seeds(n, 0, rays if dev else None)
+    if _is_tensor(seeds):
+        import torch
+        ok = (torch.int32,) + ((torch.uint32,) if hasattr(torch, "uint32") else ())
+        if seeds.dtype not in ok:
+            raise HipptError(f"seeds must be int32 or uint32, not {seeds.dtype}")
+        if seeds.dim() != 1 or seeds.shape[0] != n or not seeds.is_contiguous():
+            raise HipptError(f"seeds must be contiguous with shape ({n},), not {tuple(seeds.shape)}")
+        if seeds.device.type == "cpu":
+            seeds = seeds.numpy()
+        elif not dev or seeds.device != rays.device:
+            raise HipptError("seeds must be where the rays are")
+        else:
+            return seeds
+    if not isinstance(seeds, np.ndarray):
+        raise HipptError("seeds must be a numpy array or a torch tensor")
+    if dev:
+        raise HipptError("seeds must be where the rays are")
+    if seeds.dtype not in (np.int32, np.uint32):
+        raise HipptError(f"seeds must be int32 or uint32, not {seeds.dtype}")
+    if seeds.shape != (n,) or not seeds.flags["C_CONTIGUOUS"]:
+        raise HipptError(f"seeds must be contiguous with shape ({n},), not {seeds.shape}")
+    return seeds
 
 
 def _update_verts(verts):
@@ -743,6 +786,55 @@ class PathTracer:
         if not self._lib.hipptTraceCameraHits(int(frame), 0, hits.ctypes.data, ctypes.byref(e)):
             raise HipptError(_err(e, "camera hit query failed"))
         return hits
+
+    # --- path queries (include/hippt.h "path queries") ---------------------------------------------------
+    def traceRadiance(self, rays, seeds=None, max_depth: int = 8):  # noqa: N802
+        """The renderer's path from each ray (as traceRays: origin xyz, tmin, direction xyz, tmax; tmin and
+        tmax hold for the first segment only) with RNG state seeds[i] (int32 or uint32 bits, where the rays
+        are; None: path_seeds(N, 0)): (radiance float32 (N, 4): rgb and 1.0 where the first segment hit,
+        segments int32 (N,): closest-hit queries made).  numpy in, numpy out; tensors on the ROCm device in,
+        tensors on that device out (see traceRays on sharing one HIP runtime with torch)."""
+        r, dev = _query_rays(rays)
+        n = int(r.shape[0])
+        sd = _path_seeds_arg(seeds, n, r, dev)
+        e = ctypes.c_char_p()
+        if dev:
+            import torch
+            rad = torch.empty((n, 4), dtype=torch.float32, device=r.device)
+            segs = torch.empty(n, dtype=torch.int32, device=r.device)
+            torch.cuda.current_stream(r.device).synchronize()
+            ok = self._lib.hipptTraceRadiance(r.data_ptr(), sd.data_ptr(), n, int(max_depth), RAYS_DEVICE, rad.data_ptr(),
+                                              segs.data_ptr(), ctypes.byref(e))
+        else:
+            rad = np.empty((n, 4), np.float32)
+            segs = np.empty(n, np.int32)
+            ok = self._lib.hipptTraceRadiance(r.ctypes.data, sd.ctypes.data, n, int(max_depth), 0, rad.ctypes.data,
+                                              segs.ctypes.data, ctypes.byref(e))
+        if not ok:
+            raise HipptError(_err(e, "path query failed"))
+        return rad, segs
+
+    def cameraRays(self, frame: int = 0, device: bool = False):  # noqa: N802
+        """The rays renderFrames starts sample `frame` of every pixel with and the RNG state each is left
+        with after the camera sample: (rays float32 (H*W, 8), seeds (H*W,)), row 0 = v = 0, so that
+        traceRadiance(*cameraRays(f)) is sample f of the renderer.  numpy (seeds uint32), or with
+        device=True tensors on the context's device (seeds int32, the same bits)."""
+        n = self._height * self._width
+        e = ctypes.c_char_p()
+        if device:
+            import torch
+            dev = torch.device("cuda", self._devices[0] if self._devices else torch.cuda.current_device())
+            rays = torch.empty((n, 8), dtype=torch.float32, device=dev)
+            seeds = torch.empty(n, dtype=torch.int32, device=dev)
+            torch.cuda.current_stream(dev).synchronize()
+            ok = self._lib.hipptCameraRays(int(frame), RAYS_DEVICE, rays.data_ptr(), seeds.data_ptr(), ctypes.byref(e))
+        else:
+            rays = np.empty((n, 8), np.float32)
+            seeds = np.empty(n, np.uint32)
+            ok = self._lib.hipptCameraRays(int(frame), 0, rays.ctypes.data, seeds.ctypes.data, ctypes.byref(e))
+        if not ok:
+            raise HipptError(_err(e, "camera rays failed"))
+        return rays, seeds
 
     def gbuffer(self, frame: int = 0) -> dict:
         """The guide buffers of sample `frame`'s camera rays, each (H, W) with row 0 = v = 0: depth (t;

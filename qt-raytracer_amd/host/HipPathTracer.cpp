@@ -128,6 +128,30 @@ bool HipPathTracer::traceHits(const std::vector<float> &rays, std::vector<hipptH
     return true;
 }
 
+bool HipPathTracer::traceRadiance(const std::vector<float> &rays, const std::vector<unsigned> &seeds, int maxDepth,
+                                  std::vector<float> &radiance, std::vector<int> &segments) {
+    if (rays.size() % 8 != 0 || seeds.size() != rays.size() / 8) {
+        m_lastError = "rays need 8 floats and one seed each";
+        return false;
+    }
+    const long long n = (long long)(rays.size() / 8);
+    radiance.resize(size_t(n) * 4);
+    segments.resize(size_t(n));
+    const char *err = nullptr;
+    if (!hipptTraceRadiance(rays.data(), seeds.data(), n, maxDepth, 0, radiance.data(), segments.data(), &err))
+        return fail(err, "path query failed");
+    return true;
+}
+
+bool HipPathTracer::cameraRays(int frame, std::vector<float> &rays, std::vector<unsigned> &seeds) {
+    const size_t n = size_t(std::max(0, m_width)) * size_t(std::max(0, m_height));
+    rays.resize(n * 8);
+    seeds.resize(n);
+    const char *err = nullptr;
+    if (!hipptCameraRays(frame, 0, rays.data(), seeds.data(), &err)) return fail(err, "camera rays failed");
+    return true;
+}
+
 bool HipPathTracer::denoise(const hipptDenoiseParams *params, std::vector<unsigned> &pixels) {
     pixels.resize(size_t(m_width > 0 ? m_width : 0) * size_t(m_height > 0 ? m_height : 0));
     const char *err = nullptr;

@@ -54,6 +54,14 @@ public:
     // The same query with a hit record per ray (hipptHit: t, prim, the shading normal faced against the
     // ray, the barycentrics, material index | HIPPT_HIT_SPHERE | HIPPT_HIT_BACKFACE).
     bool traceHits(const std::vector<float> &rays, std::vector<hipptHit> &hits);
+    // Path queries (include/hippt.h "path queries"): the renderer's path from each ray (8 floats, as
+    // traceRays; tmin and tmax hold for the first segment) with RNG state seeds[i]: radiance gets 4 floats
+    // per ray (rgb and 1 where the first segment hit), segments the closest-hit queries each path made.
+    bool traceRadiance(const std::vector<float> &rays, const std::vector<unsigned> &seeds, int maxDepth,
+                       std::vector<float> &radiance, std::vector<int> &segments);
+    // The rays renderFrames starts sample `frame` of every pixel with (8 floats each, row 0 = v = 0) and
+    // the RNG state each is left with: traceRadiance of them is that sample of the renderer.
+    bool cameraRays(int frame, std::vector<float> &rays, std::vector<unsigned> &seeds);
     // The primitive under pixel (x, y) and its distance, for sample `frame`'s camera ray; y counts rows
     // as hostPixels() does (row 0 = v = 0, the bottom row: a viewport click at yTop is height - 1 - yTop).
     // *prim = -1 and *t = +inf over the sky.

@@ -5,6 +5,7 @@
 //   hippt_render [--backend cuda|vulkan|gl] [--mesh FILE.obj|.ply] [--albedo r,g,b[;r,g,b...]]
 //                [--width W] [--height H] [--spp N] [--depth D] [--per-frame] [--present]
 //                [--out FILE] [--ppm FILE.ppm] [--pick X,Y] [--denoise PASSES]
+//                [--radiance-in FILE|camera --radiance-out FILE]
 //
 // --backend cuda (default): HipPathTracer, the CudaPathTracer interface.  Without --mesh: the
 // reference kernel's built-in 4-sphere scene, one renderFrame per frame (the CUDA backend's
@@ -21,6 +22,10 @@
 // ray_prim, ray_t_bits, ray_hit_words (the hipptHit's 8 words)}.  --denoise PASSES (cuda backend, with
 // --mesh): --out and --ppm get HipPathTracer::denoise's image (that many passes, the other parameters
 // at their defaults) in place of the rendered one.
+// --radiance-in FILE --radiance-out FILE (cuda backend, with --mesh): after the render,
+// HipPathTracer::traceRadiance at --depth over the file's rays (records of 9 words: the ray's 8 floats and
+// its RNG state; "camera": HipPathTracer::cameraRays of frame 0) written as records of 5 words (the
+// radiance's 4 floats and the segment count), reported as "radiance_rays".
 // Prints one JSON line.
 #include <chrono>
 #include <cstdio>
@@ -40,7 +45,8 @@ int usage() {
     std::fprintf(stderr,
                  "usage: hippt_render [--backend cuda|vulkan|gl] [--mesh FILE] [--albedo r,g,b[;...]] [--width W]\n"
                  "                    [--height H] [--spp N] [--depth D] [--per-frame] [--present] [--out FILE]\n"
-                 "                    [--ppm FILE.ppm] [--pick X,Y] [--update-mesh FILE] [--denoise PASSES]\n");
+                 "                    [--ppm FILE.ppm] [--pick X,Y] [--update-mesh FILE] [--denoise PASSES]\n"
+                 "                    [--radiance-in FILE|camera --radiance-out FILE]\n");
     return 2;
 }
 
@@ -61,7 +67,7 @@ std::vector<float> parse_floats(const std::string &s) {
 }  // namespace
 
 int main(int argc, char **argv) {
-    std::string mesh, out, ppm, albedoArg, pickArg, updateMesh, backend = "cuda";
+    std::string mesh, out, ppm, albedoArg, pickArg, updateMesh, radianceIn, radianceOut, backend = "cuda";
     int width = 320, height = 180, spp = 16, depth = 8, denoise = -1;
     bool perFrame = false, present = false;
     for (int i = 1; i < argc; ++i) {
@@ -83,6 +89,8 @@ int main(int argc, char **argv) {
         else if (a == "--pick") pickArg = v;
         else if (a == "--update-mesh") updateMesh = v;
         else if (a == "--denoise") denoise = std::atoi(v);
+        else if (a == "--radiance-in") radianceIn = v;
+        else if (a == "--radiance-out") radianceOut = v;
         else return usage();
     }
     if (backend != "cuda" && backend != "vulkan" && backend != "gl") return usage();
@@ -266,6 +274,42 @@ int main(int argc, char **argv) {
                       "\"ray_t_bits\": %u, \"ray_hit_words\": [%u, %u, %u, %u, %u, %u, %u, %u]}", int(xy[0]), int(xy[1]), prim,
                       tb, prims[0], rb, hw[0], hw[1], hw[2], hw[3], hw[4], hw[5], hw[6], hw[7]);
         pickJson = buf;
+    }
+    if (!radianceIn.empty()) {
+        std::vector<float> rays, radiance;
+        std::vector<unsigned> seeds;
+        std::vector<int> segments;
+        if (radianceIn == "camera") {
+            if (!tracer.cameraRays(0, rays, seeds)) {
+                std::fprintf(stderr, "hippt_render: cameraRays: %s\n", tracer.lastError().c_str());
+                return 1;
+            }
+        } else {
+            FILE *f = std::fopen(radianceIn.c_str(), "rb");
+            unsigned rec[9];
+            while (f && std::fread(rec, sizeof rec, 1, f) == 1) {
+                float r8[8];
+                std::memcpy(r8, rec, sizeof r8);
+                rays.insert(rays.end(), r8, r8 + 8);
+                seeds.push_back(rec[8]);
+            }
+            if (!f) return 1;
+            std::fclose(f);
+        }
+        if (!tracer.traceRadiance(rays, seeds, depth, radiance, segments)) {
+            std::fprintf(stderr, "hippt_render: traceRadiance: %s\n", tracer.lastError().c_str());
+            return 1;
+        }
+        FILE *f = radianceOut.empty() ? nullptr : std::fopen(radianceOut.c_str(), "wb");
+        if (!f) return 1;
+        for (size_t i = 0; i < segments.size(); ++i) {
+            unsigned rec[5];
+            std::memcpy(rec, &radiance[4 * i], 16);
+            std::memcpy(rec + 4, &segments[i], 4);
+            if (std::fwrite(rec, sizeof rec, 1, f) != 1) return 1;
+        }
+        std::fclose(f);
+        pickJson += ", \"radiance_rays\": " + std::to_string(segments.size());
     }
     hipptGetStats(&st);
     std::printf("{\"backend\": \"cuda\", \"frames\": %d, \"seconds\": %.6f, \"segments\": %llu, "
