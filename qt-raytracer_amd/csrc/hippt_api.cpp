@@ -39,6 +39,7 @@
 #include "hippt_path.h"
 #include "hippt_plan.h"
 #include "hippt_query.h"
+#include "hippt_query_layout.h"
 #include "hippt_refit.h"
 #include "hippt_sky_rect.h"
 #include "hippt_slab.h"
@@ -100,7 +101,7 @@ struct OccKey {
     int version = -1, stackDepth = 0, fmt = 0, poolWords = 0;
     unsigned topBytes = 0;
     bool ldsScene = false, full = false, spills = false;
-    int variant = 0;  // queries: any | camera << 1 | records << 2 | path << 3
+    int variant = 0;  // queries: the QueryMode, 8 for a path query
 };
 
 bool same_key(const OccKey &a, const OccKey &b) {
@@ -428,8 +429,8 @@ bool fail(const char **errorMessage, const std::string &msg) {
     return false;
 }
 
-// fail() for the C ABI's exception handlers (no lock held there: the entry point's lock_guard is gone
-// by the time its function-try-block's handler runs).  An exception (std::bad_alloc from a scene
+// fail() for the C ABI's exception handlers (abi_guard below; no lock held there: the guard's lock is
+// gone by the time its handler runs).  An exception (std::bad_alloc from a scene
 // buffer sized by caller input, ...) becomes the reference's false + message
 // (CudaPathTracerKernel.cu:181-184) instead of crossing extern "C" into std::terminate.
 bool fail_free(const char **errorMessage, const char *what) {
@@ -442,6 +443,43 @@ bool fail_free(const char **errorMessage, const char *what) {
         hipError_t e_ = (expr);                                                           \
         if (e_ != hipSuccess) return fail(err, std::string(#expr ": ") + hipGetErrorString(e_)); \
     } while (0)
+
+// ---- the C ABI's guard ---------------------------------------------------------------------------
+// Every extern "C" entry point is its argument packing plus one of these calls.  They run `body`, under
+// the state's lock where `lock` says so, and turn an exception into the entry point's failure value: an
+// exception must not cross the C ABI (the caller is C or Qt code).  The lock is released before the
+// failure value is made (fail_free takes it again).  The failure value is one of three: false with the
+// exception's message (abi_bool), a fixed value (abi_value), nothing (abi_void); the two entry points
+// that leave the message and return a value of their own call abi_guard itself.
+enum AbiLock { kUnlocked, kLocked };
+
+template <class Body, class OnThrow>
+auto abi_guard(AbiLock lock, Body body, OnThrow onThrow) -> decltype(body()) {
+    try {
+        std::unique_lock<std::mutex> g(S().mu, std::defer_lock);
+        if (lock == kLocked) g.lock();
+        return body();
+    } catch (const std::exception &e) {
+        return onThrow(e.what());
+    } catch (...) {
+        return onThrow("unknown exception");
+    }
+}
+// false and the exception's message in *err (and hipptLastError)
+template <class Body>
+bool abi_bool(AbiLock lock, const char **err, Body body) {
+    return abi_guard(lock, body, [err](const char *what) { return fail_free(err, what); });
+}
+// a fixed value
+template <class R, class Body>
+R abi_value(AbiLock lock, R fallback, Body body) {
+    return abi_guard(lock, body, [fallback](const char *) { return fallback; });
+}
+// nothing
+template <class Body>
+void abi_void(AbiLock lock, Body body) {
+    abi_guard(lock, body, [](const char *) {});
+}
 
 // ---- fp32 helpers with the oracle's contract (explicit fma only) ---------------------------
 inline float fdot(const float *a, const float *b) { return std::fmaf(a[0], b[0], std::fmaf(a[1], b[1], a[2] * b[2])); }
@@ -2045,27 +2083,31 @@ bool render_locked(int frameIndex, int count, int maxDepth, const unsigned int *
 // already holds, followed by a wait for the query's own event.  It reads the scene buffers only: it
 // does not flush the deferred combine or the chain, launches no held batch, and leaves the stats and
 // the timing events alone, so pending asynchronous frames come out as if it had not been made.
+using hippt::QueryMode;
+using hippt::qlayout::Slot;
+
 struct QueryCall {
-    const float *rays = nullptr;  // numRays x 8 floats (camera: null)
-    long long n = 0;
+    QueryMode mode = QueryMode::Closest;
+    bool path = false;     // hipptTraceRadiance: the renderer's path per ray, in place of the mode's result
+    bool camRays = false;  // hipptCameraRays: no traversal, the camera's rays and RNG states alone
+    long long n = 0;       // rays (a camera call: the image's pixels instead)
     int flags = 0;
-    float *t = nullptr;
-    int *prim = nullptr;
-    unsigned char *occ = nullptr;
-    hipptHit *hits = nullptr;  // hit records (hipptTraceHits, hipptTraceCameraHits): these, not t / prim
-    bool any = false, camera = false, records = false;
-    int frame = 0;
-    // path queries (hipptTraceRadiance): the renderer's path per ray, these in place of t / prim
-    bool path = false;
-    const unsigned *seeds = nullptr;
-    float *radiance = nullptr;  // numRays x 4 floats
-    int *segments = nullptr;    // may be null
-    int maxDepth = 0;
-    // the camera's rays (hipptCameraRays; with `camera`): no traversal, these outputs alone
-    bool camRays = false;
-    float *outRays = nullptr;  // width * height x 8 floats
-    unsigned *outSeeds = nullptr;
+    int frame = 0;     // camera calls
+    int maxDepth = 0;  // path
+    hippt::qlayout::Table bufs;  // the caller's buffers (hippt_query_layout.h)
+    bool camera() const { return camRays || hippt::query_camera(mode); }
 };
+
+QueryCall query_call(QueryMode mode, long long n, int frame, int flags,
+                     std::initializer_list<std::pair<Slot, const void *>> bufs) {
+    QueryCall q;
+    q.mode = mode;
+    q.n = n;
+    q.frame = frame;
+    q.flags = flags;
+    for (const auto &b : bufs) q.bufs.add(b.first, b.second);
+    return q;
+}
 
 // The device pointers of one launch of a path query or of the camera's rays (those QueryParams lacks).
 struct PathPtrs {
@@ -2075,6 +2117,63 @@ struct PathPtrs {
     float4 *outRays = nullptr;
     unsigned *outSeeds = nullptr;
 };
+
+// Puts a buffer's device pointer where its slot says.
+void set_slot(hippt::QueryParams &q, PathPtrs &pp, Slot slot, void *p) {
+    switch (slot) {
+    case Slot::Rays: q.rays = static_cast<const float4 *>(p); break;
+    case Slot::T: q.t = static_cast<float *>(p); break;
+    case Slot::Prim: q.prim = static_cast<int *>(p); break;
+    case Slot::Occluded: q.occluded = static_cast<unsigned char *>(p); break;
+    case Slot::Hits: q.hits = static_cast<float4 *>(p); break;
+    case Slot::Seeds: pp.seeds = static_cast<const unsigned *>(p); break;
+    case Slot::Radiance: pp.radiance = static_cast<float4 *>(p); break;
+    case Slot::Segments: pp.segments = static_cast<int *>(p); break;
+    case Slot::OutRays: pp.outRays = static_cast<float4 *>(p); break;
+    case Slot::OutSeeds: pp.outSeeds = static_cast<unsigned *>(p); break;
+    }
+}
+
+// Ray `at` of a caller's buffer.
+char *ray_at(const hippt::qlayout::Buffer &b, long long at) {
+    return static_cast<char *>(const_cast<void *>(b.ptr)) + size_t(at) * b.bytesPerRay;
+}
+
+// Makes *buf a device buffer of at least `need` bytes (*bytes: its size).  A buffer that is too small
+// is freed first: if the allocation fails, *buf is null and *bytes 0.  `what` names the allocation in
+// the error message.
+bool grow(void **buf, size_t *bytes, size_t need, const char *what, const char **err) {
+    if (*bytes >= need) return true;
+    (void)hipFree(*buf);
+    *buf = nullptr;
+    *bytes = 0;
+    const hipError_t e = hipMalloc(buf, need);
+    if (e != hipSuccess) return fail(err, std::string(what) + ": " + hipGetErrorString(e));
+    *bytes = need;
+    return true;
+}
+
+// The check of a call's device pointers (the null ones skipped), in order; per pointer: device memory,
+// on `requiredDevice` (-1: on the device of the pointers before it), aligned.  *device: where they are.
+bool device_pointers_ok(const std::string &who, const char *flagName, int requiredDevice, const void *const *ptrs,
+                        const size_t *aligns, int count, int *device, const char **err) {
+    int dev = requiredDevice;
+    for (int k = 0; k < count; ++k) {
+        if (!ptrs[k]) continue;
+        hipPointerAttribute_t a{};
+        if (hipPointerGetAttributes(&a, ptrs[k]) != hipSuccess || a.type != hipMemoryTypeDevice) {
+            (void)hipGetLastError();
+            return fail(err, who + ": " + flagName + " needs device memory pointers");
+        }
+        if (dev >= 0 && a.device != dev)
+            return fail(err, who + (requiredDevice >= 0 ? ": the pointers are not on the context's device"
+                                                        : ": pointers on different devices"));
+        dev = a.device;
+        if (reinterpret_cast<uintptr_t>(ptrs[k]) % aligns[k]) return fail(err, who + ": misaligned device pointer");
+    }
+    if (device) *device = dev;
+    return true;
+}
 
 // The traversal's layout and parameters for the current scene on context c: the render's plan under
 // the queries' profile (hippt_plan.h query_knobs: the wavefront extend kernel's loop parameters, float
@@ -2100,7 +2199,7 @@ bool query_setup(Ctx &c, const QueryCall &call, hippt::QueryParams &q, const cha
     q.waveThreshold = L.waveThreshold;
     q.leafExit = L.leafExit;
     q.nodeExit = L.nodeExit;
-    if (call.camera) {
+    if (call.camera()) {
         hippt::QueryCam &k = q.cam;
         k.cam = current_camera();
         k.invW = 1.0f / float(std::max(1, s.width - 1));
@@ -2119,22 +2218,18 @@ bool query_setup(Ctx &c, const QueryCall &call, hippt::QueryParams &q, const cha
     OccKey occKey;
     occKey.version = s.scene.version, occKey.stackDepth = L.stackDepth, occKey.fmt = L.fmt, occKey.topBytes = L.topBytes;
     occKey.ldsScene = L.ldsScene, occKey.full = f.full;
-    occKey.variant = (call.any ? 1 : 0) | (call.camera ? 2 : 0) | (call.records ? 4 : 0) | (call.path ? 8 : 0);
+    occKey.variant = call.path ? 8 : int(call.mode);
     if (!same_key(c.qOccKey, occKey)) {
         c.qBlocksPerCu = call.path ? hippt::path_blocks_per_cu(hippt::PathParams{q, c.mats, nullptr, nullptr, nullptr, 1})
-                                   : hippt::query_blocks_per_cu(q, call.any, call.camera, call.records);
+                                   : hippt::query_blocks_per_cu(q, call.mode);
         c.qOccKey = occKey;
     }
     if (!c.qCtr) HIP_TRY(hipMalloc(&c.qCtr, hippt::kQueryCtrBytes));
     if (L.wide) {
         const size_t bytes = size_t(c.cus) * size_t(c.qBlocksPerCu) * hippt::kMeshBlock * size_t(q.spillCap) * sizeof(int);
-        if (c.qSpillBytes < bytes) {  // (no query is in flight: every call waits for its own)
-            (void)hipFree(c.qSpill);
-            c.qSpill = nullptr;
-            c.qSpillBytes = 0;
-            HIP_TRY(hipMalloc(&c.qSpill, bytes));
-            c.qSpillBytes = bytes;
-        }
+        // (no query is in flight: every call waits for its own)
+        if (!grow(reinterpret_cast<void **>(&c.qSpill), &c.qSpillBytes, bytes, "hipMalloc(&c.qSpill, bytes)", err))
+            return false;
         q.spill = c.qSpill;
     }
     q.counter = c.qCtr;
@@ -2159,56 +2254,55 @@ bool query_enqueue(Ctx &c, hippt::QueryParams q, unsigned first, unsigned m, con
         HIP_TRY(hippt::launch_path(hippt::PathParams{q, c.mats, pp.seeds, pp.radiance, pp.segments, call.maxDepth}, int(blocks),
                                    c.stream));
     else
-        HIP_TRY(hippt::launch_query(q, int(blocks), call.any, call.camera, call.records, c.stream));
+        HIP_TRY(hippt::launch_query(q, int(blocks), call.mode, c.stream));
+    return true;
+}
+
+// Enqueues rays [0, n) of a query whose buffers are device memory, at most kLaunchRays per launch.
+bool query_enqueue_device(Ctx &c, const hippt::QueryParams &q0, const QueryCall &call, long long n, const char **err) {
+    constexpr long long kLaunchRays = 1LL << 30;
+    for (long long at = 0; at < n; at += kLaunchRays) {
+        hippt::QueryParams q = q0;
+        PathPtrs pp;
+        for (int k = 0; k < call.bufs.n; ++k)
+            if (call.bufs.b[k].ptr) set_slot(q, pp, call.bufs.b[k].slot, ray_at(call.bufs.b[k], at));
+        if (!query_enqueue(c, q, unsigned(at), unsigned(std::min(kLaunchRays, n - at)), call, err, pp)) return false;
+    }
     return true;
 }
 
 bool query_locked(const QueryCall &call, const char **err) {
     State &s = S();
+    const hippt::qlayout::Table &bufs = call.bufs;
     // argument and state checks first: none of them touches the GPU
     const bool pathApi = call.path || call.camRays;  // (their messages name them)
     const std::string who = pathApi ? "path query" : "ray query";
     if (call.path && call.maxDepth < 1) return fail(err, who + ": maxDepth must be at least 1");
     if (call.n < 0) return fail(err, who + ": negative ray count");
-    if (!call.camera && !call.rays && call.n > 0) return fail(err, who + ": null ray buffer");
-    if (call.path && !call.seeds && call.n > 0) return fail(err, who + ": null seed buffer");
-    if (call.path ? (!call.radiance && call.n > 0)
-        : call.camRays ? (!call.outRays && !call.outSeeds)
-        : call.records ? !call.hits
-        : call.any     ? !call.occ
-                       : (!call.t && !call.prim))
+    if (!call.camera() && !bufs.ptr(Slot::Rays) && call.n > 0) return fail(err, who + ": null ray buffer");
+    if (call.path && !bufs.ptr(Slot::Seeds) && call.n > 0) return fail(err, who + ": null seed buffer");
+    if (call.path ? (!bufs.ptr(Slot::Radiance) && call.n > 0) : !bufs.any_out())
         return fail(err, who + ": no output buffer");
-    if (call.camera && call.frame < 0) return fail(err, who + ": negative frame");
+    if (call.camera() && call.frame < 0) return fail(err, who + ": negative frame");
     if (pathApi && (call.flags & ~HIPPT_RAYS_DEVICE)) return fail(err, who + ": unknown flags");
     if (s.scene.kind != HIPPT_SCENE_MESH)
         return fail(err, who + ": needs a scene from hipptUploadMesh or hipptUploadScene (the built-in scene has none)");
     if (!s.ready || s.ctxs.empty()) return fail(err, who + ": HIP path tracer not initialized");
     long long n = call.n;
-    if (call.camera) {
+    if (call.camera()) {
         n = (long long)s.width * (long long)s.height;
         if (n > (1LL << 31) - 1) return fail(err, who + ": image too large");
     }
     if (n == 0) return true;
     const bool device = (call.flags & HIPPT_RAYS_DEVICE) != 0;
     if (call.flags & ~HIPPT_RAYS_DEVICE) return fail(err, who + ": unknown flags");
-    constexpr long long kLaunchRays = 1LL << 30;
     if (device) {
         // every pointer on the device of one context: the whole batch runs there, unstaged
+        const void *ptrs[hippt::qlayout::kMaxBuffers];
+        size_t aligns[hippt::qlayout::kMaxBuffers];
+        for (int k = 0; k < bufs.n; ++k) ptrs[k] = bufs.b[k].ptr, aligns[k] = bufs.b[k].align;
         int dev = -1;
-        const void *ptrs[10] = {call.rays, call.t,        call.prim,     call.occ,     call.hits,
-                                call.seeds, call.radiance, call.segments, call.outRays, call.outSeeds};
-        const size_t align[10] = {16, 4, 4, 1, 32, 4, 16, 4, 16, 4};
-        for (int k = 0; k < 10; ++k) {
-            if (!ptrs[k]) continue;
-            hipPointerAttribute_t a{};
-            if (hipPointerGetAttributes(&a, ptrs[k]) != hipSuccess || a.type != hipMemoryTypeDevice) {
-                (void)hipGetLastError();
-                return fail(err, who + ": HIPPT_RAYS_DEVICE needs device memory pointers");
-            }
-            if (dev >= 0 && a.device != dev) return fail(err, who + ": pointers on different devices");
-            dev = a.device;
-            if (reinterpret_cast<uintptr_t>(ptrs[k]) % align[k]) return fail(err, who + ": misaligned device pointer");
-        }
+        if (!device_pointers_ok(who, "HIPPT_RAYS_DEVICE", -1, ptrs, aligns, bufs.n, &dev, err)) return false;
         Ctx *cp = nullptr;
         for (Ctx &c : s.ctxs)
             if (c.device == dev && !cp) cp = &c;
@@ -2218,52 +2312,25 @@ bool query_locked(const QueryCall &call, const char **err) {
         if (!ensure_scene(c, err)) return false;
         hippt::QueryParams q;
         if (!query_setup(c, call, q, err)) return false;
-        for (long long at = 0; at < n; at += kLaunchRays) {
-            const unsigned m = unsigned(std::min(kLaunchRays, n - at));
-            q.rays = call.rays ? reinterpret_cast<const float4 *>(call.rays + 8 * at) : nullptr;
-            q.t = call.t ? call.t + at : nullptr;
-            q.prim = call.prim ? call.prim + at : nullptr;
-            q.occluded = call.occ ? call.occ + at : nullptr;
-            q.hits = call.hits ? reinterpret_cast<float4 *>(call.hits + at) : nullptr;
-            PathPtrs pp;
-            pp.seeds = call.seeds ? call.seeds + at : nullptr;
-            pp.radiance = call.radiance ? reinterpret_cast<float4 *>(call.radiance + 4 * at) : nullptr;
-            pp.segments = call.segments ? call.segments + at : nullptr;
-            pp.outRays = call.outRays ? reinterpret_cast<float4 *>(call.outRays + 8 * at) : nullptr;
-            pp.outSeeds = call.outSeeds ? call.outSeeds + at : nullptr;
-            if (!query_enqueue(c, q, unsigned(at), m, call, err, pp)) return false;
-        }
+        if (!query_enqueue_device(c, q, call, n, err)) return false;
         HIP_TRY(hipEventRecord(c.qDone, c.stream));
         HIP_TRY(hipEventSynchronize(c.qDone));
         return true;
     }
     // host memory: contiguous shares over the contexts, each cut into slices staged through the
-    // context's buffers (rays in, results out); slice j of every context is enqueued before slice j + 1
+    // context's buffers (inputs in, results out); slice j of every context is enqueued before slice j + 1
     const long long slice = s.querySlice > 0 ? std::max(64LL, s.querySlice) : (1LL << 22);
     const size_t K = s.ctxs.size();
     std::vector<hippt::QueryParams> qs(K);
     std::vector<char *> stage(K, nullptr);
-    const size_t cap = size_t(std::min(slice, n));
-    // (rays, then the results: hit records, or t, prim and the occlusion bytes; a path query: rays,
-    // seeds, then radiance and segments; the camera's rays: rays and seeds, both results)
-    const size_t offT = cap * 32, offP = offT + cap * 4, offO = offP + cap * 4, offH = offT;
-    const size_t offS = cap * 32, offR = offS + ((cap * 4 + 15) & ~size_t(15)), offG = offR + cap * 16;
-    const size_t stageBytes = pathApi        ? offG + cap * 4
-                              : call.records ? offH + cap * sizeof(hipptHit)
-                                             : offO + ((cap + 15) & ~size_t(15));
+    const hippt::qlayout::Staging lay = hippt::qlayout::staging(bufs, size_t(std::min(slice, n)));
     for (size_t k = 0; k < K; ++k) {
         Ctx &c = s.ctxs[k];
         if (n * (long long)(k + 1) / (long long)K == n * (long long)k / (long long)K) continue;  // an empty share
         HIP_TRY(hipSetDevice(c.device));
         if (!ensure_scene(c, err)) return false;
         if (!query_setup(c, call, qs[k], err)) return false;
-        if (c.qStageBytes < stageBytes) {
-            (void)hipFree(c.qStage);
-            c.qStage = nullptr;
-            c.qStageBytes = 0;
-            HIP_TRY(hipMalloc(&c.qStage, stageBytes));
-            c.qStageBytes = stageBytes;
-        }
+        if (!grow(&c.qStage, &c.qStageBytes, lay.total, "hipMalloc(&c.qStage, stageBytes)", err)) return false;
         stage[k] = static_cast<char *>(c.qStage);
     }
     bool left = true;
@@ -2278,41 +2345,21 @@ bool query_locked(const QueryCall &call, const char **err) {
             const unsigned m = unsigned(std::min(slice, b - at));
             HIP_TRY(hipSetDevice(c.device));
             hippt::QueryParams q = qs[k];
-            char *const st = stage[k];
-            if (!call.camera) {
-                HIP_TRY(hipMemcpyAsync(st, call.rays + 8 * at, size_t(m) * 32, hipMemcpyHostToDevice, c.stream));
-                q.rays = reinterpret_cast<const float4 *>(st);
-            }
-            q.t = call.t ? reinterpret_cast<float *>(st + offT) : nullptr;
-            q.prim = call.prim ? reinterpret_cast<int *>(st + offP) : nullptr;
-            q.occluded = call.occ ? reinterpret_cast<unsigned char *>(st + offO) : nullptr;
-            q.hits = call.hits ? reinterpret_cast<float4 *>(st + offH) : nullptr;
             PathPtrs pp;
-            if (call.path) {
-                HIP_TRY(hipMemcpyAsync(st + offS, call.seeds + at, size_t(m) * 4, hipMemcpyHostToDevice, c.stream));
-                pp.seeds = reinterpret_cast<const unsigned *>(st + offS);
-                pp.radiance = reinterpret_cast<float4 *>(st + offR);
-                pp.segments = call.segments ? reinterpret_cast<int *>(st + offG) : nullptr;
-            }
-            if (call.camRays) {
-                pp.outRays = call.outRays ? reinterpret_cast<float4 *>(st) : nullptr;
-                pp.outSeeds = call.outSeeds ? reinterpret_cast<unsigned *>(st + offS) : nullptr;
+            for (int i = 0; i < bufs.n; ++i) {
+                const hippt::qlayout::Buffer &bf = bufs.b[i];
+                if (!bf.ptr) continue;
+                char *const dev = stage[k] + lay.off[i];
+                if (!bf.out) HIP_TRY(hipMemcpyAsync(dev, ray_at(bf, at), m * bf.bytesPerRay, hipMemcpyHostToDevice, c.stream));
+                set_slot(q, pp, bf.slot, dev);
             }
             if (!query_enqueue(c, q, unsigned(at), m, call, err, pp)) return false;
-            if (call.path) {
-                HIP_TRY(hipMemcpyAsync(call.radiance + 4 * at, pp.radiance, size_t(m) * 16, hipMemcpyDeviceToHost, c.stream));
-                if (call.segments)
-                    HIP_TRY(hipMemcpyAsync(call.segments + at, pp.segments, size_t(m) * 4, hipMemcpyDeviceToHost, c.stream));
+            for (int i = 0; i < bufs.n; ++i) {
+                const hippt::qlayout::Buffer &bf = bufs.b[i];
+                if (bf.ptr && bf.out)
+                    HIP_TRY(hipMemcpyAsync(ray_at(bf, at), stage[k] + lay.off[i], m * bf.bytesPerRay, hipMemcpyDeviceToHost,
+                                           c.stream));
             }
-            if (call.outRays)
-                HIP_TRY(hipMemcpyAsync(call.outRays + 8 * at, pp.outRays, size_t(m) * 32, hipMemcpyDeviceToHost, c.stream));
-            if (call.outSeeds)
-                HIP_TRY(hipMemcpyAsync(call.outSeeds + at, pp.outSeeds, size_t(m) * 4, hipMemcpyDeviceToHost, c.stream));
-            if (call.hits)
-                HIP_TRY(hipMemcpyAsync(call.hits + at, q.hits, size_t(m) * sizeof(hipptHit), hipMemcpyDeviceToHost, c.stream));
-            if (call.t) HIP_TRY(hipMemcpyAsync(call.t + at, q.t, size_t(m) * 4, hipMemcpyDeviceToHost, c.stream));
-            if (call.prim) HIP_TRY(hipMemcpyAsync(call.prim + at, q.prim, size_t(m) * 4, hipMemcpyDeviceToHost, c.stream));
-            if (call.occ) HIP_TRY(hipMemcpyAsync(call.occ + at, q.occluded, size_t(m), hipMemcpyDeviceToHost, c.stream));
         }
     }
     for (size_t k = 0; k < K; ++k) {
@@ -2358,30 +2405,16 @@ bool denoise_locked(const hipptDenoiseParams *params, unsigned int *pixels, floa
     const bool device = (P.flags & HIPPT_DENOISE_DEVICE) != 0;
     if (device) {
         const void *ptrs[2] = {pixels, rgba};
-        const size_t align[2] = {4, 16};
-        for (int k = 0; k < 2; ++k) {
-            if (!ptrs[k]) continue;
-            hipPointerAttribute_t a{};
-            if (hipPointerGetAttributes(&a, ptrs[k]) != hipSuccess || a.type != hipMemoryTypeDevice) {
-                (void)hipGetLastError();
-                return fail(err, "denoise: HIPPT_DENOISE_DEVICE needs device memory pointers");
-            }
-            if (a.device != c.device) return fail(err, "denoise: the pointers are not on the context's device");
-            if (reinterpret_cast<uintptr_t>(ptrs[k]) % align[k]) return fail(err, "denoise: misaligned device pointer");
-        }
+        const size_t aligns[2] = {4, 16};
+        if (!device_pointers_ok("denoise", "HIPPT_DENOISE_DEVICE", c.device, ptrs, aligns, 2, nullptr, err)) return false;
     }
     if (!sync_locked(err)) return false;
     HIP_TRY(hipSetDevice(c.device));
     if (!ensure_scene(c, err)) return false;
     const size_t px = size_t(n);
     const size_t bytes = px * 80;
-    if (c.dnBytes < bytes) {  // (no denoise is in flight: every call waits for its own)
-        (void)hipFree(c.dnBuf);
-        c.dnBuf = nullptr;
-        c.dnBytes = 0;
-        HIP_TRY(hipMalloc(&c.dnBuf, bytes));
-        c.dnBytes = bytes;
-    }
+    // (no denoise is in flight: every call waits for its own)
+    if (!grow(&c.dnBuf, &c.dnBytes, bytes, "hipMalloc(&c.dnBuf, bytes)", err)) return false;
     float4 *const hits = static_cast<float4 *>(c.dnBuf);  // 2 per pixel
     float4 *col[2] = {hits + 2 * px, hits + 3 * px};
     float4 *const guide = hits + 4 * px;
@@ -2403,18 +2436,10 @@ bool denoise_locked(const hipptDenoiseParams *params, unsigned int *pixels, floa
     };
     if (!mark(-1)) return false;
     // the guides: sample guideFrame's camera hit records
-    QueryCall call;
-    call.camera = true;
-    call.records = true;
-    call.frame = P.guideFrame;
-    call.hits = reinterpret_cast<hipptHit *>(hits);
+    const QueryCall call = query_call(QueryMode::CameraHits, 0, P.guideFrame, 0, {{Slot::Hits, hits}});
     hippt::QueryParams q;
     if (!query_setup(c, call, q, err)) return false;
-    constexpr long long kLaunchRays = 1LL << 30;
-    for (long long at = 0; at < n; at += kLaunchRays) {
-        q.hits = hits + 2 * at;
-        if (!query_enqueue(c, q, unsigned(at), unsigned(std::min(kLaunchRays, n - at)), call, err)) return false;
-    }
+    if (!query_enqueue_device(c, q, call, n, err)) return false;
     if (!mark(0)) return false;
     const int demodulate = (P.flags & HIPPT_DENOISE_NO_DEMODULATE) ? 0 : 1;
     HIP_TRY(hippt::launch_denoise_prepare(
@@ -2458,89 +2483,75 @@ bool denoise_locked(const hipptDenoiseParams *params, unsigned int *pixels, floa
 }  // namespace
 
 // ---- reference ABI ----------------------------------------------------------------------------
-extern "C" bool cudaPathTracerInit(int width, int height, const char **errorMessage) try {
-    std::lock_guard<std::mutex> g(S().mu);
-    return init_locked(width, height, errorMessage);
-} catch (const std::exception &e) {
-    return fail_free(errorMessage, e.what());
-} catch (...) {
-    return fail_free(errorMessage, "unknown exception");
+extern "C" bool cudaPathTracerInit(int width, int height, const char **errorMessage) {
+    return abi_bool(kLocked, errorMessage, [&]() -> bool {
+        return init_locked(width, height, errorMessage);
+    });
 }
 
 extern "C" bool cudaPathTracerRender(int frameIndex, int maxDepth, const unsigned int **hostPixels,
-                                     const char **errorMessage) try {
-    std::lock_guard<std::mutex> g(S().mu);
-    // the CUDA backend's ABI always hands out its ARGB words (HIPPT_OPT_PIXEL_FORMAT applies to
-    // the hippt* render calls)
-    // (restored on every way out, an exception caught below included: ADVICE r4)
-    struct FormatScope {
-        int &fmt;
-        const int saved;
-        ~FormatScope() { fmt = saved; }
-    } scope{S().pixelFormat, S().pixelFormat};
-    scope.fmt = HIPPT_PIXEL_ARGB;
-    return render_locked(frameIndex, 1, maxDepth, hostPixels, errorMessage);
-} catch (const std::exception &e) {
-    return fail_free(errorMessage, e.what());
-} catch (...) {
-    return fail_free(errorMessage, "unknown exception");
+                                     const char **errorMessage) {
+    return abi_bool(kLocked, errorMessage, [&]() -> bool {
+        // the CUDA backend's ABI always hands out its ARGB words (HIPPT_OPT_PIXEL_FORMAT applies to
+        // the hippt* render calls)
+        // (restored on every way out, an exception caught below included: ADVICE r4)
+        struct FormatScope {
+            int &fmt;
+            const int saved;
+            ~FormatScope() { fmt = saved; }
+        } scope{S().pixelFormat, S().pixelFormat};
+        scope.fmt = HIPPT_PIXEL_ARGB;
+        return render_locked(frameIndex, 1, maxDepth, hostPixels, errorMessage);
+    });
 }
 
-extern "C" void cudaPathTracerShutdown(void) try {
-    std::lock_guard<std::mutex> g(S().mu);
-    destroy_all();
-} catch (...) {
-    // an exception must not cross the C ABI (the caller is C or Qt code)
+extern "C" void cudaPathTracerShutdown(void) {
+    abi_void(kLocked, [&] {
+        destroy_all();
+    });
 }
 
-extern "C" bool hipPathTracerInit(int width, int height, const char **errorMessage) try {
-    return cudaPathTracerInit(width, height, errorMessage);
-} catch (const std::exception &e) {
-    return fail_free(errorMessage, e.what());
-} catch (...) {
-    return fail_free(errorMessage, "unknown exception");
+extern "C" bool hipPathTracerInit(int width, int height, const char **errorMessage) {
+    return abi_bool(kUnlocked, errorMessage, [&]() -> bool {
+        return cudaPathTracerInit(width, height, errorMessage);
+    });
 }
 extern "C" bool hipPathTracerRender(int frameIndex, int maxDepth, const unsigned int **hostPixels,
-                                    const char **errorMessage) try {
-    return cudaPathTracerRender(frameIndex, maxDepth, hostPixels, errorMessage);
-} catch (const std::exception &e) {
-    return fail_free(errorMessage, e.what());
-} catch (...) {
-    return fail_free(errorMessage, "unknown exception");
+                                    const char **errorMessage) {
+    return abi_bool(kUnlocked, errorMessage, [&]() -> bool {
+        return cudaPathTracerRender(frameIndex, maxDepth, hostPixels, errorMessage);
+    });
 }
 extern "C" void hipPathTracerShutdown(void) { cudaPathTracerShutdown(); }
 
 // ---- scene --------------------------------------------------------------------------------------
 extern "C" void hipptBuildCamera(const double lookfrom[3], const double lookat[3], const double vup[3],
-                                 double vfovDeg, double aspect, double aperture, double focusDist, hipptCamera *out) try {
-    static_assert(sizeof(hipptCamera) == sizeof(CameraF), "camera layout");
-    CameraF c;
-    build_camera(lookfrom, lookat, vup, vfovDeg, aspect, aperture, focusDist, c);
-    std::memcpy(out, &c, sizeof(c));
-} catch (...) {
-    // an exception must not cross the C ABI (the caller is C or Qt code)
+                                 double vfovDeg, double aspect, double aperture, double focusDist, hipptCamera *out) {
+    abi_void(kUnlocked, [&] {
+        static_assert(sizeof(hipptCamera) == sizeof(CameraF), "camera layout");
+        CameraF c;
+        build_camera(lookfrom, lookat, vup, vfovDeg, aspect, aperture, focusDist, c);
+        std::memcpy(out, &c, sizeof(c));
+    });
 }
 
-extern "C" bool hipptUseBuiltinScene(int sceneId, const char **err) try {
-    std::lock_guard<std::mutex> g(S().mu);
-    if (sceneId != HIPPT_SCENE_SPHERE4) return fail(err, "unknown built-in scene id");
-    // a pending mesh combine belongs to the image rendered so far: enqueue it before the switch
-    for (Ctx &c : S().ctxs)
-        if (!flush_deferred(c, err)) return false;
-    S().scene.kind = HIPPT_SCENE_SPHERE4;
-    return true;
-} catch (const std::exception &e) {
-    return fail_free(err, e.what());
-} catch (...) {
-    return fail_free(err, "unknown exception");
+extern "C" bool hipptUseBuiltinScene(int sceneId, const char **err) {
+    return abi_bool(kLocked, err, [&]() -> bool {
+        if (sceneId != HIPPT_SCENE_SPHERE4) return fail(err, "unknown built-in scene id");
+        // a pending mesh combine belongs to the image rendered so far: enqueue it before the switch
+        for (Ctx &c : S().ctxs)
+            if (!flush_deferred(c, err)) return false;
+        S().scene.kind = HIPPT_SCENE_SPHERE4;
+        return true;
+    });
 }
 
-extern "C" bool hipptUploadScene(const float *verts, const int *triMaterial, int numTris, const float *spheres,
+namespace {
+bool upload_scene_locked(const float *verts, const int *triMaterial, int numTris, const float *spheres,
                                  const int *sphereMaterial, int numSpheres, const hipptMaterial *materials,
                                  int numMaterials, const double lookfrom[3], const double lookat[3],
                                  const double vup[3], double vfovDeg, double aperture, double focusDist,
-                                 const char **err) try {
-    std::lock_guard<std::mutex> g(S().mu);
+                                 const char **err) {
     State &s = S();
     if (numTris < 0 || numSpheres < 0) return fail(err, "negative primitive count");
     if ((numTris > 0 && (!verts || !triMaterial)) || (numSpheres > 0 && (!spheres || !sphereMaterial)) ||
@@ -2678,28 +2689,34 @@ extern "C" bool hipptUploadScene(const float *verts, const int *triMaterial, int
     s.scene = std::move(sc);
     s.upd.hostStale = false;  // (an update of the replaced scene)
     return true;
-} catch (const std::exception &e) {
-    return fail_free(err, e.what());
-} catch (...) {
-    return fail_free(err, "unknown exception");
+}
+}  // namespace
+
+extern "C" bool hipptUploadScene(const float *verts, const int *triMaterial, int numTris, const float *spheres,
+                                 const int *sphereMaterial, int numSpheres, const hipptMaterial *materials,
+                                 int numMaterials, const double lookfrom[3], const double lookat[3],
+                                 const double vup[3], double vfovDeg, double aperture, double focusDist,
+                                 const char **err) {
+    return abi_bool(kLocked, err, [&] {
+        return upload_scene_locked(verts, triMaterial, numTris, spheres, sphereMaterial, numSpheres, materials, numMaterials,
+                                   lookfrom, lookat, vup, vfovDeg, aperture, focusDist, err);
+    });
 }
 
 extern "C" bool hipptUploadMesh(const float *verts, const int *triMaterial, int numTris, const float *albedo,
                                 int numMaterials, const double lookfrom[3], const double lookat[3],
                                 const double vup[3], double vfovDeg, double aperture, double focusDist,
-                                const char **err) try {
-    if (!albedo) return fail(err, "null scene pointer");
-    if (numTris <= 0) return fail(err, "BVH requires at least one triangle");
-    std::vector<hipptMaterial> mats(size_t(std::max(0, numMaterials)));
-    for (int m = 0; m < numMaterials; ++m)
-        mats[size_t(m)] = hipptMaterial{HIPPT_MAT_LAMBERTIAN, {albedo[3 * m], albedo[3 * m + 1], albedo[3 * m + 2]}, 0.0f,
-                                        1.0f};
-    return hipptUploadScene(verts, triMaterial, numTris, nullptr, nullptr, 0, mats.data(), numMaterials, lookfrom,
-                            lookat, vup, vfovDeg, aperture, focusDist, err);
-} catch (const std::exception &e) {
-    return fail_free(err, e.what());
-} catch (...) {
-    return fail_free(err, "unknown exception");
+                                const char **err) {
+    return abi_bool(kUnlocked, err, [&]() -> bool {
+        if (!albedo) return fail(err, "null scene pointer");
+        if (numTris <= 0) return fail(err, "BVH requires at least one triangle");
+        std::vector<hipptMaterial> mats(size_t(std::max(0, numMaterials)));
+        for (int m = 0; m < numMaterials; ++m)
+            mats[size_t(m)] = hipptMaterial{HIPPT_MAT_LAMBERTIAN, {albedo[3 * m], albedo[3 * m + 1], albedo[3 * m + 2]}, 0.0f,
+                                            1.0f};
+        return hipptUploadScene(verts, triMaterial, numTris, nullptr, nullptr, 0, mats.data(), numMaterials, lookfrom,
+                                lookat, vup, vfovDeg, aperture, focusDist, err);
+    });
 }
 
 // ---- vertex updates --------------------------------------------------------------------------------
@@ -2844,186 +2861,123 @@ bool update_vertices_locked(const float *verts, int numTris, int flags, const ch
 
 }  // namespace
 
-extern "C" bool hipptUpdateVertices(const float *verts, int numTris, int flags, const char **err) try {
-    std::lock_guard<std::mutex> g(S().mu);
-    return update_vertices_locked(verts, numTris, flags, err);
-} catch (const std::exception &e) {
-    return fail_free(err, e.what());
-} catch (...) {
-    return fail_free(err, "unknown exception");
+extern "C" bool hipptUpdateVertices(const float *verts, int numTris, int flags, const char **err) {
+    return abi_bool(kLocked, err, [&]() -> bool {
+        return update_vertices_locked(verts, numTris, flags, err);
+    });
 }
 
-extern "C" long long hipptSceneDownload(int what, void *dst, long long bytes, const char **err) try {
-    std::lock_guard<std::mutex> g(S().mu);
-    State &s = S();
-    auto bad = [&](const char *m) -> long long { return (fail(err, m), -1); };
-    if (s.scene.kind != HIPPT_SCENE_MESH) return bad("scene download: no mesh scene");
-    const SceneHost &sc = s.scene;
-    size_t need = 0;
-    switch (what) {
-    case HIPPT_SCENE_NODES2: need = sc.nodes.size(); break;
-    case HIPPT_SCENE_NODES4: need = sc.nodes4.size(); break;
-    case HIPPT_SCENE_PRIMS: need = sc.tris.size(); break;
-    case HIPPT_SCENE_SHADE: need = sc.shade.size(); break;
-    default: return bad("scene download: unknown buffer");
-    }
-    need *= sizeof(float4);
-    if (!dst) return (long long)need;
-    if (bytes < (long long)need) return bad("scene download: destination too small");
-    if (!s.ready || s.ctxs.empty()) return bad("scene download: HIP path tracer not initialized");
-    Ctx &c = s.ctxs[0];
-    if (!ensure_scene(c, err)) return -1;
-    if (!launch_held(c, err)) return -1;
-    const float4 *src = what == HIPPT_SCENE_NODES2   ? c.nodes
-                        : what == HIPPT_SCENE_NODES4 ? c.nodes4
-                        : what == HIPPT_SCENE_PRIMS  ? c.tris
-                                                     : c.shade;
-    if (hipSetDevice(c.device) != hipSuccess ||
-        hipMemcpyAsync(dst, src, need, hipMemcpyDeviceToHost, c.stream) != hipSuccess ||
-        hipStreamSynchronize(c.stream) != hipSuccess) {
-        (void)hipGetLastError();
-        return bad("scene download: copy failed");
-    }
-    return (long long)need;
-} catch (const std::exception &e) {
-    return (fail_free(err, e.what()), -1);
-} catch (...) {
-    return (fail_free(err, "unknown exception"), -1);
+extern "C" long long hipptSceneDownload(int what, void *dst, long long bytes, const char **err) {
+    return abi_guard(
+        kLocked,
+        [&]() -> long long {
+            State &s = S();
+            auto bad = [&](const char *m) -> long long { return (fail(err, m), -1); };
+            if (s.scene.kind != HIPPT_SCENE_MESH) return bad("scene download: no mesh scene");
+            const SceneHost &sc = s.scene;
+            size_t need = 0;
+            switch (what) {
+            case HIPPT_SCENE_NODES2: need = sc.nodes.size(); break;
+            case HIPPT_SCENE_NODES4: need = sc.nodes4.size(); break;
+            case HIPPT_SCENE_PRIMS: need = sc.tris.size(); break;
+            case HIPPT_SCENE_SHADE: need = sc.shade.size(); break;
+            default: return bad("scene download: unknown buffer");
+            }
+            need *= sizeof(float4);
+            if (!dst) return (long long)need;
+            if (bytes < (long long)need) return bad("scene download: destination too small");
+            if (!s.ready || s.ctxs.empty()) return bad("scene download: HIP path tracer not initialized");
+            Ctx &c = s.ctxs[0];
+            if (!ensure_scene(c, err)) return -1;
+            if (!launch_held(c, err)) return -1;
+            const float4 *src = what == HIPPT_SCENE_NODES2   ? c.nodes
+                                : what == HIPPT_SCENE_NODES4 ? c.nodes4
+                                : what == HIPPT_SCENE_PRIMS  ? c.tris
+                                                             : c.shade;
+            if (hipSetDevice(c.device) != hipSuccess ||
+                hipMemcpyAsync(dst, src, need, hipMemcpyDeviceToHost, c.stream) != hipSuccess ||
+                hipStreamSynchronize(c.stream) != hipSuccess) {
+                (void)hipGetLastError();
+                return bad("scene download: copy failed");
+            }
+            return (long long)need;
+        },
+        [err](const char *what) { return (fail_free(err, what), -1LL); });
 }
 
 // ---- ray queries ---------------------------------------------------------------------------------
+// (each call's buffers in the order of the device-pointer check)
 extern "C" bool hipptTraceRays(const float *rays, long long numRays, int flags, float *t, int *prim,
-                               const char **err) try {
-    std::lock_guard<std::mutex> g(S().mu);
-    QueryCall q;
-    q.rays = rays;
-    q.n = numRays;
-    q.flags = flags;
-    q.t = t;
-    q.prim = prim;
-    return query_locked(q, err);
-} catch (const std::exception &e) {
-    return fail_free(err, e.what());
-} catch (...) {
-    return fail_free(err, "unknown exception");
+                               const char **err) {
+    return abi_bool(kLocked, err, [&] {
+        return query_locked(
+            query_call(QueryMode::Closest, numRays, 0, flags, {{Slot::Rays, rays}, {Slot::T, t}, {Slot::Prim, prim}}), err);
+    });
 }
 
 extern "C" bool hipptOccluded(const float *rays, long long numRays, int flags, unsigned char *occluded,
-                              const char **err) try {
-    std::lock_guard<std::mutex> g(S().mu);
-    QueryCall q;
-    q.rays = rays;
-    q.n = numRays;
-    q.flags = flags;
-    q.occ = occluded;
-    q.any = true;
-    return query_locked(q, err);
-} catch (const std::exception &e) {
-    return fail_free(err, e.what());
-} catch (...) {
-    return fail_free(err, "unknown exception");
+                              const char **err) {
+    return abi_bool(kLocked, err, [&] {
+        return query_locked(query_call(QueryMode::Any, numRays, 0, flags, {{Slot::Rays, rays}, {Slot::Occluded, occluded}}),
+                            err);
+    });
 }
 
-extern "C" bool hipptTraceCamera(int frame, int flags, float *t, int *prim, const char **err) try {
-    std::lock_guard<std::mutex> g(S().mu);
-    QueryCall q;
-    q.camera = true;
-    q.frame = frame;
-    q.flags = flags;
-    q.t = t;
-    q.prim = prim;
-    return query_locked(q, err);
-} catch (const std::exception &e) {
-    return fail_free(err, e.what());
-} catch (...) {
-    return fail_free(err, "unknown exception");
+extern "C" bool hipptTraceCamera(int frame, int flags, float *t, int *prim, const char **err) {
+    return abi_bool(kLocked, err, [&] {
+        return query_locked(query_call(QueryMode::Camera, 0, frame, flags, {{Slot::T, t}, {Slot::Prim, prim}}), err);
+    });
 }
 
-extern "C" bool hipptTraceHits(const float *rays, long long numRays, int flags, hipptHit *hits, const char **err) try {
-    std::lock_guard<std::mutex> g(S().mu);
-    QueryCall q;
-    q.rays = rays;
-    q.n = numRays;
-    q.flags = flags;
-    q.hits = hits;
-    q.records = true;
-    return query_locked(q, err);
-} catch (const std::exception &e) {
-    return fail_free(err, e.what());
-} catch (...) {
-    return fail_free(err, "unknown exception");
+extern "C" bool hipptTraceHits(const float *rays, long long numRays, int flags, hipptHit *hits, const char **err) {
+    return abi_bool(kLocked, err, [&] {
+        return query_locked(query_call(QueryMode::Hits, numRays, 0, flags, {{Slot::Rays, rays}, {Slot::Hits, hits}}), err);
+    });
 }
 
-extern "C" bool hipptTraceCameraHits(int frame, int flags, hipptHit *hits, const char **err) try {
-    std::lock_guard<std::mutex> g(S().mu);
-    QueryCall q;
-    q.camera = true;
-    q.frame = frame;
-    q.flags = flags;
-    q.hits = hits;
-    q.records = true;
-    return query_locked(q, err);
-} catch (const std::exception &e) {
-    return fail_free(err, e.what());
-} catch (...) {
-    return fail_free(err, "unknown exception");
+extern "C" bool hipptTraceCameraHits(int frame, int flags, hipptHit *hits, const char **err) {
+    return abi_bool(kLocked, err, [&] {
+        return query_locked(query_call(QueryMode::CameraHits, 0, frame, flags, {{Slot::Hits, hits}}), err);
+    });
 }
 
 // ---- path queries --------------------------------------------------------------------------------
 extern "C" bool hipptTraceRadiance(const float *rays, const unsigned int *seeds, long long numRays, int maxDepth, int flags,
-                                   float *radiance, int *segments, const char **err) try {
-    std::lock_guard<std::mutex> g(S().mu);
-    QueryCall q;
-    q.path = true;
-    q.rays = rays;
-    q.seeds = seeds;
-    q.n = numRays;
-    q.maxDepth = maxDepth;
-    q.flags = flags;
-    q.radiance = radiance;
-    q.segments = segments;
-    return query_locked(q, err);
-} catch (const std::exception &e) {
-    return fail_free(err, e.what());
-} catch (...) {
-    return fail_free(err, "unknown exception");
+                                   float *radiance, int *segments, const char **err) {
+    return abi_bool(kLocked, err, [&] {
+        QueryCall q = query_call(
+            QueryMode::Closest, numRays, 0, flags,
+            {{Slot::Rays, rays}, {Slot::Seeds, seeds}, {Slot::Radiance, radiance}, {Slot::Segments, segments}});
+        q.path = true;
+        q.maxDepth = maxDepth;
+        return query_locked(q, err);
+    });
 }
 
-extern "C" bool hipptCameraRays(int frame, int flags, float *rays, unsigned int *seeds, const char **err) try {
-    std::lock_guard<std::mutex> g(S().mu);
-    QueryCall q;
-    q.camera = true;
-    q.camRays = true;
-    q.frame = frame;
-    q.flags = flags;
-    q.outRays = rays;
-    q.outSeeds = seeds;
-    return query_locked(q, err);
-} catch (const std::exception &e) {
-    return fail_free(err, e.what());
-} catch (...) {
-    return fail_free(err, "unknown exception");
+extern "C" bool hipptCameraRays(int frame, int flags, float *rays, unsigned int *seeds, const char **err) {
+    return abi_bool(kLocked, err, [&] {
+        QueryCall q = query_call(QueryMode::Closest, 0, frame, flags, {{Slot::OutRays, rays}, {Slot::OutSeeds, seeds}});
+        q.camRays = true;
+        return query_locked(q, err);
+    });
 }
 
-extern "C" void hipptDenoiseDefaults(hipptDenoiseParams *out) try {
-    if (!out) return;
-    std::memset(out, 0, sizeof(*out));
-    out->passes = 5;
-    out->guideFrame = 0;
-    out->normalPower = 6;
-    out->sigmaColor = 1.0f;
-    out->sigmaDepth = 0.05f;
-} catch (...) {
-    // an exception must not cross the C ABI (the caller is C or Qt code)
+extern "C" void hipptDenoiseDefaults(hipptDenoiseParams *out) {
+    abi_void(kUnlocked, [&] {
+        if (!out) return;
+        std::memset(out, 0, sizeof(*out));
+        out->passes = 5;
+        out->guideFrame = 0;
+        out->normalPower = 6;
+        out->sigmaColor = 1.0f;
+        out->sigmaDepth = 0.05f;
+    });
 }
 
-extern "C" bool hipptDenoise(const hipptDenoiseParams *params, unsigned int *pixels, float *rgba, const char **err) try {
-    std::lock_guard<std::mutex> g(S().mu);
-    return denoise_locked(params, pixels, rgba, err);
-} catch (const std::exception &e) {
-    return fail_free(err, e.what());
-} catch (...) {
-    return fail_free(err, "unknown exception");
+extern "C" bool hipptDenoise(const hipptDenoiseParams *params, unsigned int *pixels, float *rgba, const char **err) {
+    return abi_bool(kLocked, err, [&]() -> bool {
+        return denoise_locked(params, pixels, rgba, err);
+    });
 }
 
 namespace {
@@ -3033,225 +2987,188 @@ struct MeshOwner {
 };
 }  // namespace
 
-extern "C" bool hipptReadMesh(const char *path, hipptMesh *out, const char **err) try {
-    if (!path || !out) return fail(err, "null argument");
-    std::memset(out, 0, sizeof(*out));
-    std::unique_ptr<MeshOwner> own(new MeshOwner);
-    std::string msg;
-    if (!hippt::read_mesh(path, own->data, msg)) {
-        std::lock_guard<std::mutex> g(S().mu);
-        return fail(err, msg);
-    }
-    for (const std::string &n : own->data.groups) own->names.push_back(n.c_str());
-    out->verts = own->data.verts.data();
-    out->triGroup = own->data.group.data();
-    out->numTris = int(own->data.group.size());
-    out->numGroups = int(own->data.groups.size());
-    out->groupNames = own->names.data();
-    out->owner_ = own.release();
-    return true;
-} catch (const std::exception &e) {
-    return fail_free(err, e.what());
-} catch (...) {
-    return fail_free(err, "unknown exception");
+extern "C" bool hipptReadMesh(const char *path, hipptMesh *out, const char **err) {
+    return abi_bool(kUnlocked, err, [&]() -> bool {
+        if (!path || !out) return fail(err, "null argument");
+        std::memset(out, 0, sizeof(*out));
+        std::unique_ptr<MeshOwner> own(new MeshOwner);
+        std::string msg;
+        if (!hippt::read_mesh(path, own->data, msg)) {
+            std::lock_guard<std::mutex> g(S().mu);
+            return fail(err, msg);
+        }
+        for (const std::string &n : own->data.groups) own->names.push_back(n.c_str());
+        out->verts = own->data.verts.data();
+        out->triGroup = own->data.group.data();
+        out->numTris = int(own->data.group.size());
+        out->numGroups = int(own->data.groups.size());
+        out->groupNames = own->names.data();
+        out->owner_ = own.release();
+        return true;
+    });
 }
 
-extern "C" void hipptFreeMesh(hipptMesh *mesh) try {
-    if (!mesh) return;
-    delete static_cast<MeshOwner *>(mesh->owner_);
-    std::memset(mesh, 0, sizeof(*mesh));
-} catch (...) {
-    // an exception must not cross the C ABI (the caller is C or Qt code)
+extern "C" void hipptFreeMesh(hipptMesh *mesh) {
+    abi_void(kUnlocked, [&] {
+        if (!mesh) return;
+        delete static_cast<MeshOwner *>(mesh->owner_);
+        std::memset(mesh, 0, sizeof(*mesh));
+    });
 }
 
-extern "C" bool hipptSetCamera(const hipptCamera *camera, const char **err) try {
-    std::lock_guard<std::mutex> g(S().mu);
-    if (!camera) return fail(err, "null camera");
-    std::memcpy(&S().scene.cam, camera, sizeof(CameraF));
-    S().scene.rawCamera = true;
-    return true;
-} catch (const std::exception &e) {
-    return fail_free(err, e.what());
-} catch (...) {
-    return fail_free(err, "unknown exception");
+extern "C" bool hipptSetCamera(const hipptCamera *camera, const char **err) {
+    return abi_bool(kLocked, err, [&]() -> bool {
+        if (!camera) return fail(err, "null camera");
+        std::memcpy(&S().scene.cam, camera, sizeof(CameraF));
+        S().scene.rawCamera = true;
+        return true;
+    });
 }
 
 // ---- devices ------------------------------------------------------------------------------------
-extern "C" int hipptDeviceCount(void) try {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-    return n;
-} catch (const std::exception &e) {
-    return 0;
-} catch (...) {
-    return 0;
+extern "C" int hipptDeviceCount(void) {
+    return abi_value(kUnlocked, 0, [&]() -> int {
+        int n = 0;
+        if (hipGetDeviceCount(&n) != hipSuccess) return 0;
+        return n;
+    });
 }
 
-extern "C" bool hipptSetDevices(const int *deviceIds, int numDevices, const char **err) try {
-    std::lock_guard<std::mutex> g(S().mu);
-    State &s = S();
-    if (numDevices < 0 || (numDevices > 0 && !deviceIds)) return fail(err, "invalid device list");
-    int avail = 0;
-    HIP_TRY(hipGetDeviceCount(&avail));
-    for (int i = 0; i < numDevices; ++i)
-        if (deviceIds[i] < 0 || deviceIds[i] >= avail) return fail(err, "device id out of range");
-    s.devices.assign(deviceIds, deviceIds + numDevices);
-    return true;
-} catch (const std::exception &e) {
-    return fail_free(err, e.what());
-} catch (...) {
-    return fail_free(err, "unknown exception");
+extern "C" bool hipptSetDevices(const int *deviceIds, int numDevices, const char **err) {
+    return abi_bool(kLocked, err, [&]() -> bool {
+        State &s = S();
+        if (numDevices < 0 || (numDevices > 0 && !deviceIds)) return fail(err, "invalid device list");
+        int avail = 0;
+        HIP_TRY(hipGetDeviceCount(&avail));
+        for (int i = 0; i < numDevices; ++i)
+            if (deviceIds[i] < 0 || deviceIds[i] >= avail) return fail(err, "device id out of range");
+        s.devices.assign(deviceIds, deviceIds + numDevices);
+        return true;
+    });
 }
 
-extern "C" bool hipptSetRowRange(int y0, int y1, const char **err) try {
-    std::lock_guard<std::mutex> g(S().mu);
-    if (y0 < 0 || (y1 > 0 && y1 < y0)) return fail(err, "invalid row range");
-    S().rowY0 = y0;
-    S().rowY1 = y1;
-    S().rowPhase = 0;
-    S().rowStride = 1;
-    return true;
-} catch (const std::exception &e) {
-    return fail_free(err, e.what());
-} catch (...) {
-    return fail_free(err, "unknown exception");
+extern "C" bool hipptSetRowRange(int y0, int y1, const char **err) {
+    return abi_bool(kLocked, err, [&]() -> bool {
+        if (y0 < 0 || (y1 > 0 && y1 < y0)) return fail(err, "invalid row range");
+        S().rowY0 = y0;
+        S().rowY1 = y1;
+        S().rowPhase = 0;
+        S().rowStride = 1;
+        return true;
+    });
 }
 
-extern "C" bool hipptSetRowInterleave(int phase, int stride, const char **err) try {
-    std::lock_guard<std::mutex> g(S().mu);
-    if (stride < 1 || phase < 0 || phase >= stride) return fail(err, "invalid row interleave");
-    S().rowPhase = phase;
-    S().rowStride = stride;
-    S().rowY0 = 0;
-    S().rowY1 = 0;
-    return true;
-} catch (const std::exception &e) {
-    return fail_free(err, e.what());
-} catch (...) {
-    return fail_free(err, "unknown exception");
+extern "C" bool hipptSetRowInterleave(int phase, int stride, const char **err) {
+    return abi_bool(kLocked, err, [&]() -> bool {
+        if (stride < 1 || phase < 0 || phase >= stride) return fail(err, "invalid row interleave");
+        S().rowPhase = phase;
+        S().rowStride = stride;
+        S().rowY0 = 0;
+        S().rowY1 = 0;
+        return true;
+    });
 }
 
 // ---- rendering ----------------------------------------------------------------------------------
 extern "C" bool hipptRenderFrames(int firstFrame, int count, int maxDepth, const unsigned int **hostPixels,
-                                  const char **err) try {
-    std::lock_guard<std::mutex> g(S().mu);
-    return render_locked(firstFrame, count, maxDepth, hostPixels, err);
-} catch (const std::exception &e) {
-    return fail_free(err, e.what());
-} catch (...) {
-    return fail_free(err, "unknown exception");
+                                  const char **err) {
+    return abi_bool(kLocked, err, [&]() -> bool {
+        return render_locked(firstFrame, count, maxDepth, hostPixels, err);
+    });
 }
 
-extern "C" bool hipptRenderFramesAsync(int firstFrame, int count, int maxDepth, const char **err) try {
-    std::lock_guard<std::mutex> g(S().mu);
-    return enqueue_locked(firstFrame, count, maxDepth, false, err);
-} catch (const std::exception &e) {
-    return fail_free(err, e.what());
-} catch (...) {
-    return fail_free(err, "unknown exception");
+extern "C" bool hipptRenderFramesAsync(int firstFrame, int count, int maxDepth, const char **err) {
+    return abi_bool(kLocked, err, [&]() -> bool {
+        return enqueue_locked(firstFrame, count, maxDepth, false, err);
+    });
 }
 
-extern "C" bool hipptSynchronize(const char **err) try {
-    std::lock_guard<std::mutex> g(S().mu);
-    return sync_locked(err);
-} catch (const std::exception &e) {
-    return fail_free(err, e.what());
-} catch (...) {
-    return fail_free(err, "unknown exception");
+extern "C" bool hipptSynchronize(const char **err) {
+    return abi_bool(kLocked, err, [&]() -> bool {
+        return sync_locked(err);
+    });
 }
 
-extern "C" bool hipptRenderFramesPresent(int firstFrame, int count, int maxDepth, const char **err) try {
-    std::lock_guard<std::mutex> g(S().mu);
-    State &s = S();
-    if (!s.ready) return fail(err, "HIP path tracer not initialized");
-    const int b = s.presentNext;
-    // mapped + coherent like State::host: the frame's kernel writes the hand-off frame itself
-    if (!s.present[b])
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&s.present[b]), s.hostCount * sizeof(unsigned),
-                              hipHostMallocPortable | hipHostMallocMapped | hipHostMallocCoherent));
-    if (!enqueue_locked(firstFrame, count, maxDepth, true, err, s.present[b])) return false;
-    for (Ctx &c : s.ctxs) {
-        HIP_TRY(hipSetDevice(c.device));
-        if (!c.presentEv[b]) HIP_TRY(hipEventCreateWithFlags(&c.presentEv[b], hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(c.presentEv[b], c.stream));
-        if (!harvest_locked(c, err)) return false;
-    }
-    if (s.latest == b) s.latest = -1;  // its image is being replaced
-    s.presentPending[b] = true;
-    s.presentSeq[b] = s.presentCalls++;
-    s.presentFrames[b] = firstFrame + count;
-    s.presentNext = b ^ 1;
-    return true;
-} catch (const std::exception &e) {
-    return fail_free(err, e.what());
-} catch (...) {
-    return fail_free(err, "unknown exception");
-}
-
-extern "C" bool hipptLatestFrame(const unsigned int **hostPixels, int *frames, const char **err) try {
-    std::lock_guard<std::mutex> g(S().mu);
-    State &s = S();
-    if (!s.ready) return fail(err, "HIP path tracer not initialized");
-    for (int b = 0; b < 2; ++b) {
-        if (!s.presentPending[b]) continue;
-        bool done = true;
+extern "C" bool hipptRenderFramesPresent(int firstFrame, int count, int maxDepth, const char **err) {
+    return abi_bool(kLocked, err, [&]() -> bool {
+        State &s = S();
+        if (!s.ready) return fail(err, "HIP path tracer not initialized");
+        const int b = s.presentNext;
+        // mapped + coherent like State::host: the frame's kernel writes the hand-off frame itself
+        if (!s.present[b])
+            HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&s.present[b]), s.hostCount * sizeof(unsigned),
+                                  hipHostMallocPortable | hipHostMallocMapped | hipHostMallocCoherent));
+        if (!enqueue_locked(firstFrame, count, maxDepth, true, err, s.present[b])) return false;
         for (Ctx &c : s.ctxs) {
             HIP_TRY(hipSetDevice(c.device));
-            const hipError_t q = hipEventQuery(c.presentEv[b]);
-            if (q == hipErrorNotReady) {
-                done = false;
-                break;
+            if (!c.presentEv[b]) HIP_TRY(hipEventCreateWithFlags(&c.presentEv[b], hipEventDisableTiming));
+            HIP_TRY(hipEventRecord(c.presentEv[b], c.stream));
+            if (!harvest_locked(c, err)) return false;
+        }
+        if (s.latest == b) s.latest = -1;  // its image is being replaced
+        s.presentPending[b] = true;
+        s.presentSeq[b] = s.presentCalls++;
+        s.presentFrames[b] = firstFrame + count;
+        s.presentNext = b ^ 1;
+        return true;
+    });
+}
+
+extern "C" bool hipptLatestFrame(const unsigned int **hostPixels, int *frames, const char **err) {
+    return abi_bool(kLocked, err, [&]() -> bool {
+        State &s = S();
+        if (!s.ready) return fail(err, "HIP path tracer not initialized");
+        for (int b = 0; b < 2; ++b) {
+            if (!s.presentPending[b]) continue;
+            bool done = true;
+            for (Ctx &c : s.ctxs) {
+                HIP_TRY(hipSetDevice(c.device));
+                const hipError_t q = hipEventQuery(c.presentEv[b]);
+                if (q == hipErrorNotReady) {
+                    done = false;
+                    break;
+                }
+                if (q != hipSuccess) return fail(err, std::string("hipEventQuery: ") + hipGetErrorString(q));
             }
-            if (q != hipSuccess) return fail(err, std::string("hipEventQuery: ") + hipGetErrorString(q));
+            if (done) {
+                s.presentPending[b] = false;
+                if (s.latest < 0 || s.presentSeq[b] > s.presentSeq[s.latest]) s.latest = b;
+            }
         }
-        if (done) {
-            s.presentPending[b] = false;
-            if (s.latest < 0 || s.presentSeq[b] > s.presentSeq[s.latest]) s.latest = b;
-        }
-    }
-    if (hostPixels) *hostPixels = s.latest >= 0 ? s.present[s.latest] : nullptr;
-    if (frames) *frames = s.latest >= 0 ? s.presentFrames[s.latest] : 0;
-    return true;
-} catch (const std::exception &e) {
-    return fail_free(err, e.what());
-} catch (...) {
-    return fail_free(err, "unknown exception");
+        if (hostPixels) *hostPixels = s.latest >= 0 ? s.present[s.latest] : nullptr;
+        if (frames) *frames = s.latest >= 0 ? s.presentFrames[s.latest] : 0;
+        return true;
+    });
 }
 
-extern "C" bool hipptReadback(unsigned int *pixels, float *accum, const char **err) try {
-    std::lock_guard<std::mutex> g(S().mu);
-    State &s = S();
-    if (!s.ready) return fail(err, "HIP path tracer not initialized");
-    if (!sync_locked(err)) return false;
-    for (Ctx &c : s.ctxs) {
-        HIP_TRY(hipSetDevice(c.device));
-        if (pixels && !copy_rows_async(c, pixels, c.out, sizeof(uint32_t), err)) return false;
-        if (accum && !copy_rows_async(c, accum, c.accum, sizeof(float4), err)) return false;
-        HIP_TRY(hipStreamSynchronize(c.stream));
-    }
-    return true;
-} catch (const std::exception &e) {
-    return fail_free(err, e.what());
-} catch (...) {
-    return fail_free(err, "unknown exception");
+extern "C" bool hipptReadback(unsigned int *pixels, float *accum, const char **err) {
+    return abi_bool(kLocked, err, [&]() -> bool {
+        State &s = S();
+        if (!s.ready) return fail(err, "HIP path tracer not initialized");
+        if (!sync_locked(err)) return false;
+        for (Ctx &c : s.ctxs) {
+            HIP_TRY(hipSetDevice(c.device));
+            if (pixels && !copy_rows_async(c, pixels, c.out, sizeof(uint32_t), err)) return false;
+            if (accum && !copy_rows_async(c, accum, c.accum, sizeof(float4), err)) return false;
+            HIP_TRY(hipStreamSynchronize(c.stream));
+        }
+        return true;
+    });
 }
 
-extern "C" bool hipptResetAccumulation(const char **err) try {
-    std::lock_guard<std::mutex> g(S().mu);
-    State &s = S();
-    if (!s.ready) return fail(err, "HIP path tracer not initialized");
-    for (Ctx &c : s.ctxs) {
-        if (!flush_deferred(c, err)) return false;
-        HIP_TRY(hipSetDevice(c.device));
-        const size_t px = size_t(c.rows) * size_t(s.width);
-        HIP_TRY(hipMemsetAsync(c.accum, 0, px * sizeof(float4), c.stream));
-        HIP_TRY(hipStreamSynchronize(c.stream));
-    }
-    return true;
-} catch (const std::exception &e) {
-    return fail_free(err, e.what());
-} catch (...) {
-    return fail_free(err, "unknown exception");
+extern "C" bool hipptResetAccumulation(const char **err) {
+    return abi_bool(kLocked, err, [&]() -> bool {
+        State &s = S();
+        if (!s.ready) return fail(err, "HIP path tracer not initialized");
+        for (Ctx &c : s.ctxs) {
+            if (!flush_deferred(c, err)) return false;
+            HIP_TRY(hipSetDevice(c.device));
+            const size_t px = size_t(c.rows) * size_t(s.width);
+            HIP_TRY(hipMemsetAsync(c.accum, 0, px * sizeof(float4), c.stream));
+            HIP_TRY(hipStreamSynchronize(c.stream));
+        }
+        return true;
+    });
 }
 
 // A context's launch counters summed over their kStatSlots copies (hippt_device.h).
@@ -3266,75 +3183,68 @@ bool read_stats(const Ctx &c, unsigned long long (&v)[kStatWords]) {
 }
 
 // ---- counters / options -------------------------------------------------------------------------
-extern "C" bool hipptGetStats(hipptStats *out) try {
-    std::lock_guard<std::mutex> g(S().mu);
-    State &s = S();
-    if (!out) return false;
-    std::memset(out, 0, sizeof(*out));
-    const char *err = nullptr;
-    if (s.ready && !sync_locked(&err)) return false;
-    for (Ctx &c : s.ctxs) {
-        unsigned long long v[kStatWords];
-        if (!read_stats(c, v)) return false;
-        out->segments += v[0];
-        out->pixelSamples += v[1] + c.hostSamples;
-        out->nodeVisits += v[2];
-        out->triTests += v[3];
-    }
-    out->traceMs = s.traceMs;
-    out->combineMs = s.combineMs;
-    out->traceLaunches = s.traceLaunches;
-    out->combineLaunches = s.combineLaunches;
-    out->bvhNodes = s.scene.kind == HIPPT_SCENE_MESH ? s.scene.numNodes : 0;
-    out->bvhDepth = s.scene.kind == HIPPT_SCENE_MESH ? s.scene.levels : 0;
-    out->numTris = s.scene.kind == HIPPT_SCENE_MESH ? s.scene.numTris : 0;
-    out->numDevices = int(s.ctxs.size());
-    return true;
-} catch (const std::exception &e) {
-    return false;
-} catch (...) {
-    return false;
+extern "C" bool hipptGetStats(hipptStats *out) {
+    return abi_value(kLocked, false, [&]() -> bool {
+        State &s = S();
+        if (!out) return false;
+        std::memset(out, 0, sizeof(*out));
+        const char *err = nullptr;
+        if (s.ready && !sync_locked(&err)) return false;
+        for (Ctx &c : s.ctxs) {
+            unsigned long long v[kStatWords];
+            if (!read_stats(c, v)) return false;
+            out->segments += v[0];
+            out->pixelSamples += v[1] + c.hostSamples;
+            out->nodeVisits += v[2];
+            out->triTests += v[3];
+        }
+        out->traceMs = s.traceMs;
+        out->combineMs = s.combineMs;
+        out->traceLaunches = s.traceLaunches;
+        out->combineLaunches = s.combineLaunches;
+        out->bvhNodes = s.scene.kind == HIPPT_SCENE_MESH ? s.scene.numNodes : 0;
+        out->bvhDepth = s.scene.kind == HIPPT_SCENE_MESH ? s.scene.levels : 0;
+        out->numTris = s.scene.kind == HIPPT_SCENE_MESH ? s.scene.numTris : 0;
+        out->numDevices = int(s.ctxs.size());
+        return true;
+    });
 }
 
-extern "C" int hipptGetCounters(unsigned long long *out, int n) try {
-    std::lock_guard<std::mutex> g(S().mu);
-    State &s = S();
-    if (!out || n <= 0) return 0;
-    n = std::min(n, kStatWords);
-    std::memset(out, 0, sizeof(unsigned long long) * size_t(n));
-    const char *err = nullptr;
-    if (s.ready && !sync_locked(&err)) return 0;
-    for (Ctx &c : s.ctxs) {
-        unsigned long long v[kStatWords];
-        if (!read_stats(c, v)) return 0;
-        v[1] += c.hostSamples;
-        for (int i = 0; i < n; ++i) out[i] += v[i];
-    }
-    return n;
-} catch (const std::exception &e) {
-    return 0;
-} catch (...) {
-    return 0;
+extern "C" int hipptGetCounters(unsigned long long *out, int n) {
+    return abi_value(kLocked, 0, [&]() -> int {
+        State &s = S();
+        if (!out || n <= 0) return 0;
+        n = std::min(n, kStatWords);
+        std::memset(out, 0, sizeof(unsigned long long) * size_t(n));
+        const char *err = nullptr;
+        if (s.ready && !sync_locked(&err)) return 0;
+        for (Ctx &c : s.ctxs) {
+            unsigned long long v[kStatWords];
+            if (!read_stats(c, v)) return 0;
+            v[1] += c.hostSamples;
+            for (int i = 0; i < n; ++i) out[i] += v[i];
+        }
+        return n;
+    });
 }
 
-extern "C" void hipptResetStats(void) try {
-    std::lock_guard<std::mutex> g(S().mu);
-    State &s = S();
-    const char *err = nullptr;
-    if (s.ready) sync_locked(&err);
-    for (Ctx &c : s.ctxs) {
-        (void)hipSetDevice(c.device);
-        (void)hipMemset(c.stats, 0, kStatBytes);
-        c.hostSamples = 0;
-    }
-    s.traceMs = s.combineMs = 0;
-    s.traceLaunches = s.combineLaunches = 0;
-} catch (...) {
-    // an exception must not cross the C ABI (the caller is C or Qt code)
+extern "C" void hipptResetStats(void) {
+    abi_void(kLocked, [&] {
+        State &s = S();
+        const char *err = nullptr;
+        if (s.ready) sync_locked(&err);
+        for (Ctx &c : s.ctxs) {
+            (void)hipSetDevice(c.device);
+            (void)hipMemset(c.stats, 0, kStatBytes);
+            c.hostSamples = 0;
+        }
+        s.traceMs = s.combineMs = 0;
+        s.traceLaunches = s.combineLaunches = 0;
+    });
 }
 
-extern "C" bool hipptSetOption(int key, long long value) try {
-    std::lock_guard<std::mutex> g(S().mu);
+namespace {
+bool set_option_locked(int key, long long value) {
     State &s = S();
     switch (key) {
     case HIPPT_OPT_COUNT_TRAVERSAL: s.knobs.countTraversal = value != 0; return true;
@@ -3473,23 +3383,21 @@ extern "C" bool hipptSetOption(int key, long long value) try {
         return true;
     default: return false;
     }
-} catch (const std::exception &e) {
-    return false;
-} catch (...) {
-    return false;
+}
+}  // namespace
+
+extern "C" bool hipptSetOption(int key, long long value) {
+    return abi_value(kLocked, false, [&] { return set_option_locked(key, value); });
 }
 
-extern "C" int hipptActiveBvhWidth(void) try {
-    std::lock_guard<std::mutex> g(S().mu);
-    return S().activeWidth;
-} catch (const std::exception &e) {
-    return 0;
-} catch (...) {
-    return 0;
+extern "C" int hipptActiveBvhWidth(void) {
+    return abi_value(kLocked, 0, [&]() -> int {
+        return S().activeWidth;
+    });
 }
 
-extern "C" long long hipptGetOption(int key) try {
-    std::lock_guard<std::mutex> g(S().mu);
+namespace {
+long long get_option_locked(int key) {
     State &s = S();
     switch (key) {
     case HIPPT_OPT_COUNT_TRAVERSAL: return s.knobs.countTraversal ? 1 : 0;
@@ -3551,114 +3459,107 @@ extern "C" long long hipptGetOption(int key) try {
             return s.denoiseNs[key - HIPPT_INFO_DENOISE_NS];
         return -1;
     }
-} catch (const std::exception &e) {
-    return -1;
-} catch (...) {
-    return -1;
+}
+}  // namespace
+
+extern "C" long long hipptGetOption(int key) {
+    return abi_value(kLocked, -1LL, [&] { return get_option_locked(key); });
 }
 
-extern "C" int hipptChainAudit(unsigned int *words, int maxWords) try {
-    std::lock_guard<std::mutex> g(S().mu);
-    State &s = S();
-    const char *e = nullptr;
-    if (s.ready && !sync_locked(&e)) return -1;  // closes the open runs (their final flushes) first
-    size_t n = 0;
-    while (n < s.auditWords.size()) {
-        const size_t recs = std::min(s.auditWords[n + 8], hippt::kAuditBatches) + 1u;
-        const size_t len = (1 + recs) * hippt::kAuditWords;
-        if (n + len > size_t(std::max(0, maxWords))) break;
-        n += len;
-    }
-    if (words && n) std::memcpy(words, s.auditWords.data(), n * sizeof(unsigned));
-    s.auditWords.erase(s.auditWords.begin(), s.auditWords.begin() + long(n));
-    return int(n);
-} catch (const std::exception &e) {
-    return -1;
-} catch (...) {
-    return -1;
+extern "C" int hipptChainAudit(unsigned int *words, int maxWords) {
+    return abi_value(kLocked, -1, [&]() -> int {
+        State &s = S();
+        const char *e = nullptr;
+        if (s.ready && !sync_locked(&e)) return -1;  // closes the open runs (their final flushes) first
+        size_t n = 0;
+        while (n < s.auditWords.size()) {
+            const size_t recs = std::min(s.auditWords[n + 8], hippt::kAuditBatches) + 1u;
+            const size_t len = (1 + recs) * hippt::kAuditWords;
+            if (n + len > size_t(std::max(0, maxWords))) break;
+            n += len;
+        }
+        if (words && n) std::memcpy(words, s.auditWords.data(), n * sizeof(unsigned));
+        s.auditWords.erase(s.auditWords.begin(), s.auditWords.begin() + long(n));
+        return int(n);
+    });
 }
 
 extern "C" const char *hipptLastError(void) { return S().error; }
 
 // ---- host BVH builder -----------------------------------------------------------------------------
-extern "C" hipptBvh *hipptBvhBuild(const float *verts, int numTris, float extentHint, const char **err) try {
-    std::unique_ptr<hipptBvh> b(new hipptBvh());
-    std::string msg;
-    hippt::BvhParams params;
-    {
-        std::lock_guard<std::mutex> g(S().mu);
-        params = S().bvh;  // the build options an upload would use
-    }
-    if (!verts || !hippt::build_bvh(verts, numTris, extentHint, b->bvh, msg, params)) {
-        std::lock_guard<std::mutex> g(S().mu);
-        fail(err, msg.empty() ? "null vertex pointer" : msg);
-        return nullptr;
-    }
-    hippt::collapse_bvh4(b->bvh, b->bvh4, params);
-    hippt::order_bvh4_top(b->bvh4, plan::kTopOrderNodes);
-    (void)hippt::quantize_bvh4(b->bvh4, b->bvh4q);  // empty for boxes near +-FLT_MAX
-    return b.release();
-} catch (const std::exception &e) {
-    return (fail_free(err, e.what()), nullptr);
-} catch (...) {
-    return (fail_free(err, "unknown exception"), nullptr);
+extern "C" hipptBvh *hipptBvhBuild(const float *verts, int numTris, float extentHint, const char **err) {
+    return abi_guard(
+        kUnlocked,
+        [&]() -> hipptBvh * {
+            std::unique_ptr<hipptBvh> b(new hipptBvh());
+            std::string msg;
+            hippt::BvhParams params;
+            {
+                std::lock_guard<std::mutex> g(S().mu);
+                params = S().bvh;  // the build options an upload would use
+            }
+            if (!verts || !hippt::build_bvh(verts, numTris, extentHint, b->bvh, msg, params)) {
+                std::lock_guard<std::mutex> g(S().mu);
+                fail(err, msg.empty() ? "null vertex pointer" : msg);
+                return nullptr;
+            }
+            hippt::collapse_bvh4(b->bvh, b->bvh4, params);
+            hippt::order_bvh4_top(b->bvh4, plan::kTopOrderNodes);
+            (void)hippt::quantize_bvh4(b->bvh4, b->bvh4q);  // empty for boxes near +-FLT_MAX
+            return b.release();
+        },
+        [err](const char *what) { return (fail_free(err, what), static_cast<hipptBvh *>(nullptr)); });
 }
 
-extern "C" bool hipptBvhRefit(hipptBvh *b, const float *verts, int numTris, float extentHint, const char **err) try {
-    auto bad = [&](const std::string &m) {
-        std::lock_guard<std::mutex> g(S().mu);
-        return fail(err, m);
-    };
-    if (!b) return bad("null BVH");
-    if (!verts) return bad("null vertex pointer");
-    if (numTris <= 0 || size_t(numTris) != b->bvh.order.size()) return bad("refit: numTris differs from the build's");
-    for (size_t k = 0; k < size_t(numTris) * 9; ++k)
-        if (!std::isfinite(verts[k])) return bad("non-finite primitive coordinate");
-    std::vector<float> boxes(size_t(numTris) * 6);
-    triangle_boxes(verts, numTris, boxes.data());
-    std::string msg;
-    if (!hippt::refit_bvh(b->bvh, b->bvh4, boxes.data(), numTris, extentHint, msg)) return bad(msg);
-    (void)hippt::quantize_bvh4(b->bvh4, b->bvh4q);  // linear in the nodes; empty for boxes near +-FLT_MAX
-    return true;
-} catch (const std::exception &e) {
-    return fail_free(err, e.what());
-} catch (...) {
-    return fail_free(err, "unknown exception");
+extern "C" bool hipptBvhRefit(hipptBvh *b, const float *verts, int numTris, float extentHint, const char **err) {
+    return abi_bool(kUnlocked, err, [&]() -> bool {
+        auto bad = [&](const std::string &m) {
+            std::lock_guard<std::mutex> g(S().mu);
+            return fail(err, m);
+        };
+        if (!b) return bad("null BVH");
+        if (!verts) return bad("null vertex pointer");
+        if (numTris <= 0 || size_t(numTris) != b->bvh.order.size()) return bad("refit: numTris differs from the build's");
+        for (size_t k = 0; k < size_t(numTris) * 9; ++k)
+            if (!std::isfinite(verts[k])) return bad("non-finite primitive coordinate");
+        std::vector<float> boxes(size_t(numTris) * 6);
+        triangle_boxes(verts, numTris, boxes.data());
+        std::string msg;
+        if (!hippt::refit_bvh(b->bvh, b->bvh4, boxes.data(), numTris, extentHint, msg)) return bad(msg);
+        (void)hippt::quantize_bvh4(b->bvh4, b->bvh4q);  // linear in the nodes; empty for boxes near +-FLT_MAX
+        return true;
+    });
 }
 
 extern "C" int hipptBvhNodeCount(const hipptBvh *b) { return b ? int(b->bvh.nodes.size() / hippt::kNodeWords) : 0; }
 extern "C" int hipptBvhDepth(const hipptBvh *b) { return b ? b->bvh.levels : 0; }
-extern "C" void hipptBvhCopy(const hipptBvh *b, uint32_t *nodes, int *triOrder) try {
-    if (!b) return;
-    if (nodes) std::memcpy(nodes, b->bvh.nodes.data(), b->bvh.nodes.size() * sizeof(uint32_t));
-    if (triOrder) std::memcpy(triOrder, b->bvh.order.data(), b->bvh.order.size() * sizeof(int));
-} catch (...) {
-    // an exception must not cross the C ABI (the caller is C or Qt code)
+extern "C" void hipptBvhCopy(const hipptBvh *b, uint32_t *nodes, int *triOrder) {
+    abi_void(kUnlocked, [&] {
+        if (!b) return;
+        if (nodes) std::memcpy(nodes, b->bvh.nodes.data(), b->bvh.nodes.size() * sizeof(uint32_t));
+        if (triOrder) std::memcpy(triOrder, b->bvh.order.data(), b->bvh.order.size() * sizeof(int));
+    });
 }
 extern "C" void hipptBvhFree(hipptBvh *b) { delete b; }
-extern "C" int hipptBvh4NodeCount(const hipptBvh *b) try {
-    return b ? int(b->bvh4.nodes.size() / hippt::kNode4Words) : 0;
-} catch (const std::exception &e) {
-    return 0;
-} catch (...) {
-    return 0;
+extern "C" int hipptBvh4NodeCount(const hipptBvh *b) {
+    return abi_value(kUnlocked, 0, [&]() -> int {
+        return b ? int(b->bvh4.nodes.size() / hippt::kNode4Words) : 0;
+    });
 }
 extern "C" int hipptBvh4Depth(const hipptBvh *b) { return b ? b->bvh4.levels : 0; }
 extern "C" int hipptBvh4StackBound(const hipptBvh *b) { return b ? b->bvh4.stackBound : 0; }
-extern "C" void hipptBvh4Copy(const hipptBvh *b, uint32_t *nodes) try {
-    if (b && nodes) std::memcpy(nodes, b->bvh4.nodes.data(), b->bvh4.nodes.size() * sizeof(uint32_t));
-} catch (...) {
-    // an exception must not cross the C ABI (the caller is C or Qt code)
+extern "C" void hipptBvh4Copy(const hipptBvh *b, uint32_t *nodes) {
+    abi_void(kUnlocked, [&] {
+        if (b && nodes) std::memcpy(nodes, b->bvh4.nodes.data(), b->bvh4.nodes.size() * sizeof(uint32_t));
+    });
 }
-extern "C" int hipptBvh4QNodeCount(const hipptBvh *b) try {
-    return b ? int(b->bvh4q.size() / hippt::kNode4QWords) : 0;
-} catch (const std::exception &e) {
-    return 0;
-} catch (...) {
-    return 0;
+extern "C" int hipptBvh4QNodeCount(const hipptBvh *b) {
+    return abi_value(kUnlocked, 0, [&]() -> int {
+        return b ? int(b->bvh4q.size() / hippt::kNode4QWords) : 0;
+    });
 }
-extern "C" void hipptBvh4QCopy(const hipptBvh *b, uint32_t *nodes) try {
-    if (b && nodes) std::memcpy(nodes, b->bvh4q.data(), b->bvh4q.size() * sizeof(uint32_t));
-} catch (...) {
-    // an exception must not cross the C ABI (the caller is C or Qt code)
+extern "C" void hipptBvh4QCopy(const hipptBvh *b, uint32_t *nodes) {
+    abi_void(kUnlocked, [&] {
+        if (b && nodes) std::memcpy(nodes, b->bvh4q.data(), b->bvh4q.size() * sizeof(uint32_t));
+    });
 }

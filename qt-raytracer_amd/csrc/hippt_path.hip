@@ -18,50 +18,19 @@
 // wavefront shade kernel): it is called under per-lane control flow (hit, depth, material).
 #include "hippt_path.h"
 
-#include <algorithm>
-
-#include "hippt_trace.h"
+#include "hippt_ray_loop.h"
 
 namespace hippt {
 namespace {
-using namespace trace;
-
-__device__ __forceinline__ bool finite3(float x, float y, float z) {
-    return fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY;
-}
+using namespace rayloop;
 
 // LDS_SCENE: the scene copy in LDS (else the tree in global memory, the top of a 4-wide one in LDS);
 // FULL: spheres or materials other than Lambertian present; WIDE: the 4-wide tree.
 template <bool LDS_SCENE, bool FULL, bool WIDE>
 __global__ __launch_bounds__(kMeshBlock) void path_kernel(PathParams P) {
     const QueryParams &Q = P.q;
-    extern __shared__ int lds[];  // LDS scene: nodes at address 0, then stack, primitives
-    constexpr int ldsNodeF4 = WIDE ? kLdsNode4F4 : kLdsNodeF4;  // mesh_lds_bytes layout
-    constexpr bool TOP = WIDE && !LDS_SCENE;
-    int *const stk = LDS_SCENE ? lds + Q.numNodes * ldsNodeF4 * 4 : lds + (TOP ? (Q.topBytes >> 2) : 0u);
-    int *const my = stk + threadIdx.x;
-    const float4 *nodes = Q.nodes, *tris = Q.tris;
-    if (LDS_SCENE) {
-        float4 *sNodes = reinterpret_cast<float4 *>(lds);
-        float4 *sTris = reinterpret_cast<float4 *>(stk + (Q.stackDepth + 1) * kMeshBlock);
-        if (WIDE) {
-            for (int i = threadIdx.x; i < Q.numNodes * kLdsNode4F4; i += kMeshBlock) sNodes[i] = Q.nodes[i];
-        } else {
-            for (int i = threadIdx.x; i < Q.numNodes * 4; i += kMeshBlock)
-                sNodes[(i >> 2) * kLdsNodeF4 + (i & 3)] = Q.nodes[i];
-        }
-        for (int i = threadIdx.x; i < Q.numTris * 3; i += kMeshBlock) sTris[i] = Q.tris[i];
-        __syncthreads();
-        nodes = sNodes;
-        tris = sTris;
-    }
-    if (TOP && Q.topBytes) {
-        float4 *sTop = reinterpret_cast<float4 *>(lds);
-        for (unsigned i = threadIdx.x; i < (Q.topBytes >> 4); i += kMeshBlock) sTop[i] = Q.nodes[i];
-        __syncthreads();
-    }
-    constexpr int nodeF4 = WIDE ? (LDS_SCENE ? kLdsNode4F4 : 8) : (LDS_SCENE ? kLdsNodeF4 : 4);
-    const SpillArea S{Q.spill, (blockIdx.x * unsigned(kMeshBlock) + threadIdx.x) * unsigned(Q.spillCap), Q.stackCap};
+    const Staged sc = stage_scene<LDS_SCENE, WIDE>(Q.nodes, Q.tris, Q.numNodes, Q.numTris, Q.stackDepth, Q.topBytes);
+    const SpillArea S = lane_spill(Q.spill, Q.spillCap, Q.stackCap);
     // shard k: rays [k * per, (k + 1) * per) below numRays, `per` a multiple of 64 (whole lines)
     const unsigned per = ((Q.numRays + kQueryShards * 64u - 1u) / (kQueryShards * 64u)) * 64u;
     unsigned fs = blockIdx.x % kQueryShards, left = kQueryShards;  // the wave's shard; shards not yet found drained
@@ -86,27 +55,19 @@ __global__ __launch_bounds__(kMeshBlock) void path_kernel(PathParams P) {
         while (left && __ballot(need)) {
             const unsigned qi =
                 wave_fetch(need, poolNext, poolEnd, &Q.counter[fs * kQueryCtrStride], Q.chunk, fsCount);
-            if (need && qi != kNone) {
+            if (need && qi != kNone) {  // a new path: segment 0 starts as a ray query's ray
                 need = false;
                 idx = fsBase + qi;
-                const float4 a = Q.rays[2 * size_t(idx)], b = Q.rays[2 * size_t(idx) + 1];
-                rng = P.seeds[idx];
-                r.ox = a.x;
-                r.oy = a.y;
-                r.oz = a.z;
-                r.dx = b.x;
-                r.dy = b.y;
-                r.dz = b.z;
-                tmin = a.w + 0.0f;  // -0 -> +0: the box test's near bound orders as unsigned
-                const float tmax = b.w;
+                float tmax;
+                rng = P.seeds[idx];  // (before the ray: the three loads are in flight together)
+                const bool valid = load_query_ray(Q.rays, idx, r, tmin, tmax);
                 tr = tg = tb = 1.0f;
                 depth = 0;
                 hit0 = false;
+                // begin_query_ray, with the mark of hipptTraceRays' invalid rays (no segment, (0, 0, 0, 0))
+                // in its branch: set after it, the mark costs path_kernel<false, false, false> 2 VGPRs
                 begin(T);
                 T.bestO = -1;  // a hit at exactly t == tmax loses the tie on the id: tmax is exclusive
-                // hipptTraceRays' invalid rays: no segment, (0, 0, 0, 0)
-                const bool valid = finite3(r.ox, r.oy, r.oz) && finite3(r.dx, r.dy, r.dz) && fabsf(tmin) < INFINITY &&
-                                   (r.dx != 0.0f || r.dy != 0.0f || r.dz != 0.0f) && tmin >= 0.0f && tmax > tmin;
                 if (valid) {
                     prepare(r);
                     T.bestT = tmax;
@@ -127,12 +88,7 @@ __global__ __launch_bounds__(kMeshBlock) void path_kernel(PathParams P) {
         if (!__any(idx != kNone)) break;
         if (__any(busy(T))) {
             do {
-                if (WIDE)
-                    traverse_round_wide<nodeF4, false, FULL, false, true, LDS_SCENE, TOP>(
-                        T, r, my, nodes, tris, nvis, ntest, pc, Q.leafExit, Q.nodeExit, S, Q.topBytes, 0u, tmin);
-                else
-                    traverse_round<nodeF4, false, FULL>(T, r, my, nodes, tris, nvis, ntest, pc, Q.leafExit, Q.nodeExit,
-                                                        tmin);
+                traverse_step<LDS_SCENE, FULL, WIDE>(T, r, tmin, sc, Q, S, nvis, ntest, pc);
             } while (__popcll(__ballot(busy(T))) > unsigned(Q.waveThreshold));
         }
         if (idx != kNone && !busy(T)) {  // the segment's traversal is finished: po_mesh_sample's loop body
@@ -149,7 +105,7 @@ __global__ __launch_bounds__(kMeshBlock) void path_kernel(PathParams P) {
                 segs = ++depth;
                 // depth exhausted or absorbed: contributes 0
                 if (depth < P.maxDepth &&
-                    scatter<FULL, false, -1>(r, T.bestT, T.bestI, Q.shade, tris, P.mats, rng, tr, tg, tb, pc)) {
+                    scatter<FULL, false, -1>(r, T.bestT, T.bestI, Q.shade, sc.tris, P.mats, rng, tr, tg, tb, pc)) {
                     finished = false;
                     prepare(r);
                     begin(T);
@@ -167,14 +123,8 @@ __global__ __launch_bounds__(kMeshBlock) void path_kernel(PathParams P) {
 }
 
 using PathFn = void (*)(PathParams);
-template <bool LDS_SCENE, bool FULL>
-PathFn path_fn_wide(bool wide) {
-    return wide ? path_kernel<LDS_SCENE, FULL, true> : path_kernel<LDS_SCENE, FULL, false>;
-}
 PathFn path_fn(const QueryParams &q) {
-    const bool wide = q.wide != 0;
-    if (q.ldsScene) return q.full ? path_fn_wide<true, true>(wide) : path_fn_wide<true, false>(wide);
-    return q.full ? path_fn_wide<false, true>(wide) : path_fn_wide<false, false>(wide);
+    return for_scene_layout(q, [](auto lds, auto full, auto wide) -> PathFn { return path_kernel<lds(), full(), wide()>; });
 }
 
 constexpr int kCameraRaysBlock = 256;
@@ -195,34 +145,15 @@ __global__ __launch_bounds__(kCameraRaysBlock) void camera_rays_kernel(CameraRay
 
 hipError_t launch_path(const PathParams &p, int blocks, hipStream_t s) {
     const QueryParams &q = p.q;
-    const bool lds = q.ldsScene != 0;
-    // the launch's contract with the kernel: what it dereferences is there, the LDS top is whole
-    // nodes of the array, claims are whole waves, records are stored whole
-    if (!q.nodes || !q.tris || !q.shade || !q.counter || !q.rays || !p.mats || !p.seeds || !p.radiance || blocks <= 0 ||
-        q.numRays == 0 || q.chunk < 64 || q.chunk % 64 || q.numRays > (1u << 31) || (q.wide != 0 && q.wide != 1) ||
-        p.maxDepth < 1)
+    if (!query_params_ok(q, blocks)) return hipErrorInvalidValue;
+    // the path's own pointers; rays and records are read and stored whole
+    if (!q.shade || !q.rays || !p.mats || !p.seeds || !p.radiance || p.maxDepth < 1 ||
+        reinterpret_cast<uintptr_t>(q.rays) % 16 || reinterpret_cast<uintptr_t>(p.radiance) % 16)
         return hipErrorInvalidValue;
-    if (reinterpret_cast<uintptr_t>(q.rays) % 16 || reinterpret_cast<uintptr_t>(p.radiance) % 16) return hipErrorInvalidValue;
-    if (q.wide && q.stackCap < 1) return hipErrorInvalidValue;
-    if (q.wide && !q.spill) return hipErrorInvalidValue;
-    if (q.topBytes && (lds || !q.wide || q.topBytes % 128u || q.topBytes > (unsigned(q.numNodes) << 7)))
-        return hipErrorInvalidValue;
-    const PathFn fn = path_fn(q);
-    if (q.wide && (lds || q.topBytes)) {  // the 4-wide traversal reads the LDS nodes at address 0
-        const hipError_t e = check_lds_at_zero(reinterpret_cast<const void *>(fn));
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(fn, dim3(blocks), dim3(kMeshBlock), query_lds_bytes(q), s, p);
-    return hipGetLastError();
+    return launch_ray_kernel(path_fn(q), q, p, blocks, s);
 }
 
-int path_blocks_per_cu(const PathParams &p) {
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, path_fn(p.q), kMeshBlock, query_lds_bytes(p.q)) != hipSuccess ||
-        n <= 0)
-        n = 1;
-    return std::min(n, 8);
-}
+int path_blocks_per_cu(const PathParams &p) { return ray_kernel_blocks_per_cu(path_fn(p.q), p.q); }
 
 hipError_t launch_camera_rays(const CameraRaysParams &p, hipStream_t s) {
     if ((!p.rays && !p.seeds) || p.numRays == 0 || p.numRays > (1u << 31) || reinterpret_cast<uintptr_t>(p.rays) % 16)

@@ -3,6 +3,8 @@
 // hipptOccluded, hipptTraceCamera).
 #pragma once
 
+#include <type_traits>
+
 #include "hippt_device.h"
 
 namespace hippt {
@@ -49,10 +51,48 @@ struct QueryParams {
     float4 *hits;         // 2 float4 per ray (hipptHit)
 };
 
-// any: occlusion (the traversal of a ray ends at its first accepted hit); camera: rays generated in
-// the kernel; hits: hit records (not with any).
-hipError_t launch_query(const QueryParams &q, int blocks, bool any, bool camera, bool hits, hipStream_t s);
+// What a launch of the query kernel computes per ray.
+enum class QueryMode {
+    Closest,     // t[i], prim[i] of the closest hit
+    Any,         // occluded[i]: the traversal of a ray ends at its first accepted hit
+    Camera,      // Closest over rays generated in the kernel
+    Hits,        // hits[2 i], hits[2 i + 1]: the closest hit's record
+    CameraHits,  // Hits over rays generated in the kernel
+};
+constexpr bool query_camera(QueryMode m) { return m == QueryMode::Camera || m == QueryMode::CameraHits; }
+constexpr bool query_hits(QueryMode m) { return m == QueryMode::Hits || m == QueryMode::CameraHits; }
+
+// The launch's contract with a ray-per-lane kernel (query_kernel, path_kernel), as far as every such
+// kernel shares it: what it dereferences is there, the LDS top is whole nodes of the array, claims are
+// whole waves.
+inline bool query_params_ok(const QueryParams &q, int blocks) {
+    if (!q.nodes || !q.tris || !q.counter || blocks <= 0 || q.numRays == 0 || q.chunk < 64 || q.chunk % 64 ||
+        q.numRays > (1u << 31) || (q.wide != 0 && q.wide != 1))
+        return false;
+    if (q.wide && (q.stackCap < 1 || !q.spill)) return false;
+    return !q.topBytes ||
+           (!q.ldsScene && q.wide && q.topBytes % 128u == 0 && q.topBytes <= (unsigned(q.numNodes) << 7));
+}
+
+// The kernel variant of q's scene layout: f(ldsScene, full, wide), each a std::bool_constant.
+template <class F>
+auto for_scene_layout(const QueryParams &q, F f) {
+    using Y = std::true_type;
+    using N = std::false_type;
+    switch ((q.ldsScene ? 4 : 0) | (q.full ? 2 : 0) | (q.wide ? 1 : 0)) {
+    case 0: return f(N{}, N{}, N{});
+    case 1: return f(N{}, N{}, Y{});
+    case 2: return f(N{}, Y{}, N{});
+    case 3: return f(N{}, Y{}, Y{});
+    case 4: return f(Y{}, N{}, N{});
+    case 5: return f(Y{}, N{}, Y{});
+    case 6: return f(Y{}, Y{}, N{});
+    default: return f(Y{}, Y{}, Y{});
+    }
+}
+
+hipError_t launch_query(const QueryParams &q, int blocks, QueryMode mode, hipStream_t s);
 size_t query_lds_bytes(const QueryParams &q);
-int query_blocks_per_cu(const QueryParams &q, bool any, bool camera, bool hits);
+int query_blocks_per_cu(const QueryParams &q, QueryMode mode);
 
 }  // namespace hippt

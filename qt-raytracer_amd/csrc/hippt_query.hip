@@ -18,17 +18,11 @@
 // computed with the oracle's arithmetic; the box test only culls.
 #include "hippt_query.h"
 
-#include <algorithm>
-
-#include "hippt_trace.h"
+#include "hippt_ray_loop.h"
 
 namespace hippt {
 namespace {
-using namespace trace;
-
-__device__ __forceinline__ bool finite3(float x, float y, float z) {
-    return fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY;
-}
+using namespace rayloop;
 
 // The hit record (include/hippt.h hipptHit) of the finished traversal T of ray r, as two float4: the
 // winner's shade record and primitive (leaf-order index T.bestI; `tris` is the LDS copy where the scene
@@ -71,44 +65,20 @@ __device__ __forceinline__ void hit_record(const Trav &T, const Ray &r, const fl
     h1 = float4{nz, u, v, __int_as_float(mw)};
 }
 
+
 // LDS_SCENE: the scene copy in LDS (else the tree in global memory, the top of a 4-wide one in LDS);
-// FULL: spheres present; WIDE: the 4-wide tree; ANY: occlusion; CAMERA: rays from camera_sample;
-// HITS: hit records (hit_record below) in place of (t, prim), not with ANY.
-template <bool LDS_SCENE, bool FULL, bool WIDE, bool ANY, bool CAMERA, bool HITS>
+// FULL: spheres present; WIDE: the 4-wide tree; MODE: hippt_query.h QueryMode.
+template <bool LDS_SCENE, bool FULL, bool WIDE, QueryMode MODE>
 __global__ __launch_bounds__(kMeshBlock) void query_kernel(QueryParams Q) {
-    extern __shared__ int lds[];  // LDS scene: nodes at address 0, then stack, primitives
-    constexpr int ldsNodeF4 = WIDE ? kLdsNode4F4 : kLdsNodeF4;  // mesh_lds_bytes layout
-    constexpr bool TOP = WIDE && !LDS_SCENE;
-    int *const stk = LDS_SCENE ? lds + Q.numNodes * ldsNodeF4 * 4 : lds + (TOP ? (Q.topBytes >> 2) : 0u);
-    int *const my = stk + threadIdx.x;
-    const float4 *nodes = Q.nodes, *tris = Q.tris;
-    if (LDS_SCENE) {
-        float4 *sNodes = reinterpret_cast<float4 *>(lds);
-        float4 *sTris = reinterpret_cast<float4 *>(stk + (Q.stackDepth + 1) * kMeshBlock);
-        if (WIDE) {
-            for (int i = threadIdx.x; i < Q.numNodes * kLdsNode4F4; i += kMeshBlock) sNodes[i] = Q.nodes[i];
-        } else {
-            for (int i = threadIdx.x; i < Q.numNodes * 4; i += kMeshBlock)
-                sNodes[(i >> 2) * kLdsNodeF4 + (i & 3)] = Q.nodes[i];
-        }
-        for (int i = threadIdx.x; i < Q.numTris * 3; i += kMeshBlock) sTris[i] = Q.tris[i];
-        __syncthreads();
-        nodes = sNodes;
-        tris = sTris;
-    }
-    if (TOP && Q.topBytes) {
-        float4 *sTop = reinterpret_cast<float4 *>(lds);
-        for (unsigned i = threadIdx.x; i < (Q.topBytes >> 4); i += kMeshBlock) sTop[i] = Q.nodes[i];
-        __syncthreads();
-    }
-    constexpr int nodeF4 = WIDE ? (LDS_SCENE ? kLdsNode4F4 : 8) : (LDS_SCENE ? kLdsNodeF4 : 4);
-    const SpillArea S{Q.spill, (blockIdx.x * unsigned(kMeshBlock) + threadIdx.x) * unsigned(Q.spillCap), Q.stackCap};
+    constexpr bool ANY = MODE == QueryMode::Any, CAMERA = query_camera(MODE), HITS = query_hits(MODE);
+    const Staged sc = stage_scene<LDS_SCENE, WIDE>(Q.nodes, Q.tris, Q.numNodes, Q.numTris, Q.stackDepth, Q.topBytes);
+    const SpillArea S = lane_spill(Q.spill, Q.spillCap, Q.stackCap);
     // shard k: rays [k * per, (k + 1) * per) below numRays, `per` a multiple of 64 (whole lines)
     const unsigned per = ((Q.numRays + kQueryShards * 64u - 1u) / (kQueryShards * 64u)) * 64u;
     unsigned fs = blockIdx.x % kQueryShards, left = kQueryShards;  // the wave's shard; shards not yet found drained
     unsigned fsBase = min(fs * per, Q.numRays), fsCount = min((fs + 1u) * per, Q.numRays) - fsBase;
     unsigned poolNext = 0, poolEnd = 0;
-    unsigned idx = kNone;   // this lane's ray
+    unsigned idx = kNone;  // this lane's ray
     bool need = true;
     Ray r{};
     float tmin = 0.0f;
@@ -126,34 +96,17 @@ __global__ __launch_bounds__(kMeshBlock) void query_kernel(QueryParams Q) {
                 need = false;
                 idx = fsBase + qi;
                 float tmax;
+                bool valid;
                 if (CAMERA) {
                     uint32_t rng;
                     camera_sample(Q.cam, Q.firstItem + idx, r, rng);
                     tmin = 0.001f;
                     tmax = INFINITY;
+                    valid = query_ray_valid(r, tmin, tmax);
                 } else {
-                    const float4 a = Q.rays[2 * size_t(idx)], b = Q.rays[2 * size_t(idx) + 1];
-                    r.ox = a.x;
-                    r.oy = a.y;
-                    r.oz = a.z;
-                    r.dx = b.x;
-                    r.dy = b.y;
-                    r.dz = b.z;
-                    tmin = a.w + 0.0f;  // -0 -> +0: the box test's near bound orders as unsigned
-                    tmax = b.w;
+                    valid = load_query_ray(Q.rays, idx, r, tmin, tmax);
                 }
-                begin(T);
-                T.bestO = -1;  // a hit at exactly t == tmax loses the tie on the id: tmax is exclusive
-                // rays that are a miss without being traversed (the oracle's arithmetic agrees):
-                // non-finite origin, direction or tmin, NaN tmax, zero direction, tmin < 0, tmax <= tmin
-                const bool valid = finite3(r.ox, r.oy, r.oz) && finite3(r.dx, r.dy, r.dz) && fabsf(tmin) < INFINITY &&
-                                   (r.dx != 0.0f || r.dy != 0.0f || r.dz != 0.0f) && tmin >= 0.0f && tmax > tmin;
-                if (valid) {
-                    prepare(r);
-                    T.bestT = tmax;
-                } else {
-                    T.cur = kDone;
-                }
+                begin_query_ray(T, r, tmax, valid);
             }
             if (__ballot(need)) {  // a requesting lane got none: this shard is drained
                 fs = fs + 1 == kQueryShards ? 0u : fs + 1;
@@ -167,12 +120,7 @@ __global__ __launch_bounds__(kMeshBlock) void query_kernel(QueryParams Q) {
         if (!__any(idx != kNone)) break;
         if (__any(busy(T))) {
             do {
-                if (WIDE)
-                    traverse_round_wide<nodeF4, false, FULL, false, true, LDS_SCENE, TOP>(
-                        T, r, my, nodes, tris, nvis, ntest, pc, Q.leafExit, Q.nodeExit, S, Q.topBytes, 0u, tmin);
-                else
-                    traverse_round<nodeF4, false, FULL>(T, r, my, nodes, tris, nvis, ntest, pc, Q.leafExit, Q.nodeExit,
-                                                        tmin);
+                traverse_step<LDS_SCENE, FULL, WIDE>(T, r, tmin, sc, Q, S, nvis, ntest, pc);
                 if (ANY && T.bestO >= 0) {  // occlusion: any accepted hit answers the ray
                     T.cur = kDone;
                     T.leaf = 0;
@@ -185,7 +133,7 @@ __global__ __launch_bounds__(kMeshBlock) void query_kernel(QueryParams Q) {
             const bool hit = T.bestO >= 0;  // T.bestO: the original id (T.bestI is the leaf-order index)
             if (HITS) {
                 float4 h0{INFINITY, __int_as_float(-1), 0.0f, 0.0f}, h1{0.0f, 0.0f, 0.0f, __int_as_float(-1)};
-                if (hit) hit_record<FULL>(T, r, Q.shade, tris, h0, h1);
+                if (hit) hit_record<FULL>(T, r, Q.shade, sc.tris, h0, h1);
                 float4 *const out = Q.hits + 2 * size_t(idx);
                 out[0] = h0;
                 out[1] = h1;
@@ -203,26 +151,17 @@ __global__ __launch_bounds__(kMeshBlock) void query_kernel(QueryParams Q) {
 
 using QueryFn = void (*)(QueryParams);
 template <bool LDS_SCENE, bool FULL, bool WIDE>
-QueryFn query_fn_mode(bool any, bool camera, bool hits) {
-    if (hits)
-        return camera ? query_kernel<LDS_SCENE, FULL, WIDE, false, true, true>
-                      : query_kernel<LDS_SCENE, FULL, WIDE, false, false, true>;
-    if (camera) return query_kernel<LDS_SCENE, FULL, WIDE, false, true, false>;
-    return any ? query_kernel<LDS_SCENE, FULL, WIDE, true, false, false>
-               : query_kernel<LDS_SCENE, FULL, WIDE, false, false, false>;
+QueryFn query_fn_mode(QueryMode mode) {
+    switch (mode) {
+    case QueryMode::Any: return query_kernel<LDS_SCENE, FULL, WIDE, QueryMode::Any>;
+    case QueryMode::Camera: return query_kernel<LDS_SCENE, FULL, WIDE, QueryMode::Camera>;
+    case QueryMode::Hits: return query_kernel<LDS_SCENE, FULL, WIDE, QueryMode::Hits>;
+    case QueryMode::CameraHits: return query_kernel<LDS_SCENE, FULL, WIDE, QueryMode::CameraHits>;
+    default: return query_kernel<LDS_SCENE, FULL, WIDE, QueryMode::Closest>;
+    }
 }
-template <bool LDS_SCENE, bool FULL>
-QueryFn query_fn_wide(bool wide, bool any, bool camera, bool hits) {
-    return wide ? query_fn_mode<LDS_SCENE, FULL, true>(any, camera, hits)
-                : query_fn_mode<LDS_SCENE, FULL, false>(any, camera, hits);
-}
-QueryFn query_fn(const QueryParams &q, bool any, bool camera, bool hits) {
-    const bool wide = q.wide != 0;
-    if (q.ldsScene)
-        return q.full ? query_fn_wide<true, true>(wide, any, camera, hits)
-                      : query_fn_wide<true, false>(wide, any, camera, hits);
-    return q.full ? query_fn_wide<false, true>(wide, any, camera, hits)
-                  : query_fn_wide<false, false>(wide, any, camera, hits);
+QueryFn query_fn(const QueryParams &q, QueryMode mode) {
+    return for_scene_layout(q, [&](auto lds, auto full, auto wide) { return query_fn_mode<lds(), full(), wide()>(mode); });
 }
 
 }  // namespace
@@ -232,39 +171,17 @@ size_t query_lds_bytes(const QueryParams &q) {
     return mesh_lds_bytes(q.stackDepth, lds ? q.numNodes : 0, lds ? q.numTris : 0, q.wide != 0, q.topBytes);
 }
 
-hipError_t launch_query(const QueryParams &q, int blocks, bool any, bool camera, bool hits, hipStream_t s) {
-    const bool lds = q.ldsScene != 0;
-    // the launch's contract with the kernel: what it dereferences is there, the LDS top is whole
-    // nodes of the array, claims are whole waves
-    if (!q.nodes || !q.tris || !q.counter || blocks <= 0 || q.numRays == 0 || q.chunk < 64 || q.chunk % 64 ||
-        q.numRays > (1u << 31) || (q.wide != 0 && q.wide != 1) || (any && camera))
+hipError_t launch_query(const QueryParams &q, int blocks, QueryMode mode, hipStream_t s) {
+    if (!query_params_ok(q, blocks)) return hipErrorInvalidValue;
+    // the mode's own pointers: two 16-byte stores per hit record, from the shade records
+    if (query_hits(mode) ? (!q.shade || !q.hits || reinterpret_cast<uintptr_t>(q.hits) % 16)
+        : mode == QueryMode::Any ? !q.occluded
+                                 : (!q.t && !q.prim))
         return hipErrorInvalidValue;
-    if (hits) {  // hit records: not with occlusion, the shade records there, two 16-byte stores per record
-        if (any || !q.shade || !q.hits || reinterpret_cast<uintptr_t>(q.hits) % 16) return hipErrorInvalidValue;
-    } else if (any ? !q.occluded : (!q.t && !q.prim)) {
-        return hipErrorInvalidValue;
-    }
-    if (!camera && !q.rays) return hipErrorInvalidValue;
-    if (q.wide && q.stackCap < 1) return hipErrorInvalidValue;
-    if (q.wide && !q.spill) return hipErrorInvalidValue;
-    if (q.topBytes && (lds || !q.wide || q.topBytes % 128u || q.topBytes > (unsigned(q.numNodes) << 7)))
-        return hipErrorInvalidValue;
-    const QueryFn fn = query_fn(q, any, camera, hits);
-    if (q.wide && (lds || q.topBytes)) {  // the 4-wide traversal reads the LDS nodes at address 0
-        const hipError_t e = check_lds_at_zero(reinterpret_cast<const void *>(fn));
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(fn, dim3(blocks), dim3(kMeshBlock), query_lds_bytes(q), s, q);
-    return hipGetLastError();
+    if (!query_camera(mode) && !q.rays) return hipErrorInvalidValue;
+    return launch_ray_kernel(query_fn(q, mode), q, q, blocks, s);
 }
 
-int query_blocks_per_cu(const QueryParams &q, bool any, bool camera, bool hits) {
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, query_fn(q, any, camera, hits), kMeshBlock, query_lds_bytes(q)) !=
-            hipSuccess ||
-        n <= 0)
-        n = 1;
-    return std::min(n, 8);
-}
+int query_blocks_per_cu(const QueryParams &q, QueryMode mode) { return ray_kernel_blocks_per_cu(query_fn(q, mode), q); }
 
 }  // namespace hippt

@@ -1,0 +1,145 @@
+// hippt_ray_loop.h — what the ray-per-lane query kernels share (hippt_query.hip query_kernel,
+// hippt_path.hip path_kernel; the scene staging also hippt_wavefront.hip wf_extend): the scene copy in
+// LDS, the ray load with its validity rule, the traversal round and the launch.  A kernel joins them in
+// its own persistent loop: stage; then claim ray indices from the shard counters, start the claimed
+// rays, traverse until at most waveThreshold lanes are busy, finish the lanes whose traversal has ended.
+//
+// The walk over the shards and the loop itself stay written out in both kernels.  Moved here (the walk
+// as a small struct, the loop as an inlined function over two hooks) they compile to other register
+// counts than the code they replace: the walk +1 or +2 VGPRs in seven 2-wide query kernels, the loop up
+// to +11 in the 2-wide path kernels.  Device code only.
+#pragma once
+
+#include <algorithm>
+
+#include "hippt_query.h"
+#include "hippt_trace.h"
+
+namespace hippt {
+namespace rayloop {
+using namespace trace;
+
+// ---- scene staging ----
+// A block's view of the scene after staging: the nodes and primitives to traverse (the LDS copies where
+// the scene is there) and the lane's slot of the LDS stack.
+struct Staged {
+    const float4 *nodes, *tris;
+    int *my;
+};
+
+// LDS_SCENE: copies the tree and the primitives into LDS (nodes at address 0, then the stack, then the
+// primitives: the mesh_lds_bytes layout); else, a 4-wide tree: copies its first topBytes into LDS at
+// address 0, below the stack.  Every thread of the block calls it (it synchronises).
+template <bool LDS_SCENE, bool WIDE>
+__device__ __forceinline__ Staged stage_scene(const float4 *gNodes, const float4 *gTris, int numNodes, int numTris,
+                                              int stackDepth, unsigned topBytes) {
+    extern __shared__ int lds[];  // LDS scene: nodes at address 0, then stack, primitives
+    constexpr int ldsNodeF4 = WIDE ? kLdsNode4F4 : kLdsNodeF4;  // mesh_lds_bytes layout
+    constexpr bool TOP = WIDE && !LDS_SCENE;
+    int *const stk = LDS_SCENE ? lds + numNodes * ldsNodeF4 * 4 : lds + (TOP ? (topBytes >> 2) : 0u);
+    Staged s{gNodes, gTris, stk + threadIdx.x};
+    if (LDS_SCENE) {
+        float4 *sNodes = reinterpret_cast<float4 *>(lds);
+        float4 *sTris = reinterpret_cast<float4 *>(stk + (stackDepth + 1) * kMeshBlock);
+        if (WIDE) {
+            for (int i = threadIdx.x; i < numNodes * kLdsNode4F4; i += kMeshBlock) sNodes[i] = gNodes[i];
+        } else {
+            for (int i = threadIdx.x; i < numNodes * 4; i += kMeshBlock)
+                sNodes[(i >> 2) * kLdsNodeF4 + (i & 3)] = gNodes[i];
+        }
+        for (int i = threadIdx.x; i < numTris * 3; i += kMeshBlock) sTris[i] = gTris[i];
+        __syncthreads();
+        s.nodes = sNodes;
+        s.tris = sTris;
+    }
+    if (TOP && topBytes) {
+        float4 *sTop = reinterpret_cast<float4 *>(lds);
+        for (unsigned i = threadIdx.x; i < (topBytes >> 4); i += kMeshBlock) sTop[i] = gNodes[i];
+        __syncthreads();
+    }
+    return s;
+}
+
+// This lane's part of the launch's stack spill area (MeshParams::spill).
+__device__ __forceinline__ SpillArea lane_spill(int *spill, int spillCap, int stackCap) {
+    return SpillArea{spill, (blockIdx.x * unsigned(kMeshBlock) + threadIdx.x) * unsigned(spillCap), stackCap};
+}
+
+// ---- ray load ----
+__device__ __forceinline__ bool finite3(float x, float y, float z) {
+    return fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY;
+}
+
+// Rays that are a miss without being traversed (the oracle's arithmetic agrees): non-finite origin,
+// direction or tmin, NaN tmax, zero direction, tmin < 0, tmax <= tmin.
+__device__ __forceinline__ bool query_ray_valid(const Ray &r, float tmin, float tmax) {
+    return finite3(r.ox, r.oy, r.oz) && finite3(r.dx, r.dy, r.dz) && fabsf(tmin) < INFINITY &&
+           (r.dx != 0.0f || r.dy != 0.0f || r.dz != 0.0f) && tmin >= 0.0f && tmax > tmin;
+}
+
+// Ray idx of a query's ray buffer (2 float4 per ray: (origin, tmin) (direction, tmax)); returns whether
+// it is to be traversed (query_ray_valid).
+__device__ __forceinline__ bool load_query_ray(const float4 *rays, unsigned idx, Ray &r, float &tmin, float &tmax) {
+    const float4 a = rays[2 * size_t(idx)], b = rays[2 * size_t(idx) + 1];
+    r.ox = a.x;
+    r.oy = a.y;
+    r.oz = a.z;
+    r.dx = b.x;
+    r.dy = b.y;
+    r.dz = b.z;
+    tmin = a.w + 0.0f;  // -0 -> +0: the box test's near bound orders as unsigned
+    tmax = b.w;
+    return query_ray_valid(r, tmin, tmax);
+}
+
+// Starts the traversal of a query's ray over [tmin, tmax), or, an invalid ray, leaves it finished
+// without a hit.
+__device__ __forceinline__ void begin_query_ray(Trav &T, Ray &r, float tmax, bool valid) {
+    begin(T);
+    T.bestO = -1;  // a hit at exactly t == tmax loses the tie on the id: tmax is exclusive
+    if (valid) {
+        prepare(r);
+        T.bestT = tmax;
+    } else {
+        T.cur = kDone;
+    }
+}
+
+// ---- traversal step ----
+// One speculative while-while round of the queries' traversal (hippt_trace.h), over float nodes of
+// either width, with the ray's own tmin.
+template <bool LDS_SCENE, bool FULL, bool WIDE>
+__device__ __forceinline__ void traverse_step(Trav &T, const Ray &r, float tmin, const Staged &sc, const QueryParams &Q,
+                                              const SpillArea &S, unsigned long long &nvis, unsigned long long &ntest,
+                                              unsigned *pc) {
+    constexpr int nodeF4 = WIDE ? (LDS_SCENE ? kLdsNode4F4 : 8) : (LDS_SCENE ? kLdsNodeF4 : 4);
+    constexpr bool TOP = WIDE && !LDS_SCENE;
+    if (WIDE)
+        traverse_round_wide<nodeF4, false, FULL, false, true, LDS_SCENE, TOP>(
+            T, r, sc.my, sc.nodes, sc.tris, nvis, ntest, pc, Q.leafExit, Q.nodeExit, S, Q.topBytes, 0u, tmin);
+    else
+        traverse_round<nodeF4, false, FULL>(T, r, sc.my, sc.nodes, sc.tris, nvis, ntest, pc, Q.leafExit, Q.nodeExit, tmin);
+}
+
+// ---- launch (host) ----
+// Launches a ray-per-lane kernel over q's scene layout, after the check its 4-wide LDS reads need.
+template <class Params>
+hipError_t launch_ray_kernel(void (*fn)(Params), const QueryParams &q, const Params &p, int blocks, hipStream_t s) {
+    if (q.wide && (q.ldsScene || q.topBytes)) {  // the 4-wide traversal reads the LDS nodes at address 0
+        const hipError_t e = check_lds_at_zero(reinterpret_cast<const void *>(fn));
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(fn, dim3(blocks), dim3(kMeshBlock), query_lds_bytes(q), s, p);
+    return hipGetLastError();
+}
+
+// Resident blocks per CU of such a kernel (at most 8).
+template <class Params>
+int ray_kernel_blocks_per_cu(void (*fn)(Params), const QueryParams &q) {
+    int n = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, kMeshBlock, query_lds_bytes(q)) != hipSuccess || n <= 0) n = 1;
+    return std::min(n, 8);
+}
+
+}  // namespace rayloop
+}  // namespace hippt

@@ -12,6 +12,7 @@
 //                atomics), camera ray, append to the next ray queue.
 // Queue appends are aggregated per 1024-thread block (one atomic per block) into 8 sharded
 // segments; counters also give the exact segment and sample counts without per-wave atomics.
+#include "hippt_ray_loop.h"
 #include "hippt_trace.h"
 #include "hippt_wavefront.h"
 
@@ -114,13 +115,8 @@ __global__ void wf_init(WfParams W) {
 // planes; global memory only).
 template <bool STATS, bool LDS_SCENE, bool FULL, bool WIDE, bool QUANT, bool HALF = false>
 __global__ __launch_bounds__(kMeshBlock) void wf_extend(WfParams W, int cur) {
-    extern __shared__ int lds[];  // LDS scene: nodes at address 0, then stack, primitives
-    constexpr int ldsNodeF4 = WIDE ? kLdsNode4F4 : kLdsNodeF4;  // mesh_lds_bytes layout
     const MeshParams &P = W.mp;
-    // trees in global memory: the top of the tree (P.topBytes) at LDS address 0, then the stack
-    constexpr bool TOP = WIDE && !LDS_SCENE;
-    int *const stk = LDS_SCENE ? lds + P.numNodes * ldsNodeF4 * 4 : lds + (TOP ? (P.topBytes >> 2) : 0u);
-    int *const my = stk + threadIdx.x;
+    constexpr bool TOP = WIDE && !LDS_SCENE;  // trees in global memory: the top of the tree (P.topBytes) in LDS
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         // this iteration's rays = its segments; the paths wf_generate started into this queue
         // = samples (every path of a batch ends within it) and advance the work base; this
@@ -137,28 +133,10 @@ __global__ __launch_bounds__(kMeshBlock) void wf_extend(WfParams W, int cur) {
         if (gen) atomicAdd(&P.stats[1], (unsigned long long)gen);
         W.ctr[ctr_word(kCtrWork)] += gen;
     }
-    const float4 *nodes = P.nodes, *tris = P.tris;
-    if (LDS_SCENE) {
-        float4 *sNodes = reinterpret_cast<float4 *>(lds);
-        float4 *sTris = reinterpret_cast<float4 *>(stk + (P.stackDepth + 1) * kMeshBlock);
-        if (WIDE) {
-            for (int i = threadIdx.x; i < P.numNodes * kLdsNode4F4; i += kMeshBlock) sNodes[i] = P.nodes[i];
-        } else {
-            for (int i = threadIdx.x; i < P.numNodes * 4; i += kMeshBlock)
-                sNodes[(i >> 2) * kLdsNodeF4 + (i & 3)] = P.nodes[i];
-        }
-        for (int i = threadIdx.x; i < P.numTris * 3; i += kMeshBlock) sTris[i] = P.tris[i];
-        __syncthreads();
-        nodes = sNodes;
-        tris = sTris;
-    }
-    if (TOP && P.topBytes) {
-        float4 *sTop = reinterpret_cast<float4 *>(lds);
-        for (unsigned i = threadIdx.x; i < (P.topBytes >> 4); i += kMeshBlock) sTop[i] = P.nodes[i];
-        __syncthreads();
-    }
+    const rayloop::Staged sc =
+        rayloop::stage_scene<LDS_SCENE, WIDE>(P.nodes, P.tris, P.numNodes, P.numTris, P.stackDepth, P.topBytes);
     constexpr int nodeF4 = WIDE ? (QUANT ? 4 : (LDS_SCENE ? kLdsNode4F4 : 8)) : (LDS_SCENE ? kLdsNodeF4 : 4);
-    const SpillArea S{P.spill, (blockIdx.x * unsigned(kMeshBlock) + threadIdx.x) * unsigned(P.spillCap), P.stackCap};
+    const SpillArea S = rayloop::lane_spill(P.spill, P.spillCap, P.stackCap);
     // each wave drains its block's home shard first, then the others in turn (one fetch
     // counter per shard spreads the atomics over kWfShards lines); consecutive lanes take
     // consecutive entries, so the ray and hit arrays are read and written in whole lines
@@ -200,9 +178,10 @@ __global__ __launch_bounds__(kMeshBlock) void wf_extend(WfParams W, int cur) {
         do {
             if (WIDE)
                 traverse_round_wide<nodeF4, STATS, FULL, QUANT, true, LDS_SCENE, TOP, false, false, HALF>(
-                    T, r, my, nodes, tris, nvis, ntest, pc, P.leafExit, P.nodeExit, S, P.topBytes);
+                    T, r, sc.my, sc.nodes, sc.tris, nvis, ntest, pc, P.leafExit, P.nodeExit, S, P.topBytes);
             else
-                traverse_round<nodeF4, STATS, FULL>(T, r, my, nodes, tris, nvis, ntest, pc, P.leafExit, P.nodeExit);
+                traverse_round<nodeF4, STATS, FULL>(T, r, sc.my, sc.nodes, sc.tris, nvis, ntest, pc, P.leafExit,
+                                                    P.nodeExit);
         } while (__popcll(__ballot(busy(T))) > unsigned(P.waveThreshold));
         if (slot != kNone && !busy(T)) {
             W.hit[slot] = make_float2(T.bestT, __int_as_float(T.bestI));
