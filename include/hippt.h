@@ -76,8 +76,23 @@ bool hipptUploadMesh(const float *verts, const int *triMaterial, int numTris, co
                      double vfovDeg, double aperture, double focusDist, const char **errorMessage);
 
 /* Materials of RayTracer.h :473-540.  LAMBERTIAN uses albedo; METAL albedo and fuzz (clamped
- * to <= 1 as Metal's constructor does, :494); DIELECTRIC the index of refraction ir. */
-enum { HIPPT_MAT_LAMBERTIAN = 0, HIPPT_MAT_METAL = 1, HIPPT_MAT_DIELECTRIC = 2 };
+ * to <= 1 as Metal's constructor does, :494); DIELECTRIC the index of refraction ir.
+ *
+ * EMISSIVE is this library's own (the reference has no light): an area light.  albedo[3] holds the
+ * emitted radiance (r, g, b), each finite and >= 0, and may exceed 1; fuzz and ir are ignored but must
+ * be finite.  The material emits on both sides and never scatters.  Path rule, the same in the
+ * renders and in hipptTraceRadiance: a segment whose closest hit is a primitive with an emissive
+ * material ends the path there with L.c = throughput.c * emission.c (one float32 multiply per channel;
+ * at segment 0 the emission itself).  The segment counts as any hit does, no RNG draw is consumed, and
+ * a = 1 if it was segment 0.  The rule applies to every traced segment including the last one the
+ * depth allows (the emission check comes before the depth check, as "Ray Tracing: The Next Week" adds
+ * `emitted` before it asks whether to recurse): maxDepth = 1 shows lights as lit and everything else
+ * black.  Emission (0, 0, 0) is an absorber, so an enclosing emissive sphere is a constant background
+ * colour in place of the sky.  hipptUploadScene rejects a negative emission component, a non-finite
+ * parameter and a kind outside 0..3 before any device call.  A scene without an emissive material
+ * renders the same bytes from the same kernels as before the material existed.  Hit records are
+ * unchanged (matFlags carries the material index); the denoiser's albedo' of an emissive hit is 1. */
+enum { HIPPT_MAT_LAMBERTIAN = 0, HIPPT_MAT_METAL = 1, HIPPT_MAT_DIELECTRIC = 2, HIPPT_MAT_EMISSIVE = 3 };
 typedef struct {
     int kind;
     float albedo[3];

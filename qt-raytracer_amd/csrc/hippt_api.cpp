@@ -283,6 +283,7 @@ struct SceneHost {
     int hybridTop = -1;
     int numNodes4 = 0, levels4 = 0, stackBound4 = 0;
     bool full = false;                          // spheres or non-Lambertian materials
+    bool emissive = false;                      // an emissive material among them (MeshParams::full = 2)
     double lookfrom[3] = {0, 0, 0}, lookat[3] = {0, 0, -1}, vup[3] = {0, 1, 0};
     double vfov = 90, aperture = 0, focus = 1;
     bool rawCamera = false;
@@ -1829,12 +1830,13 @@ void mesh_occupancy(Ctx &c, const plan::Facts &f, const plan::Layout &L) {
     key.topBytes = L.topBytes, key.ldsScene = L.ldsScene, key.full = f.full, key.spills = L.spills;
     if (same_key(c.occKey, key)) return;
     const int ln = L.ldsScene ? L.numNodes : 0, lt = L.ldsScene ? f.numTris : 0, lm = L.ldsScene ? f.numMats : 0;
+    const int full = f.full ? (s.scene.emissive ? 2 : 1) : 0;  // (the key's scene version covers `emissive`)
     c.meshBlocksPerCu[0] =
-        hippt::mesh_blocks_per_cu(false, f.full, L.fmt, L.stackDepth, ln, lt, L.spills, L.topBytes, lm, L.poolWords);
+        hippt::mesh_blocks_per_cu(false, full, L.fmt, L.stackDepth, ln, lt, L.spills, L.topBytes, lm, L.poolWords);
     c.meshBlocksPerCu[1] =
-        hippt::mesh_blocks_per_cu(true, f.full, L.fmt, L.stackDepth, ln, lt, L.spills, L.topBytes, lm, L.poolWords);
+        hippt::mesh_blocks_per_cu(true, full, L.fmt, L.stackDepth, ln, lt, L.spills, L.topBytes, lm, L.poolWords);
     c.meshBlocksPerCuChain = L.poolWords && L.fmt == hippt::kWideFloat
-                                 ? hippt::mesh_blocks_per_cu(false, f.full, L.fmt, L.stackDepth, ln, lt, L.spills,
+                                 ? hippt::mesh_blocks_per_cu(false, full, L.fmt, L.stackDepth, ln, lt, L.spills,
                                                              L.topBytes, lm, L.poolWords, true)
                                  : 0;
     c.occKey = key;
@@ -1881,7 +1883,7 @@ bool fill_mesh_params(Ctx &c, const plan::Facts &f, const plan::Layout &L, const
     p.numTris = f.numTris;
     p.numMats = f.numMats;
     p.ldsScene = L.ldsScene ? 1 : 0;
-    p.full = f.full ? 1 : 0;
+    p.full = f.full ? (s.scene.emissive ? 2 : 1) : 0;
     p.waveThreshold = L.waveThreshold;
     p.chunk = B.chunk[chained ? 1 : 0];
     p.leafExit = L.leafExit;
@@ -2566,14 +2568,18 @@ bool upload_scene_locked(const float *verts, const int *triMaterial, int numTris
         for (int a = 0; a < 4; ++a)
             if (!std::isfinite(spheres[4 * j + a])) return fail(err, "non-finite sphere");
     }
-    bool full = numSpheres > 0;
+    bool full = numSpheres > 0, emissive = false;
     for (int m = 0; m < numMaterials; ++m) {
         const hipptMaterial &mt = materials[m];
-        if (mt.kind < HIPPT_MAT_LAMBERTIAN || mt.kind > HIPPT_MAT_DIELECTRIC) return fail(err, "unknown material kind");
+        if (mt.kind < HIPPT_MAT_LAMBERTIAN || mt.kind > HIPPT_MAT_EMISSIVE) return fail(err, "unknown material kind");
         if (!std::isfinite(mt.albedo[0]) || !std::isfinite(mt.albedo[1]) || !std::isfinite(mt.albedo[2]) ||
             !std::isfinite(mt.fuzz) || !std::isfinite(mt.ir))
             return fail(err, "non-finite material parameter");
+        // an emissive material's albedo words are its radiance: >= 0, may exceed 1
+        if (mt.kind == HIPPT_MAT_EMISSIVE && (mt.albedo[0] < 0.0f || mt.albedo[1] < 0.0f || mt.albedo[2] < 0.0f))
+            return fail(err, "negative emission component");
         full = full || mt.kind != HIPPT_MAT_LAMBERTIAN;
+        emissive = emissive || mt.kind == HIPPT_MAT_EMISSIVE;
     }
     // primitive id p: triangles 0..numTris-1, then spheres (the closest-hit tie order)
     const int numPrims = numTris + numSpheres;
@@ -2675,6 +2681,7 @@ bool upload_scene_locked(const float *verts, const int *triMaterial, int numTris
     sc.numNodes = int(sc.bvh2.nodes.size() / hippt::kNodeWords);
     sc.levels = sc.bvh2.levels;
     sc.full = full;
+    sc.emissive = emissive;
     for (int i = 0; i < 3; ++i) {
         sc.lookfrom[i] = lookfrom[i];
         sc.lookat[i] = lookat[i];

@@ -77,7 +77,8 @@ struct MeshParams {
     int stackDepth;        // LDS stack entries per lane (>= BVH interior levels)
     int numNodes, numTris, numMats;
     int ldsScene;          // 1: copy nodes/triangles/shading into LDS (small scenes)
-    int full;              // 1: spheres or non-Lambertian materials present (general kernel)
+    int full;              // 1: spheres or non-Lambertian materials present (general kernel); 2: an emissive
+                           // material among them (the general kernel's EMIT variants, which alone test for one)
     int waveThreshold;     // shade once fewer than this many lanes still traverse
     unsigned chunk;        // items per queue grab (multiple of 64)
     unsigned leafExit;     // node loop exits once <= leafExit lanes still search for a leaf
@@ -187,8 +188,9 @@ constexpr unsigned kAuditBatches = 256, kAuditWords = 16, kAuditRuns = 64;
 constexpr unsigned kAuditRunWords = (kAuditBatches + 1) * kAuditWords;
 
 
-// Material kinds (RayTracer.h:473-540) and the sphere flag of a shading record.
-enum { kLambertian = 0, kMetal = 1, kDielectric = 2 };
+// Material kinds (RayTracer.h:473-540; kEmissive is this library's) and the sphere flag
+// of a shading record.
+enum { kLambertian = 0, kMetal = 1, kDielectric = 2, kEmissive = 3 };
 constexpr int kShadeSphere = 1 << 30;
 
 // The LDS-scene kernels read the node copy at LDS address 0 (trace::lds_ld4): true when the
@@ -210,7 +212,7 @@ hipError_t launch_chain_flush(const ChainFlushParams &p, hipStream_t s);
 constexpr size_t kRngTableBytes = size_t(4) << 32;
 hipError_t launch_rng_table(uint32_t *table, hipStream_t s);
 // Resident mesh-kernel blocks per CU for a given LDS stack depth and LDS scene size.
-int mesh_blocks_per_cu(bool countTraversal, bool full, int fmt, int stackDepth, int ldsNodes, int ldsTris, bool spill,
+int mesh_blocks_per_cu(bool countTraversal, int full, int fmt, int stackDepth, int ldsNodes, int ldsTris, bool spill,
                        unsigned topBytes = 0, int ldsMats = 0, int poolWords = 0, bool chain = false);
 // The LDS layout's bytes (mesh_lds_bytes), the node formats (kWide*), kMeshBlock and the pool's words
 // per ray: hippt_plan.h.  The limits its planner takes as numbers:

@@ -336,10 +336,13 @@ __device__ __forceinline__ void pool_take(const MeshParams &P, const float *pool
 }
 
 // CHAIN: chained batches (hippt_trace.h; camera-pool kernels over 4-wide float nodes only)
+// EMIT: the scene holds an emissive material (general kernels; MeshParams::full == 2): only these variants test
+// a hit for one, so that scenes without a light run the code they ran before the material existed
 template <bool STATS, bool LDS_SCENE, bool FULL, bool WIDE, bool QUANT, bool SPILL = true, bool POOL = false,
-          bool HYBRID = false, bool HALF = false, bool CHAIN = false>
+          bool HYBRID = false, bool HALF = false, bool CHAIN = false, bool EMIT = false>
 __global__ __launch_bounds__(kMeshBlock, (FULL || WIDE) ? HIPPT_WIDE_WAVES_PER_EU : HIPPT_MESH_WAVES_PER_EU) HIPPT_SGPR_ATTR void mesh_kernel(MeshParams P) {
     static_assert(!QUANT || (WIDE && !LDS_SCENE), "quantized nodes: 4-wide global-memory traversal only");
+    static_assert(!EMIT || FULL, "an emissive material makes a scene a general one");
     static_assert(!CHAIN || (POOL && WIDE && !QUANT && !HYBRID && !HALF && !STATS), "chained batches: pool kernels");
 #ifdef HIPPT_DEBUG_TIMELINE
     const unsigned tlw = blockIdx.x * 4u + (threadIdx.x >> 6);
@@ -749,6 +752,8 @@ __global__ __launch_bounds__(kMeshBlock, (FULL || WIDE) ? HIPPT_WIDE_WAVES_PER_E
             } else if (T.bestI < 0) {
                 sky(r, tr, tg, tb, Lr, Lg, Lb);
                 finished = true;
+            } else if (EMIT && emitted(T.bestI, shade, mats, tr, tg, tb, Lr, Lg, Lb)) {
+                finished = true;  // ends at a light, whatever the depth
             } else if (++depth >= P.maxDepth) {
                 finished = true;  // depth exhausted: contributes 0 (RayTracer.h:582-583)
             } else if (scatter<FULL, STATS, CHAIN ? kRiusTail : -1>(r, T.bestT, T.bestI, shade, tris, mats, rng, tr, tg,
@@ -910,33 +915,41 @@ using MeshFn = void (*)(MeshParams);
 // 4-wide trees whose stack bound fits the LDS capacity run a variant without the spill/refill
 // code (timed builds; the counting builds keep one variant, the results are the same)
 // (the camera-ray pool: 4-wide float-node kernels)
-template <bool STATS, bool FULL, bool SPILL, bool POOL>
+// (E: the EMIT variants, general kernels only)
+template <bool STATS, bool FULL, bool SPILL, bool POOL, bool E>
 static MeshFn mesh_fn_wide(bool lds, int fmt) {
-    if (lds) return mesh_kernel<STATS, true, FULL, true, false, SPILL, POOL>;
-    if (fmt == kWideHybrid) return mesh_kernel<STATS, false, FULL, true, true, SPILL, false, true>;
-    if (fmt == kWideHalf) return mesh_kernel<STATS, false, FULL, true, false, SPILL, POOL, false, true>;
-    return fmt == kWideQuant ? mesh_kernel<STATS, false, FULL, true, true, SPILL>
-                             : mesh_kernel<STATS, false, FULL, true, false, SPILL, POOL>;
+    if (lds) return mesh_kernel<STATS, true, FULL, true, false, SPILL, POOL, false, false, false, E>;
+    if (fmt == kWideHybrid) return mesh_kernel<STATS, false, FULL, true, true, SPILL, false, true, false, false, E>;
+    if (fmt == kWideHalf) return mesh_kernel<STATS, false, FULL, true, false, SPILL, POOL, false, true, false, E>;
+    return fmt == kWideQuant ? mesh_kernel<STATS, false, FULL, true, true, SPILL, false, false, false, false, E>
+                             : mesh_kernel<STATS, false, FULL, true, false, SPILL, POOL, false, false, false, E>;
 }
-template <bool STATS, bool FULL>
+template <bool STATS, bool FULL, bool E = false>
 static MeshFn mesh_fn_fmt(bool lds, int fmt, bool spill, bool pool) {
-    if (fmt == kWide2) return lds ? mesh_kernel<STATS, true, FULL, false, false> : mesh_kernel<STATS, false, FULL, false, false>;
+    if (fmt == kWide2)
+        return lds ? mesh_kernel<STATS, true, FULL, false, false, true, false, false, false, false, E>
+                   : mesh_kernel<STATS, false, FULL, false, false, true, false, false, false, false, E>;
     if (STATS || spill)
-        return pool ? mesh_fn_wide<STATS, FULL, true, true>(lds, fmt) : mesh_fn_wide<STATS, FULL, true, false>(lds, fmt);
-    return pool ? mesh_fn_wide<STATS, FULL, false, true>(lds, fmt) : mesh_fn_wide<STATS, FULL, false, false>(lds, fmt);
+        return pool ? mesh_fn_wide<STATS, FULL, true, true, E>(lds, fmt) : mesh_fn_wide<STATS, FULL, true, false, E>(lds, fmt);
+    return pool ? mesh_fn_wide<STATS, FULL, false, true, E>(lds, fmt) : mesh_fn_wide<STATS, FULL, false, false, E>(lds, fmt);
 }
 // chained batches (MeshParams::chainCtl): the timed camera-pool kernels over 4-wide float nodes
-template <bool FULL, bool SPILL>
+template <bool FULL, bool SPILL, bool E = false>
 static MeshFn mesh_fn_chain(bool lds) {
-    return lds ? mesh_kernel<false, true, FULL, true, false, SPILL, true, false, false, true>
-               : mesh_kernel<false, false, FULL, true, false, SPILL, true, false, false, true>;
+    return lds ? mesh_kernel<false, true, FULL, true, false, SPILL, true, false, false, true, E>
+               : mesh_kernel<false, false, FULL, true, false, SPILL, true, false, false, true, E>;
 }
-static MeshFn mesh_fn(bool count, bool lds, bool full, int fmt, bool spill, bool pool, bool chain = false) {
+// full: MeshParams::full (0 Lambertian triangles, 1 general, 2 general with an emissive material)
+static MeshFn mesh_fn(bool count, bool lds, int full, int fmt, bool spill, bool pool, bool chain = false) {
     if (chain) {
         if (count || fmt != kWideFloat || !pool) return nullptr;
+        if (full == 2) return spill ? mesh_fn_chain<true, true, true>(lds) : mesh_fn_chain<true, false, true>(lds);
         if (full) return spill ? mesh_fn_chain<true, true>(lds) : mesh_fn_chain<true, false>(lds);
         return spill ? mesh_fn_chain<false, true>(lds) : mesh_fn_chain<false, false>(lds);
     }
+    if (full == 2)
+        return count ? mesh_fn_fmt<true, true, true>(lds, fmt, spill, pool)
+                     : mesh_fn_fmt<false, true, true>(lds, fmt, spill, pool);
     if (count)
         return full ? mesh_fn_fmt<true, true>(lds, fmt, spill, pool) : mesh_fn_fmt<true, false>(lds, fmt, spill, pool);
     return full ? mesh_fn_fmt<false, true>(lds, fmt, spill, pool) : mesh_fn_fmt<false, false>(lds, fmt, spill, pool);
@@ -970,7 +983,8 @@ hipError_t launch_mesh(const MeshParams &p, int blocks, bool countTraversal, hip
                                         lds ? p.numMats : 0, p.poolWords);
     if (pool && p.poolOffset != bytes - (size_t(p.poolWords) * 64 + kWaveWords) * (kMeshBlock / 64) * sizeof(float))
         return hipErrorInvalidValue;
-    const MeshFn fn = mesh_fn(countTraversal, lds, p.full != 0, p.wide, p.spill != nullptr, pool, chain);
+    if (p.full < 0 || p.full > 2) return hipErrorInvalidValue;
+    const MeshFn fn = mesh_fn(countTraversal, lds, p.full, p.wide, p.spill != nullptr, pool, chain);
     if (!fn) return hipErrorInvalidValue;
     if (p.wide && (lds || p.topBytes || pool)) {
         const hipError_t e = check_lds_at_zero(reinterpret_cast<const void *>(fn));
@@ -998,7 +1012,7 @@ hipError_t launch_chain_flush(const ChainFlushParams &p, hipStream_t s) {
     return hipGetLastError();
 }
 
-int mesh_blocks_per_cu(bool countTraversal, bool full, int fmt, int stackDepth, int ldsNodes, int ldsTris, bool spill,
+int mesh_blocks_per_cu(bool countTraversal, int full, int fmt, int stackDepth, int ldsNodes, int ldsTris, bool spill,
                        unsigned topBytes, int ldsMats, int poolWords, bool chain) {
     int n = 0;
     const bool lds = ldsNodes > 0;

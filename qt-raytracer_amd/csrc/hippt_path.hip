@@ -8,7 +8,7 @@
 // LDS top of a global tree, the per-lane LDS stack with its spill area.  A lane keeps its path until
 // the path ends: a traversal that finishes on a hit within the depth limit scatters (the renderer's
 // scatter, hippt_trace.h) and the lane goes on traversing the scattered ray with the renderer's tmin
-// 0.001 and no tmax; only a finished path (sky, depth limit, absorbed, invalid ray) stores its result
+// 0.001 and no tmax; only a finished path (sky, a light, depth limit, absorbed, invalid ray) stores its result
 // and asks for a new ray.  Segment 0 alone uses the ray's own tmin and exclusive tmax, started as the
 // query kernel starts a ray.
 //
@@ -103,8 +103,9 @@ __global__ __launch_bounds__(kMeshBlock) void path_kernel(PathParams P) {
             } else {
                 hit0 = true;
                 segs = ++depth;
-                // depth exhausted or absorbed: contributes 0
-                if (depth < P.maxDepth &&
+                if (FULL && emitted(T.bestI, Q.shade, P.mats, tr, tg, tb, L0, L1, L2)) {
+                    // ends at a light with throughput x emission, whatever the depth
+                } else if (depth < P.maxDepth &&  // depth exhausted or absorbed: contributes 0
                     scatter<FULL, false, -1>(r, T.bestT, T.bestI, Q.shade, sc.tris, P.mats, rng, tr, tg, tb, pc)) {
                     finished = false;
                     prepare(r);

@@ -858,6 +858,23 @@ __device__ __forceinline__ float rius_capped(uint32_t &rng, float &rx, float &ry
     return -1.0f;
 }
 
+// The closest hit `prim` is a light (a kEmissive material): the path ends there with
+// L = throughput * emission (the material's albedo words), whatever the depth; the caller asks before
+// its depth check.  No RNG draw, no wave-level operation.  Reads the shade record's material word and
+// mats[2m], which scatter reads for every other hit.  General (FULL) kernels only: a scene that holds
+// an emissive material is never given to a Lambertian specialisation; the megakernel and the wavefront
+// shade kernel call it in their EMIT variants alone (MeshParams::full == 2).
+__device__ __forceinline__ bool emitted(int prim, const float4 *shade, const float4 *mats, float tr, float tg,
+                                        float tb, float &L0, float &L1, float &L2) {
+    const int m = __float_as_int(shade[prim].w) & ~kShadeSphere;
+    const float4 m0 = mats[2 * m];
+    if (__float_as_int(m0.w) != kEmissive) return false;
+    L0 = tr * m0.x;
+    L1 = tg * m0.y;
+    L2 = tb * m0.z;
+    return true;
+}
+
 // Scatter at the closest hit (ray_color :585-590 + the material's scatter, :473-540) of
 // primitive `prim` at t.  The ray becomes the scattered ray and the throughput takes the
 // attenuation; false = absorbed (Metal below the surface), which contributes 0.  FULL=false

@@ -201,7 +201,8 @@ __global__ __launch_bounds__(kMeshBlock) void wf_extend(WfParams W, int cur) {
 // Shade and generate keep every shard an independent pipeline: block b works on shard
 // b % kWfShards of queue cur and appends to the same shard of the other queue, so a shard never
 // holds more than its ceil(slots / kWfShards) entries.
-template <bool FULL>
+// EMIT: the scene holds an emissive material (MeshParams::full == 2)
+template <bool FULL, bool EMIT = false>
 __global__ __launch_bounds__(kWfBlock) void wf_shade(WfParams W, int cur) {
     static_assert(kWfBlock / 64 + 1 <= 65, "one LDS array serves both appends");
     __shared__ unsigned lds[65];
@@ -237,6 +238,8 @@ __global__ __launch_bounds__(kWfBlock) void wf_shade(WfParams W, int cur) {
         if (tri < 0) {
             sky(q.r, q.tr, q.tg, q.tb, L0, L1, L2);
             finished = true;
+        } else if (EMIT && emitted(tri, P.shade, P.mats, q.tr, q.tg, q.tb, L0, L1, L2)) {
+            finished = true;  // ends at a light, whatever the depth
         } else if (++q.depth >= P.maxDepth) {
             finished = true;
         } else if (scatter<FULL, false, -1>(q.r, h.x, tri, P.shade, P.tris, P.mats, q.rng, q.tr, q.tg, q.tb, nullptr,
@@ -353,7 +356,8 @@ hipError_t wf_launch_extend(const WfParams &W, int cur, int blocks, bool countTr
 }
 
 hipError_t wf_launch_shade(const WfParams &W, int cur, hipStream_t s) {
-    hipLaunchKernelGGL(W.mp.full ? wf_shade<true> : wf_shade<false>, dim3(shard_grid(W)), dim3(kWfBlock), 0, s, W, cur);
+    const auto shade = W.mp.full == 2 ? wf_shade<true, true> : W.mp.full ? wf_shade<true> : wf_shade<false>;
+    hipLaunchKernelGGL(shade, dim3(shard_grid(W)), dim3(kWfBlock), 0, s, W, cur);
     return hipGetLastError();
 }
 

@@ -26,6 +26,9 @@ LIB_PATH = os.path.join(os.path.dirname(_HERE), "libhippt.so")
 SCENE_SPHERE4 = 0
 SCENE_MESH = 1
 
+# hipptMaterial kinds (include/hippt.h); MAT_EMISSIVE: albedo holds the emitted radiance
+MAT_LAMBERTIAN, MAT_METAL, MAT_DIELECTRIC, MAT_EMISSIVE = 0, 1, 2, 3
+
 OPT_COUNT_TRAVERSAL = 1
 OPT_WAVE_THRESHOLD = 2
 OPT_SCRATCH_MB = 3
@@ -839,7 +842,8 @@ class PathTracer:
     def gbuffer(self, frame: int = 0) -> dict:
         """The guide buffers of sample `frame`'s camera rays, each (H, W) with row 0 = v = 0: depth (t;
         inf over the sky), prim (-1), normal (H, W, 3) faced towards the camera (0), albedo (H, W, 3)
-        of the hit's material as uploaded (0 over the sky), material (the index; -1)."""
+        of the hit's material as uploaded (0 over the sky; of a MAT_EMISSIVE hit its emission, which may
+        exceed 1), material (the index; -1)."""
         if self._albedo is None:
             raise HipptError("gbuffer: no scene uploaded through this PathTracer")
         hits = self.traceCameraHits(frame)

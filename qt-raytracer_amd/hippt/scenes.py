@@ -42,6 +42,7 @@ SCENE_MAGIC = 0x53505448      # v1: Lambertian triangles
 SCENE_MAGIC_V2 = 0x32505448   # v2: triangles, spheres, material kinds
 
 MAT_LAMBERTIAN, MAT_METAL, MAT_DIELECTRIC = 0, 1, 2
+MAT_EMISSIVE = 3  # this library's own (include/hippt.h): albedo holds the emitted radiance, may exceed 1
 # == hipptMaterial (include/hippt.h) == po_material (oracle/pt_oracle.h)
 MATERIAL_DTYPE = np.dtype([("kind", "<i4"), ("albedo", "<f4", (3,)), ("fuzz", "<f4"), ("ir", "<f4")])
 
@@ -277,6 +278,31 @@ def voxel_scene(n: int = 6) -> Scene:
     return Scene(name=f"voxel{n}", verts=verts, tri_mat=tri_mat,
                  albedo=np.asarray([WHITE, GREEN, RED], dtype=np.float32),
                  lookfrom=(float(2 * n + 4), float(n + 2), float(2 * n + 6)), lookat=(0.0, 1.0, 0.0), vfov=40.0)
+
+
+def cornell_lit(base: str = "cornell_mixed", sphere: bool = True) -> Scene:
+    """`cornell34` or `cornell_mixed` with the Cornell box's lamp: an emissive quad (15, 15, 15) just
+    under the ceiling and, with `sphere`, a small emissive sphere (4, 2, 1).  Not in SCENES (the
+    reference harness does not know the emissive kind)."""
+    sc = {"cornell34": cornell34, "cornell_mixed": cornell_mixed}[base]()
+    mats = sc.materials()
+    k = len(mats)
+    lamp = _quad((213, 554, 227), (343, 554, 227), (343, 554, 332), (213, 554, 332))
+    sc.name = f"{base}_lit"
+    sc.verts = np.ascontiguousarray(
+        np.concatenate([sc.verts, np.asarray(lamp, dtype=np.float64).astype(np.float32)], axis=0))
+    sc.tri_mat = np.concatenate([sc.tri_mat, np.full(len(lamp), k, np.int32)]).astype(np.int32)
+    new = [(MAT_EMISSIVE, (15.0, 15.0, 15.0))]
+    if sphere:
+        sc.spheres = np.concatenate([np.asarray(sc.spheres, np.float32).reshape(-1, 4),
+                                     np.asarray([(90.0, 400.0, 400.0, 40.0)], np.float32)], axis=0)
+        sc.sph_mat = np.concatenate([np.asarray(sc.sph_mat, np.int32), np.asarray([k + 1], np.int32)])
+        new.append((MAT_EMISSIVE, (4.0, 2.0, 1.0)))
+    sc.albedo = np.concatenate([mats["albedo"], np.asarray([m[1] for m in new], np.float32)], axis=0)
+    sc.mat_kind = np.concatenate([mats["kind"], np.asarray([m[0] for m in new], np.int32)])
+    sc.fuzz = np.concatenate([mats["fuzz"], np.zeros(len(new), np.float32)])
+    sc.ir = np.concatenate([mats["ir"], np.ones(len(new), np.float32)])
+    return sc
 
 
 SCENES = {"cornell34": cornell34, "blob70k": blob70k, "random_scene": random_scene, "cornell_mixed": cornell_mixed}

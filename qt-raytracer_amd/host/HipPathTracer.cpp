@@ -1,6 +1,9 @@
 // HipPathTracer.cpp — see HipPathTracer.h.
 #include "HipPathTracer.h"
 
+#include <algorithm>
+#include <cstdio>
+
 HipPathTracer::~HipPathTracer() { cudaPathTracerShutdown(); }
 
 bool HipPathTracer::fail(const char *err, const char *fallback) {
@@ -29,7 +32,7 @@ bool HipPathTracer::renderFrame(int maxDepth) {
 
 bool HipPathTracer::loadMeshFile(const std::string &path, const std::vector<float> &albedo,
                                  const double lookfrom[3], const double lookat[3], const double vup[3],
-                                 double vfovDeg, double aperture, double focus) {
+                                 double vfovDeg, double aperture, double focus, const std::string &emit) {
     hipptMesh mesh;
     const char *err = nullptr;
     if (!hipptReadMesh(path.c_str(), &mesh, &err)) return fail(err, "mesh read failed");
@@ -39,6 +42,29 @@ bool HipPathTracer::loadMeshFile(const std::string &path, const std::vector<floa
     bool ok = int(alb.size()) == 3 * mesh.numGroups;
     if (!ok) {
         m_lastError = "albedo needs 3 floats per mesh group";
+    } else if (!emit.empty()) {
+        // NAME=r,g,b[;NAME=r,g,b...]: those groups emit; the scene goes through hipptUploadScene
+        std::vector<hipptMaterial> mats;
+        for (int g = 0; g < mesh.numGroups; ++g)
+            mats.push_back(hipptMaterial{HIPPT_MAT_LAMBERTIAN, {alb[3 * g], alb[3 * g + 1], alb[3 * g + 2]}, 0.0f, 1.0f});
+        for (size_t at = 0; ok && at < emit.size();) {
+            const size_t end = std::min(emit.find(';', at), emit.size());
+            const std::string item = emit.substr(at, end - at);
+            at = end + 1;
+            const size_t eq = item.rfind('=');
+            float c[3];
+            int g = 0;
+            while (eq != std::string::npos && g < mesh.numGroups && item.compare(0, eq, mesh.groupNames[g]) != 0) ++g;
+            ok = eq != std::string::npos && g < mesh.numGroups &&
+                 std::sscanf(item.c_str() + eq + 1, "%f,%f,%f", &c[0], &c[1], &c[2]) == 3;
+            if (ok) mats[size_t(g)] = hipptMaterial{HIPPT_MAT_EMISSIVE, {c[0], c[1], c[2]}, 0.0f, 1.0f};
+            else m_lastError = "emit needs NAME=r,g,b of a usemtl group of the mesh: " + item;
+        }
+        if (ok) {
+            ok = hipptUploadScene(mesh.verts, mesh.triGroup, mesh.numTris, nullptr, nullptr, 0, mats.data(), mesh.numGroups,
+                                  lookfrom, lookat, vup, vfovDeg, aperture, focus, &err);
+            if (!ok) fail(err, "scene upload failed");
+        }
     } else {
         ok = hipptUploadMesh(mesh.verts, mesh.triGroup, mesh.numTris, alb.data(), mesh.numGroups, lookfrom, lookat, vup,
                              vfovDeg, aperture, focus, &err);

@@ -30,9 +30,12 @@ public:
 
     // --- extensions ----------------------------------------------------------------------------
     // Triangle mesh from an OBJ/PLY file, one Lambertian material per group (albedo: 3 floats per
-    // group; empty = white 0.73), camera as RayTracer.h Camera parameters.
+    // group; empty = white 0.73), camera as RayTracer.h Camera parameters.  emit: "NAME=r,g,b[;NAME=r,g,b...]"
+    // makes those OBJ `usemtl` groups area lights (HIPPT_MAT_EMISSIVE with that radiance; the scene is then
+    // uploaded through hipptUploadScene).
     bool loadMeshFile(const std::string &path, const std::vector<float> &albedo, const double lookfrom[3],
-                      const double lookat[3], const double vup[3], double vfovDeg, double aperture, double focus);
+                      const double lookat[3], const double vup[3], double vfovDeg, double aperture, double focus,
+                      const std::string &emit = std::string());
     bool uploadScene(const std::vector<float> &verts, const std::vector<int> &triMaterial,
                      const std::vector<float> &spheres, const std::vector<int> &sphereMaterial,
                      const std::vector<hipptMaterial> &materials, const double lookfrom[3], const double lookat[3],

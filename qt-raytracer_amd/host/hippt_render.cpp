@@ -3,7 +3,7 @@
 // RayTracerFboItem.cpp:516-575) without the scene graph.
 //
 //   hippt_render [--backend cuda|vulkan|gl] [--mesh FILE.obj|.ply] [--albedo r,g,b[;r,g,b...]]
-//                [--width W] [--height H] [--spp N] [--depth D] [--per-frame] [--present]
+//                [--emit NAME=r,g,b[;NAME=r,g,b...]] [--width W] [--height H] [--spp N] [--depth D] [--per-frame] [--present]
 //                [--out FILE] [--ppm FILE.ppm] [--pick X,Y] [--denoise PASSES]
 //                [--radiance-in FILE|camera --radiance-out FILE]
 //
@@ -12,6 +12,7 @@
 // loop).  With --mesh: the file's triangles (hipptReadMesh) under the Cornell camera, all N
 // frames in one renderFrames call, or one call per frame with --per-frame, or through the
 // non-blocking hand-off with --present.
+// --emit (with --mesh): the named OBJ `usemtl` groups are area lights of that radiance (HIPPT_MAT_EMISSIVE).
 // --backend vulkan: HipVulkanPathTracer, one renderFrame(depth) per frame (the app's "vulkan"
 // branch, RayTracerFboItem.cpp:576-600).  --backend gl: HipGpuPathTracer, initialize + resize,
 // then renderFrame(N, depth) once (or per frame with --per-frame), as the GL branch calls it.
@@ -44,6 +45,7 @@ namespace {
 int usage() {
     std::fprintf(stderr,
                  "usage: hippt_render [--backend cuda|vulkan|gl] [--mesh FILE] [--albedo r,g,b[;...]] [--width W]\n"
+                 "                    [--emit NAME=r,g,b[;...]]\n"
                  "                    [--height H] [--spp N] [--depth D] [--per-frame] [--present] [--out FILE]\n"
                  "                    [--ppm FILE.ppm] [--pick X,Y] [--update-mesh FILE] [--denoise PASSES]\n"
                  "                    [--radiance-in FILE|camera --radiance-out FILE]\n");
@@ -67,7 +69,7 @@ std::vector<float> parse_floats(const std::string &s) {
 }  // namespace
 
 int main(int argc, char **argv) {
-    std::string mesh, out, ppm, albedoArg, pickArg, updateMesh, radianceIn, radianceOut, backend = "cuda";
+    std::string mesh, out, ppm, albedoArg, emitArg, pickArg, updateMesh, radianceIn, radianceOut, backend = "cuda";
     int width = 320, height = 180, spp = 16, depth = 8, denoise = -1;
     bool perFrame = false, present = false;
     for (int i = 1; i < argc; ++i) {
@@ -80,6 +82,7 @@ int main(int argc, char **argv) {
         else if (a == "--backend") backend = v;
         else if (a == "--mesh") mesh = v;
         else if (a == "--albedo") albedoArg = v;
+        else if (a == "--emit") emitArg = v;
         else if (a == "--width") width = std::atoi(v);
         else if (a == "--height") height = std::atoi(v);
         else if (a == "--spp") spp = std::atoi(v);
@@ -98,7 +101,7 @@ int main(int argc, char **argv) {
     if (!mesh.empty()) {
         // the scene is the library's (shared by every interface)
         const double from[3] = {278, 278, -800}, at[3] = {278, 278, 0}, up[3] = {0, 1, 0};
-        if (!tracer.loadMeshFile(mesh, parse_floats(albedoArg), from, at, up, 40.0, 0.0, 10.0)) {
+        if (!tracer.loadMeshFile(mesh, parse_floats(albedoArg), from, at, up, 40.0, 0.0, 10.0, emitArg)) {
             std::fprintf(stderr, "hippt_render: %s\n", tracer.lastError().c_str());
             return 1;
         }
