@@ -127,7 +127,13 @@ typedef struct {
 bool hipptReadMesh(const char *path, hipptMesh *out, const char **errorMessage);
 void hipptFreeMesh(hipptMesh *mesh);
 
-/* Optional: replace the camera by a prebuilt one (used as-is, whatever the aspect). */
+/* Optional: replace the camera by a prebuilt one (used as-is, whatever the aspect).
+ * Known limit: the BVH's boxes are padded for rays that start within M of the origin, M the largest
+ * |coordinate| of the scene and of the camera the scene was uploaded with.  hipptRenderFrames covers a
+ * camera moved out to 32 M (the host model of the box test, tests/test_far_rays_cpu.py, loses nothing up
+ * to there and loses first hits from 48 M on); beyond that a render may lose
+ * surfaces.  Remedy: upload the scene with the far camera, which sizes the pad for it.  The ray and
+ * path queries below, the camera queries included, have no such limit. */
 bool hipptSetCamera(const hipptCamera *camera, const char **errorMessage);
 
 /* ---- vertex updates (animated or edited meshes) ------------------------------------------------ */
@@ -204,7 +210,14 @@ bool hipptResetAccumulation(const char **errorMessage);
  * arithmetic, and the BVH only culls.  A call runs after the work already queued on its device,
  * waits for its own work only and leaves pending asynchronous frames, the image and the counters of
  * hipptGetStats untouched.  A ray with a non-finite origin, direction or tmin, a NaN tmax, an
- * all-zero direction, tmin < 0 or tmax <= tmin is a miss (tmax may be +inf). */
+ * all-zero direction, tmin < 0 or tmax <= tmin is a miss (tmax may be +inf).
+ * Every other ray is answered exactly within this domain, which a caller can check (M: the largest
+ * |coordinate| of the uploaded scene and its camera; omax, dmax: the largest |component| of the ray's
+ * origin and direction; components of the direction may be zero or of any smaller size):
+ *   omax <= 2^20 M  with  2^-20 <= dmax <= 2^20,   or   omax <= 8 M  with  2^-100 <= dmax <= 2^80.
+ * tests/test_gpu_far_rays.py covers both to their edges.  Outside it a query may miss a surface.  One
+ * exception inside it: a triangle whose corners lie on one line has no hit to report; the renderer's
+ * arithmetic can still accept one from rounding noise, and a query may or may not. */
 enum { HIPPT_RAYS_DEVICE = 1 };   /* flags: every pointer of the call is device memory */
 
 /* rays: numRays x 8 floats: origin xyz, tmin, direction xyz (any length), tmax.

@@ -2189,6 +2189,7 @@ bool query_setup(Ctx &c, const QueryCall &call, hippt::QueryParams &q, const cha
     q.nodes = L.wide ? c.nodes4 : c.nodes;
     q.tris = c.tris;
     q.shade = c.shade;
+    q.pad = c.padDev;
     q.stackDepth = L.stackDepth;
     q.numNodes = L.numNodes;
     q.numTris = f.numTris;

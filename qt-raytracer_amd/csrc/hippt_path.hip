@@ -38,8 +38,9 @@ __global__ __launch_bounds__(kMeshBlock) void path_kernel(PathParams P) {
     unsigned poolNext = 0, poolEnd = 0;
     unsigned idx = kNone;  // this lane's ray
     bool need = true;
-    Ray r{};
+    QueryRay r{};
     float tmin = 0.0f;
+    const float M = scene_M(Q.pad);
     // the path's state: RNG, throughput, segments traced so far that hit (-1: an invalid ray), and
     // whether segment 0 hit
     uint32_t rng = 0;
@@ -69,7 +70,7 @@ __global__ __launch_bounds__(kMeshBlock) void path_kernel(PathParams P) {
                 begin(T);
                 T.bestO = -1;  // a hit at exactly t == tmax loses the tie on the id: tmax is exclusive
                 if (valid) {
-                    prepare(r);
+                    prepare_query<FULL, WIDE>(r, M);  // segment 0 may start anywhere
                     T.bestT = tmax;
                 } else {
                     T.cur = kDone;
@@ -108,7 +109,7 @@ __global__ __launch_bounds__(kMeshBlock) void path_kernel(PathParams P) {
                 } else if (depth < P.maxDepth &&  // depth exhausted or absorbed: contributes 0
                     scatter<FULL, false, -1>(r, T.bestT, T.bestI, Q.shade, sc.tris, P.mats, rng, tr, tg, tb, pc)) {
                     finished = false;
-                    prepare(r);
+                    prepare_segment(r);  // on a surface of the scene: the renderer's test
                     begin(T);
                     tmin = 0.001f;
                 }

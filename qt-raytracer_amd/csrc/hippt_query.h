@@ -49,6 +49,7 @@ struct QueryParams {
     // hit records (last, so that the other modes' kernel arguments stay where they were)
     const float4 *shade;  // MeshParams::shade
     float4 *hits;         // 2 float4 per ray (hipptHit)
+    const float *pad;     // the pad word of the scene's boxes (the upload's, rewritten by a refit): M * 2^-16
 };
 
 // What a launch of the query kernel computes per ray.
@@ -66,7 +67,7 @@ constexpr bool query_hits(QueryMode m) { return m == QueryMode::Hits || m == Que
 // kernel shares it: what it dereferences is there, the LDS top is whole nodes of the array, claims are
 // whole waves.
 inline bool query_params_ok(const QueryParams &q, int blocks) {
-    if (!q.nodes || !q.tris || !q.counter || blocks <= 0 || q.numRays == 0 || q.chunk < 64 || q.chunk % 64 ||
+    if (!q.nodes || !q.tris || !q.counter || !q.pad || blocks <= 0 || q.numRays == 0 || q.chunk < 64 || q.chunk % 64 ||
         q.numRays > (1u << 31) || (q.wide != 0 && q.wide != 1))
         return false;
     if (q.wide && (q.stackCap < 1 || !q.spill)) return false;

@@ -80,8 +80,9 @@ __global__ __launch_bounds__(kMeshBlock) void query_kernel(QueryParams Q) {
     unsigned poolNext = 0, poolEnd = 0;
     unsigned idx = kNone;  // this lane's ray
     bool need = true;
-    Ray r{};
+    QueryRay r{};
     float tmin = 0.0f;
+    const float M = scene_M(Q.pad);
     Trav T;
     begin(T);
     T.cur = kDone;
@@ -106,7 +107,7 @@ __global__ __launch_bounds__(kMeshBlock) void query_kernel(QueryParams Q) {
                 } else {
                     valid = load_query_ray(Q.rays, idx, r, tmin, tmax);
                 }
-                begin_query_ray(T, r, tmax, valid);
+                begin_query_ray<FULL, WIDE>(T, r, tmax, valid, M);
             }
             if (__ballot(need)) {  // a requesting lane got none: this shard is drained
                 fs = fs + 1 == kQueryShards ? 0u : fs + 1;

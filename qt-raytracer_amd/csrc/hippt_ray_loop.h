@@ -92,13 +92,74 @@ __device__ __forceinline__ bool load_query_ray(const float4 *rays, unsigned idx,
     return query_ray_valid(r, tmin, tmax);
 }
 
+// ---- the queries' ray ----
+// A ray with two origin terms per axis for the box test (hippt_slab.h "the ray queries' box test"):
+// Ray's oix, oiy, oiz are the near planes' terms in the 4-wide test and the lo planes' in the 2-wide
+// one, fox, foy, foz the far / hi planes'.  The traversal (hippt_trace.h) is the renderer's code over
+// this type: child_key and hi_oi* below replace the ones it calls for a Ray.
+struct QueryRay : Ray {
+    float fox, foy, foz;
+};
+
+__device__ __forceinline__ float hi_oix(const QueryRay &r) { return r.fox; }
+__device__ __forceinline__ float hi_oiy(const QueryRay &r) { return r.foy; }
+__device__ __forceinline__ float hi_oiz(const QueryRay &r) { return r.foz; }
+
+__device__ __forceinline__ unsigned child_key(float nx, float fx, float ny, float fy, float nz, float fz,
+                                              const QueryRay &r, float tmin, float bestT) {
+    float n;
+    return slab::box_hit_query(nx, fx, ny, fy, nz, fz, r.ix, r.iy, r.iz, r.oix, r.oiy, r.oiz, r.fox, r.foy, r.foz, tmin,
+                               bestT, n)
+               ? __float_as_uint(n)
+               : 0xffffffffu;
+}
+
+// The scene's M (the largest |coordinate| the builder or the last refit saw) from the pad word.
+__device__ __forceinline__ float scene_M(const float *pad) { return pad[0] * float(1 << slab::kPadExponent); }
+
+// prepare() for a caller's ray, which may start anywhere and have any length (hippt_slab.h query_*).
+// FULL: the scene may hold spheres, whose arithmetic overflows for long directions (query_all_boxes).
+template <bool FULL, bool WIDE>
+__device__ __forceinline__ void prepare_query(QueryRay &r, float M) {
+    const float dmax = fmaxf(fabsf(r.dx), fmaxf(fabsf(r.dy), fabsf(r.dz)));
+    const float omax = fmaxf(fabsf(r.ox), fmaxf(fabsf(r.oy), fabsf(r.oz)));
+    const float reach = omax + M, away = slab::query_away(omax, M);
+    const float floor = slab::query_dir_floor(dmax, reach);
+    r.ix = __builtin_amdgcn_rcpf(slab::query_clamp_dir(r.dx, floor));
+    r.iy = __builtin_amdgcn_rcpf(slab::query_clamp_dir(r.dy, floor));
+    r.iz = __builtin_amdgcn_rcpf(slab::query_clamp_dir(r.dz, floor));
+    const float tb = slab::query_far_bound(reach, fminf(fabsf(r.ix), fminf(fabsf(r.iy), fabsf(r.iz))));
+    float nx, ny, nz, fx, fy, fz;
+    slab::query_origin_terms(r.ox, r.dx, r.ix, floor, tb, away, slab::kQuerySlack, nx, fx);
+    slab::query_origin_terms(r.oy, r.dy, r.iy, floor, tb, away, slab::kQuerySlack, ny, fy);
+    slab::query_origin_terms(r.oz, r.dz, r.iz, floor, tb, away, slab::kQuerySlack, nz, fz);
+    if (FULL && slab::query_all_boxes(dmax, reach)) {
+        nx = ny = nz = slab::kAllBoxesNear;
+        fx = fy = fz = -slab::kAllBoxesNear;
+    }
+    // 2-wide: the lo planes are the near ones where the direction is positive
+    const bool sx = !WIDE && (__float_as_uint(r.ix) >> 31), sy = !WIDE && (__float_as_uint(r.iy) >> 31),
+               sz = !WIDE && (__float_as_uint(r.iz) >> 31);
+    r.oix = sx ? fx : nx, r.fox = sx ? nx : fx;
+    r.oiy = sy ? fy : ny, r.foy = sy ? ny : fy;
+    r.oiz = sz ? fz : nz, r.foz = sz ? nz : fz;
+}
+
+// prepare() for a ray that starts on a surface of the scene (a path's later segments): the renderer's
+// box test, one origin term per axis.
+__device__ __forceinline__ void prepare_segment(QueryRay &r) {
+    prepare(r);
+    r.fox = r.oix, r.foy = r.oiy, r.foz = r.oiz;
+}
+
 // Starts the traversal of a query's ray over [tmin, tmax), or, an invalid ray, leaves it finished
 // without a hit.
-__device__ __forceinline__ void begin_query_ray(Trav &T, Ray &r, float tmax, bool valid) {
+template <bool FULL, bool WIDE>
+__device__ __forceinline__ void begin_query_ray(Trav &T, QueryRay &r, float tmax, bool valid, float M) {
     begin(T);
     T.bestO = -1;  // a hit at exactly t == tmax loses the tie on the id: tmax is exclusive
     if (valid) {
-        prepare(r);
+        prepare_query<FULL, WIDE>(r, M);
         T.bestT = tmax;
     } else {
         T.cur = kDone;
@@ -109,7 +170,7 @@ __device__ __forceinline__ void begin_query_ray(Trav &T, Ray &r, float tmax, boo
 // One speculative while-while round of the queries' traversal (hippt_trace.h), over float nodes of
 // either width, with the ray's own tmin.
 template <bool LDS_SCENE, bool FULL, bool WIDE>
-__device__ __forceinline__ void traverse_step(Trav &T, const Ray &r, float tmin, const Staged &sc, const QueryParams &Q,
+__device__ __forceinline__ void traverse_step(Trav &T, const QueryRay &r, float tmin, const Staged &sc, const QueryParams &Q,
                                               const SpillArea &S, unsigned long long &nvis, unsigned long long &ntest,
                                               unsigned *pc) {
     constexpr int nodeF4 = WIDE ? (LDS_SCENE ? kLdsNode4F4 : 8) : (LDS_SCENE ? kLdsNodeF4 : 4);

@@ -101,5 +101,62 @@ HIPPT_SL float trim_of(float pad, float scale) { return pad * scale; }
 HIPPT_SL float trim_lo(float lo, float trim) { return lo + trim; }
 HIPPT_SL float trim_hi(float hi, float trim) { return hi - trim; }
 
+// ---- the ray queries' box test: a per-ray slack and a relative direction clamp ----------------------
+// The builder's pad covers the rounding of the test above for rays that start within a few M of the
+// scene.  A query's ray may start anywhere: at |o| = K * M the terms o * inv and plane * inv - oi are
+// about K * M * |inv| and round by 2^-24 of that, which exceeds the pad's pad * |inv| from K of a few
+// hundred on; and the absolute 1e-20 of clamp_dir replaces every component of a short direction.  The
+// queries therefore prepare their rays with the functions below (hippt_ray_loop.h prepare_query;
+// tests/native/far_model.cpp measures them, DESIGN.md §5 "Query slack"):
+//   floor = max(dmax * 2^-40, reach * 2^-120)     dmax, omax: the largest |component| of the direction
+//                                                 and the origin; reach = omax + M
+//   inv   = rcp(clamp(d, floor))                  per axis, the caller's reciprocal
+//   oi    = o * inv,  s = kQuerySlack * away * |inv|    away = max(omax - 2 M, 0): every box grown by
+//                                                 kQuerySlack * away (the oracle's own t errs by ulps
+//                                                 of |o| / |d|, whichever axis the box is thin on)
+//   near planes use oi + s, far planes oi - s     (plane_t: the near t moves down, the far t up, by s)
+//   an axis whose component was clamped: its far planes use oi - (s + tb), tb = 2 * reach * min |inv|
+// tb bounds every hit's t (the hit lies within M of the origin's frame on the longest axis), so a far
+// plane of a clamped axis, whose true crossing lies beyond the computed one, never ends a ray early;
+// its near plane errs on the safe side by itself.  The node loop is the same instructions over two
+// origin terms per axis.
+constexpr float kQuerySlack = 128.0f * 0x1p-24f;  // 4 x the measured requirement, a power of two
+
+HIPPT_SL float query_dir_floor(float dmax, float reach) { return fmaxf(dmax * 0x1p-40f, reach * 0x1p-120f); }
+HIPPT_SL float query_clamp_dir(float d, float floor) { return copysignf(fmaxf(fabsf(d), floor), d); }
+HIPPT_SL float query_far_bound(float reach, float invMin) { return 2.0f * reach * invMin; }
+// How far outside the builder's assumption the origin lies: 0 within 2 M (the pad alone covers such
+// rays, and their box tests are the parent's bit for bit), else its largest |component| less 2 M.
+HIPPT_SL float query_away(float omax, float M) { return fmaxf(omax - 2.0f * M, 0.0f); }
+
+// An axis' two origin terms from its reciprocal (of query_clamp_dir(d, floor)); slack: kQuerySlack
+// in the kernels, the model varies it.
+HIPPT_SL void query_origin_terms(float o, float d, float inv, float floor, float tb, float away, float slack,
+                                 float &oiNear, float &oiFar) {
+    const float oi = origin_term(o, inv);
+    const float s = (slack * away) * fabsf(inv);
+    oiNear = oi + s;
+    oiFar = oi - (fabsf(d) < floor ? s + tb : s);
+}
+
+// A scene with spheres: the oracle's sphere test squares (o - c) . d and multiplies |d|^2 by |o - c|^2,
+// which overflow from about dmax * reach = 2^62 on; what it then accepts (a hit at t = 0, say) is no
+// point of the ray that a box could enclose.  Such a ray takes every box: near terms +inf and far
+// terms -inf make every plane's t -inf / +inf, and the traversal is the oracle's loop over all primitives.
+HIPPT_SL bool query_all_boxes(float dmax, float reach) { return dmax * reach >= 0x1p60f; }
+constexpr float kAllBoxesNear = __builtin_inff();
+
+// box_hit over the two origin terms.
+HIPPT_SL bool box_hit_query(float nx, float fx, float ny, float fy, float nz, float fz, float ix, float iy, float iz,
+                            float onx, float ony, float onz, float ofx, float ofy, float ofz, float tmin, float bestT,
+                            float &n) {
+    const float ax = plane_t(nx, ix, onx), bx = plane_t(fx, ix, ofx);
+    const float ay = plane_t(ny, iy, ony), by = plane_t(fy, iy, ofy);
+    const float az = plane_t(nz, iz, onz), bz = plane_t(fz, iz, ofz);
+    n = entry_t(ax, ay, az, tmin);
+    const float f = exit_t(bx, by, bz, bestT);
+    return HIPPT_SLAB_MEETS(n, f);
+}
+
 }  // namespace slab
 }  // namespace hippt

@@ -300,6 +300,13 @@ __device__ __forceinline__ void prepare(Ray &r) {
     r.oiz = slab::origin_term(r.oz, r.iz);
 }
 
+// The origin term of an axis' hi planes in the 2-wide node test (traverse_round): the renderer's rays
+// have one term per axis; a ray type with two (hippt_ray_loop.h QueryRay) overloads these, and
+// child_key for the 4-wide test.
+__device__ __forceinline__ float hi_oix(const Ray &r) { return r.oix; }
+__device__ __forceinline__ float hi_oiy(const Ray &r) { return r.oiy; }
+__device__ __forceinline__ float hi_oiz(const Ray &r) { return r.oiz; }
+
 // A MeshParams field (the kernels' only argument, at kernarg offset 0) loaded where it is used: the
 // opaque kernarg address keeps the compiler from loading it at kernel entry and holding it in
 // registers (SGPRs, or VGPR lanes once those run out) across the whole kernel.  Taking the
@@ -1179,8 +1186,8 @@ __device__ __forceinline__ void leaf_step(Trav &T, const Ray &r, const float4 *t
 // unconditionally and used only when neither is (branch-free child selection).
 // tmin (here and in traverse_round_wide): the hits' lower bound and the box test's near bound, the
 // renderer's 0.001 or a queried ray's own (>= +0: the child keys are ordered as unsigned).
-template <int NODE_F4, bool STATS, bool FULL>
-__device__ __forceinline__ void traverse_round(Trav &T, const Ray &r, int *my, const float4 *nodes,
+template <int NODE_F4, bool STATS, bool FULL, class RayT>
+__device__ __forceinline__ void traverse_round(Trav &T, const RayT &r, int *my, const float4 *nodes,
                                                const float4 *tris, unsigned long long &nvis,
                                                unsigned long long &ntest, unsigned *pc, unsigned leafExit = 0,
                                                unsigned nodeExit = 0, float tmin = 0.001f) {
@@ -1190,12 +1197,12 @@ __device__ __forceinline__ void traverse_round(Trav &T, const Ray &r, int *my, c
         const float4 a = nd[0], b = nd[1], c = nd[2];
         const int4 e = *reinterpret_cast<const int4 *>(nd + 3);
         if (STATS) ++nvis;
-        const float l0x = fmaf(a.x, r.ix, -r.oix), h0x = fmaf(a.w, r.ix, -r.oix);
-        const float l0y = fmaf(a.y, r.iy, -r.oiy), h0y = fmaf(b.x, r.iy, -r.oiy);
-        const float l0z = fmaf(a.z, r.iz, -r.oiz), h0z = fmaf(b.y, r.iz, -r.oiz);
-        const float l1x = fmaf(b.z, r.ix, -r.oix), h1x = fmaf(c.y, r.ix, -r.oix);
-        const float l1y = fmaf(b.w, r.iy, -r.oiy), h1y = fmaf(c.z, r.iy, -r.oiy);
-        const float l1z = fmaf(c.x, r.iz, -r.oiz), h1z = fmaf(c.w, r.iz, -r.oiz);
+        const float l0x = fmaf(a.x, r.ix, -r.oix), h0x = fmaf(a.w, r.ix, -hi_oix(r));
+        const float l0y = fmaf(a.y, r.iy, -r.oiy), h0y = fmaf(b.x, r.iy, -hi_oiy(r));
+        const float l0z = fmaf(a.z, r.iz, -r.oiz), h0z = fmaf(b.y, r.iz, -hi_oiz(r));
+        const float l1x = fmaf(b.z, r.ix, -r.oix), h1x = fmaf(c.y, r.ix, -hi_oix(r));
+        const float l1y = fmaf(b.w, r.iy, -r.oiy), h1y = fmaf(c.z, r.iy, -hi_oiy(r));
+        const float l1z = fmaf(c.x, r.iz, -r.oiz), h1z = fmaf(c.w, r.iz, -hi_oiz(r));
         const float n0 = fmaxf(fmaxf(fminf(l0x, h0x), fminf(l0y, h0y)), fmaxf(fminf(l0z, h0z), tmin));
         const float f0 = fminf(fminf(fmaxf(l0x, h0x), fmaxf(l0y, h0y)), fminf(fmaxf(l0z, h0z), T.bestT));
         const float n1 = fmaxf(fmaxf(fminf(l1x, h1x), fminf(l1y, h1y)), fmaxf(fminf(l1z, h1z), tmin));
@@ -1344,9 +1351,9 @@ __device__ __forceinline__ void cas(unsigned &ka, int &ca, unsigned &kb, int &cb
 // is 5 unsigned min/max pairs (no compare + 4 selects per exchange moving the codes along), and the
 // stack holds keys.  Truncating the distance to its high bits only reorders near-equal children,
 // and the closest hit is argmin (t, primitive id): no result bit depends on the visiting order.
-template <bool PACKED>
+template <bool PACKED, class RayT>
 __device__ __forceinline__ unsigned child_key_p(float nx, float fx, float ny, float fy, float nz, float fz,
-                                                const Ray &r, float tmin, float bestT, int code, unsigned mask) {
+                                                const RayT &r, float tmin, float bestT, int code, unsigned mask) {
     if (!PACKED) return child_key(nx, fx, ny, fy, nz, fz, r, tmin, bestT);
     const float ax = slab::plane_t(nx, r.ix, r.oix), bx = slab::plane_t(fx, r.ix, r.oix);
     const float ay = slab::plane_t(ny, r.iy, r.oiy), by = slab::plane_t(fy, r.iy, r.oiy);
@@ -1380,8 +1387,9 @@ __device__ __forceinline__ void cas_key(unsigned &ka, unsigned &kb) {
 // half-precision planes, each axis's near and far planes one aligned 16-byte read (4 reads per
 // visit instead of 7 where the TA binds), the slab FMAs taking the halves directly (v_fma_mix_f32).
 template <int NODE_F4, bool STATS, bool FULL, bool QUANT = false, bool SPILL = true, bool LDS0 = false,
-          bool TOP = false, bool HYBRID = false, bool PACKED = false, bool HALF = false, bool DEFER = false>
-__device__ __forceinline__ void traverse_round_wide(Trav &T, const Ray &r, int *my, const float4 *nodes,
+          bool TOP = false, bool HYBRID = false, bool PACKED = false, bool HALF = false, bool DEFER = false,
+          class RayT = Ray>
+__device__ __forceinline__ void traverse_round_wide(Trav &T, const RayT &r, int *my, const float4 *nodes,
                                                     const float4 *tris, unsigned long long &nvis,
                                                     unsigned long long &ntest, unsigned *pc, unsigned leafExit,
                                                     unsigned nodeExit, const SpillArea &S,
