@@ -478,7 +478,41 @@ enum {
     , HIPPT_OPT_DENOISE_TIMING = 36 /* 1: hipptDenoise brackets each of its stages with timing events and keeps
                                        their device times (HIPPT_INFO_DENOISE_NS); 0 (default): no events.
                                        Same results either way (a measuring aid) */
+    , HIPPT_OPT_LIGHT_SAMPLING = 37 /* 1: next-event estimation: every Lambertian vertex of a path makes one
+                                       connection to a light (the path rule below); 0 (default): a path finds
+                                       a light only by hitting it, byte for byte as before the option
+                                       existed, from the same kernels.  Takes effect at the next render or
+                                       hipptTraceRadiance, without a new upload.  With 1 and no emissive
+                                       primitive in the scene the option-off code runs.  Renders under it
+                                       are traced by a ray-per-lane kernel into the batch scratch and
+                                       combined by the deferred combine: no chaining, sky rectangle, render
+                                       pad or item order (their HIPPT_INFO_* read 0), and
+                                       HIPPT_OPT_COUNT_TRAVERSAL's counts are not reported */
 };
+/* Light sampling (HIPPT_OPT_LIGHT_SAMPLING 1; this library's own, as the emissive rule is; tests/nee_ref.py
+ * restates it in numpy float32 and the GPU matches that bit for bit).  A path carries
+ * Lacc = (0, 0, 0) and spec = true (the last scatter was not Lambertian, or there was none yet).
+ *   light hit   ends the path, before the depth check: L = Lacc + thr * Le if spec, else L = Lacc
+ *   miss        L = Lacc + thr * sky;   depth exhausted or absorbed: L = Lacc
+ *   Metal, Dielectric scatter: unchanged; spec = true
+ *   Lambertian scatter (a hit with depth + 1 < maxDepth): the renderer's scatter first (new origin p, faced
+ *   normal n, thr' = thr * albedo, RNG advanced); spec = false; then, from the same RNG state:
+ *     k = min(int(rand01 * float(nLights)), nLights - 1) over the emissive primitives in ascending id
+ *     triangle (v0, e1, e2, unit normal ng): a = rand01, b = rand01, folded (a, b) -> (1 - a, 1 - b) if
+ *       a + b > 1; q = fmaf(b, e2, fmaf(a, e1, v0)); A = 0.5f * sqrtf(|cross(e1, e2)|^2); nl = ng
+ *     sphere (c, r): u = unit(random_in_unit_sphere), the Lambertian scatter's draw; q = fmaf(r, u, c);
+ *       nl = u; A = (12.566371f * r) * r
+ *     w = q - p; d2 = fdot(w, w); om = w * (1 / sqrtf(d2)); cosS = fdot(n, om); sL = fdot(nl, om)
+ *     triangle: cosL = |sL| (two-sided); sphere: cosL = -sL if |p - c|^2 >= r * r, else sL
+ *     unless cosS > 0, cosL > 0, d2 > 0 and A > 0 no shadow ray is traced (the draws are consumed)
+ *     g = (((cosS * cosL) * A) * float(nLights)) / (3.14159274f * d2); Ld.c = (thr'.c * Le.c) * g
+ *     the shadow ray (p, om), tmin 0.001, no tmax, is a closest-hit query: if its hit is light k,
+ *     Lacc.c += Ld.c.  The path goes on along the scattered ray.
+ * No MIS; one light per vertex, uniform over the list.  maxDepth means what it meant: the connection at
+ * vertex d stands for the light hit of segment d + 1 and is made exactly when that segment would exist.
+ * segments (hipptTraceRadiance, hipptGetStats) count every closest-hit query traced, shadow rays included. */
+enum { HIPPT_INFO_LIGHTS = 107          /* emissive primitives in the uploaded scene */,
+       HIPPT_INFO_LIGHT_SAMPLING = 108  /* 1 if the last render took the light-sampling route, else 0 */ };
 /* Records of the chained runs closed since the last call (HIPPT_OPT_CHAIN_AUDIT), as 32-bit words:
  * per run a 16-word header  [0] 0xC4A1D17 [1] run id [2] device [3] batch 0's first frame [4] frames
  * from one batch to the next (-1: one batch) [5] frames per batch [6] band pixels [7] items per batch

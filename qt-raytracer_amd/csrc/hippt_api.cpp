@@ -260,6 +260,15 @@ struct Ctx {
     hipEvent_t qDone = nullptr;
     OccKey qOccKey;  // of qBlocksPerCu
     int qBlocksPerCu = 0;
+    // Light sampling (HIPPT_OPT_LIGHT_SAMPLING): the scene's light list (SceneHost::lights; a scene buffer),
+    // and what the render route's launches take in place of the queries' (an asynchronous render may still
+    // be in flight when a query grows qSpill): claim counters, spill area, resident blocks per CU.
+    int *lights = nullptr;
+    unsigned *neeCtr = nullptr;
+    int *neeSpill = nullptr;
+    size_t neeSpillBytes = 0;
+    OccKey neeOccKey;  // of neeBlocksPerCu
+    int neeBlocksPerCu = 0;
     // Denoiser (hipptDenoise, hippt_denoise.h): one buffer of 80 bytes per pixel (the guide sample's hit
     // records, two colour buffers, the guide), allocated at first use, reused while large enough and
     // freed with the context; the stages' timing events (HIPPT_OPT_DENOISE_TIMING), created on use.
@@ -284,6 +293,7 @@ struct SceneHost {
     int numNodes4 = 0, levels4 = 0, stackBound4 = 0;
     bool full = false;                          // spheres or non-Lambertian materials
     bool emissive = false;                      // an emissive material among them (MeshParams::full = 2)
+    std::vector<int> lights;                    // leaf-order indices of the emissive primitives, ascending id
     double lookfrom[3] = {0, 0, 0}, lookat[3] = {0, 0, -1}, vup[3] = {0, 1, 0};
     double vfov = 90, aperture = 0, focus = 1;
     bool rawCamera = false;
@@ -338,6 +348,8 @@ struct State {
     bool chainAudit = false;            // HIPPT_OPT_CHAIN_AUDIT
     long long querySlice = 0;           // rays per staged slice of a host-memory query (HIPPT_OPT_QUERY_SLICE; 0 automatic)
     bool denoiseTiming = false;         // HIPPT_OPT_DENOISE_TIMING
+    bool lightSampling = false;         // HIPPT_OPT_LIGHT_SAMPLING
+    int activeLightSampling = 0;        // the last render took the light-sampling route (HIPPT_INFO_LIGHT_SAMPLING)
     long long denoiseNs[hippt::kDenoiseStages] = {};  // HIPPT_INFO_DENOISE_NS + k of the last timed hipptDenoise
     std::vector<unsigned> auditWords;   // closed runs' audit words not yet read (hipptChainAudit)
     std::vector<std::pair<int, uint32_t *>> rngTables;  // per device, built on first use
@@ -591,7 +603,9 @@ void free_scene_buffers(Ctx &c) {
     (void)hipFree(c.nodes4h);
     (void)hipFree(c.nodes4f);
     (void)hipFree(c.padDev);
+    (void)hipFree(c.lights);
     c.padDev = nullptr;
+    c.lights = nullptr;
     c.nodes = c.tris = c.shade = c.mats = c.nodes4 = c.nodes4q = c.nodes4h = c.nodes4f = nullptr;
     (void)hipFree(c.rfVerts);
     (void)hipFree(c.rfBoxes);
@@ -785,6 +799,8 @@ void destroy_ctx(Ctx &c, bool keep) {
     c.spillBytes = 0;
     (void)hipFree(c.qCtr);
     (void)hipFree(c.qSpill);
+    (void)hipFree(c.neeCtr);
+    (void)hipFree(c.neeSpill);
     (void)hipFree(c.qStage);
     if (c.qDone) (void)hipEventDestroy(c.qDone);
     (void)hipFree(c.dnBuf);
@@ -897,6 +913,10 @@ bool ensure_scene(Ctx &c, const char **err) {
         return false;
     HIP_TRY(hipMalloc(&c.padDev, 16));
     HIP_TRY(hipMemcpy(c.padDev, &s.scene.pad, sizeof(float), hipMemcpyHostToDevice));
+    if (!s.scene.lights.empty()) {
+        HIP_TRY(hipMalloc(&c.lights, s.scene.lights.size() * sizeof(int)));
+        HIP_TRY(hipMemcpy(c.lights, s.scene.lights.data(), s.scene.lights.size() * sizeof(int), hipMemcpyHostToDevice));
+    }
     c.sceneVersion = s.scene.version;
     return true;
 }
@@ -1805,6 +1825,13 @@ bool enqueue_sphere4(Ctx &c, int firstFrame, int count, int maxDepth, bool copy,
     return true;
 }
 
+// HIPPT_OPT_LIGHT_SAMPLING as applied: on, and the scene holds an emissive primitive (else the option-off
+// code runs).
+bool light_sampling_applies() {
+    const State &s = S();
+    return s.lightSampling && s.scene.kind == HIPPT_SCENE_MESH && !s.scene.lights.empty();
+}
+
 // A mesh call's batches on a context: as many frames per batch as the sample scratch budget
 // (HIPPT_OPT_SCRATCH_MB) and the 2^31 work items of a launch hold.
 struct BatchSize {
@@ -1938,9 +1965,13 @@ bool fill_mesh_params(Ctx &c, const plan::Facts &f, const plan::Layout &L, const
 // A mesh scene's frames on context c, in batches: each a megakernel launch (on its own, or a batch of
 // the context's chained run), or the wavefront's launches; its combine deferred into the next batch's
 // launch, or flushed.
+bool enqueue_mesh_lights(Ctx &c, const CameraF &cam, int firstFrame, int count, int maxDepth, const char **err);
+
 bool enqueue_mesh(Ctx &c, const CameraF &cam, int firstFrame, int count, int maxDepth, bool copy, const char **err) {
     State &s = S();
     if (!ensure_scene(c, err)) return false;
+    s.activeLightSampling = 0;
+    if (maxDepth > 0 && light_sampling_applies()) return enqueue_mesh_lights(c, cam, firstFrame, count, maxDepth, err);
     const unsigned bandPixels = unsigned(c.rows) * unsigned(s.width);
     const BatchSize size = frames_per_batch(bandPixels, count);
     const bool cnt = s.knobs.countTraversal;
@@ -2181,7 +2212,7 @@ bool device_pointers_ok(const std::string &who, const char *flagName, int requir
 // the queries' profile (hippt_plan.h query_knobs: the wavefront extend kernel's loop parameters, float
 // nodes, no camera pool).  Unlike a render, whose launches take a spill area only when the stack bound
 // exceeds the LDS capacity, the query kernel takes one for every 4-wide tree.
-bool query_setup(Ctx &c, const QueryCall &call, hippt::QueryParams &q, const char **err) {
+plan::Layout query_scene_params(Ctx &c, hippt::QueryParams &q) {
     State &s = S();
     const plan::Facts f = scene_facts(s.scene);
     const plan::Layout L = plan::layout(f, plan::query_knobs(s.knobs), lds_limits(), false);
@@ -2202,6 +2233,13 @@ bool query_setup(Ctx &c, const QueryCall &call, hippt::QueryParams &q, const cha
     q.waveThreshold = L.waveThreshold;
     q.leafExit = L.leafExit;
     q.nodeExit = L.nodeExit;
+    return L;
+}
+
+bool query_setup(Ctx &c, const QueryCall &call, hippt::QueryParams &q, const char **err) {
+    State &s = S();
+    const plan::Layout L = query_scene_params(c, q);
+    const plan::Facts f = scene_facts(s.scene);
     if (call.camera()) {
         hippt::QueryCam &k = q.cam;
         k.cam = current_camera();
@@ -2221,10 +2259,13 @@ bool query_setup(Ctx &c, const QueryCall &call, hippt::QueryParams &q, const cha
     OccKey occKey;
     occKey.version = s.scene.version, occKey.stackDepth = L.stackDepth, occKey.fmt = L.fmt, occKey.topBytes = L.topBytes;
     occKey.ldsScene = L.ldsScene, occKey.full = f.full;
-    occKey.variant = call.path ? 8 : int(call.mode);
+    const bool nee = call.path && light_sampling_applies();
+    occKey.variant = call.path ? (nee ? 9 : 8) : int(call.mode);
     if (!same_key(c.qOccKey, occKey)) {
-        c.qBlocksPerCu = call.path ? hippt::path_blocks_per_cu(hippt::PathParams{q, c.mats, nullptr, nullptr, nullptr, 1})
-                                   : hippt::query_blocks_per_cu(q, call.mode);
+        const hippt::PathParams pp{q, c.mats, nullptr, nullptr, nullptr, 1};
+        c.qBlocksPerCu = nee         ? hippt::nee_blocks_per_cu(hippt::NeeParams{pp, c.lights, 1, nullptr, nullptr})
+                         : call.path ? hippt::path_blocks_per_cu(pp)
+                                     : hippt::query_blocks_per_cu(q, call.mode);
         c.qOccKey = occKey;
     }
     if (!c.qCtr) HIP_TRY(hipMalloc(&c.qCtr, hippt::kQueryCtrBytes));
@@ -2236,6 +2277,82 @@ bool query_setup(Ctx &c, const QueryCall &call, hippt::QueryParams &q, const cha
         q.spill = c.qSpill;
     }
     q.counter = c.qCtr;
+    return true;
+}
+
+// The light-sampling render route (HIPPT_OPT_LIGHT_SAMPLING on a scene with a light): each
+// batch is one launch of the path queries' light-sampling kernel over the renderer's own camera samples
+// (QueryCam: the context's rows of the image, frame-major items as the combine reads them), into the batch
+// scratch, combined by the deferred combine.  No chaining, sky rectangle, render pad or item order.  Its
+// counters and spill area are the route's own: a batch may still be in flight when a query is made.
+bool enqueue_mesh_lights(Ctx &c, const CameraF &cam, int firstFrame, int count, int maxDepth, const char **err) {
+    State &s = S();
+    const unsigned bandPixels = unsigned(c.rows) * unsigned(s.width);
+    const BatchSize size = frames_per_batch(bandPixels, count);
+    hippt::QueryParams q;
+    const plan::Layout L = query_scene_params(c, q);
+    hippt::QueryCam &k = q.cam;
+    k.cam = cam;
+    k.invW = 1.0f / float(std::max(1, s.width - 1));
+    k.invH = 1.0f / float(std::max(1, s.height - 1));
+    k.width = s.width;
+    k.y0 = c.y0;
+    k.rowStride = c.stride;
+    k.bandPixels = bandPixels;
+    k.rcpBandPixels = 1.0f / float(bandPixels);
+    k.rcpWidth = 1.0f / float(s.width);
+    hippt::NeeParams np{hippt::PathParams{q, c.mats, nullptr, nullptr, nullptr, maxDepth}, c.lights,
+                        int(s.scene.lights.size()), nullptr, c.stats};
+    OccKey occKey;
+    occKey.version = s.scene.version, occKey.stackDepth = L.stackDepth, occKey.fmt = L.fmt, occKey.topBytes = L.topBytes;
+    occKey.ldsScene = L.ldsScene, occKey.full = true;
+    occKey.variant = 10;
+    if (!same_key(c.neeOccKey, occKey)) {
+        np.scratch = reinterpret_cast<float *>(c.stats);  // (any non-null pointer: selects the camera kernels)
+        c.neeBlocksPerCu = hippt::nee_blocks_per_cu(np);
+        c.neeOccKey = occKey;
+    }
+    if (!c.neeCtr) HIP_TRY(hipMalloc(&c.neeCtr, hippt::kQueryCtrBytes));
+    if (L.wide) {
+        const size_t bytes = size_t(c.cus) * size_t(c.neeBlocksPerCu) * hippt::kMeshBlock * size_t(q.spillCap) * sizeof(int);
+        if (c.neeSpillBytes < bytes) HIP_TRY(hipStreamSynchronize(c.stream));  // earlier batches use the old one
+        if (!grow(reinterpret_cast<void **>(&c.neeSpill), &c.neeSpillBytes, bytes, "hipMalloc(&c.neeSpill, bytes)", err))
+            return false;
+        np.p.q.spill = c.neeSpill;
+    }
+    np.p.q.counter = c.neeCtr;
+    s.activeWidth = L.wide ? 4 : 2;
+    s.activeTopBytes = L.topBytes;
+    s.activeBlocksPerCu = c.neeBlocksPerCu;
+    s.activeChainCap = 0;
+    s.activeRenderPad = 0;
+    s.activeSkyPixels = 0;
+    s.activeLightSampling = 1;
+    for (int b = 0; b < count; b += size.frames) {
+        const int nf = std::min(size.frames, count - b);
+        const unsigned total = bandPixels * unsigned(nf);
+        if (!flush_deferred(c, err)) return false;  // (the chain's flush too)
+        float *scratch = nullptr;
+        if (!batch_scratch(c, size.need, &scratch, err)) return false;
+        np.scratch = scratch;
+        hippt::QueryParams &bq = np.p.q;
+        bq.cam.firstFrame = firstFrame + b;
+        bq.numRays = total;
+        bq.firstItem = 0;
+        bq.chunk = plan::query_chunk(total);
+        s.activeChunk = int(bq.chunk);
+        const long long blocks = std::max(
+            1LL, std::min<long long>((long long)c.cus * c.neeBlocksPerCu, (total + hippt::kMeshBlock - 1) / hippt::kMeshBlock));
+        HIP_TRY(hipMemsetAsync(c.neeCtr, 0, hippt::kQueryCtrBytes, c.stream));
+        EventPair ev;
+        if (!next_events(c, ev, err)) return false;
+        HIP_TRY(hipEventRecord(ev.a, c.stream));
+        HIP_TRY(hippt::launch_nee(np, int(blocks), c.stream));
+        HIP_TRY(hipEventRecord(ev.b, c.stream));
+        c.pending.push_back({0, ev});
+        c.deferred = hippt::CombineParams{c.accum, c.out, scratch, bandPixels, total, firstFrame + b, nf, s.pixelFormat};
+        c.hasDeferred = true;
+    }
     return true;
 }
 
@@ -2253,7 +2370,12 @@ bool query_enqueue(Ctx &c, hippt::QueryParams q, unsigned first, unsigned m, con
     const long long blocks =
         std::max(1LL, std::min<long long>((long long)c.cus * c.qBlocksPerCu, (m + hippt::kMeshBlock - 1) / hippt::kMeshBlock));
     HIP_TRY(hipMemsetAsync(c.qCtr, 0, hippt::kQueryCtrBytes, c.stream));
-    if (call.path)
+    if (call.path && light_sampling_applies())
+        HIP_TRY(hippt::launch_nee(
+            hippt::NeeParams{hippt::PathParams{q, c.mats, pp.seeds, pp.radiance, pp.segments, call.maxDepth}, c.lights,
+                             int(S().scene.lights.size()), nullptr, nullptr},
+            int(blocks), c.stream));
+    else if (call.path)
         HIP_TRY(hippt::launch_path(hippt::PathParams{q, c.mats, pp.seeds, pp.radiance, pp.segments, call.maxDepth}, int(blocks),
                                    c.stream));
     else
@@ -2683,6 +2805,17 @@ bool upload_scene_locked(const float *verts, const int *triMaterial, int numTris
     sc.levels = sc.bvh2.levels;
     sc.full = full;
     sc.emissive = emissive;
+    // the light list (HIPPT_OPT_LIGHT_SAMPLING): leaf-order indices of the emissive primitives by ascending id
+    {
+        std::vector<std::pair<int, int>> byId;
+        for (int k = 0; k < numPrims; ++k) {
+            const int id = sc.bvh2.order[size_t(k)];
+            const int m = id >= numTris ? sphereMaterial[id - numTris] : triMaterial[id];
+            if (materials[m].kind == HIPPT_MAT_EMISSIVE) byId.emplace_back(id, k);
+        }
+        std::sort(byId.begin(), byId.end());
+        for (const auto &e : byId) sc.lights.push_back(e.second);
+    }
     for (int i = 0; i < 3; ++i) {
         sc.lookfrom[i] = lookfrom[i];
         sc.lookat[i] = lookat[i];
@@ -3389,6 +3522,10 @@ bool set_option_locked(int key, long long value) {
         if (value != 0 && value != 1) return false;
         s.denoiseTiming = value == 1;
         return true;
+    case HIPPT_OPT_LIGHT_SAMPLING:
+        if (value != 0 && value != 1) return false;
+        s.lightSampling = value == 1;
+        return true;
     default: return false;
     }
 }
@@ -3448,6 +3585,9 @@ long long get_option_locked(int key) {
     case HIPPT_INFO_CHAIN_CAP: return s.activeChainCap;
     case HIPPT_INFO_RENDER_PAD: return s.activeRenderPad;
     case HIPPT_OPT_DENOISE_TIMING: return s.denoiseTiming ? 1 : 0;
+    case HIPPT_OPT_LIGHT_SAMPLING: return s.lightSampling ? 1 : 0;
+    case HIPPT_INFO_LIGHTS: return s.scene.kind == HIPPT_SCENE_MESH ? (long long)s.scene.lights.size() : 0;
+    case HIPPT_INFO_LIGHT_SAMPLING: return s.activeLightSampling;
     case HIPPT_INFO_SKY_RECT_PIXELS: return s.activeSkyPixels;
     case HIPPT_INFO_UPDATE_DROPPED:
         // the last update's count, from the first context that ran it (every context counts the same)

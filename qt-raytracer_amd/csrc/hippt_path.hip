@@ -129,6 +129,259 @@ PathFn path_fn(const QueryParams &q) {
     return for_scene_layout(q, [](auto lds, auto full, auto wide) -> PathFn { return path_kernel<lds(), full(), wide()>; });
 }
 
+// ---- light sampling (DESIGN.md §2 "Light sampling", §16; tests/nee_ref.py is the statement of record) ----
+// The faced normal scatter() forms at the hit of primitive `prim` at t, and the material's kind: asked
+// before scatter() replaces the ray.
+__device__ __forceinline__ int hit_normal_kind(const Ray &r, float t, int prim, const float4 *shade, const float4 *prims,
+                                               const float4 *mats, float &nx, float &ny, float &nz) {
+    const float4 sh = shade[prim];
+    const int mw = __float_as_int(sh.w);
+    nx = sh.x, ny = sh.y, nz = sh.z;
+    if (mw & kShadeSphere) {
+        const float px = fmaf(t, r.dx, r.ox), py = fmaf(t, r.dy, r.oy), pz = fmaf(t, r.dz, r.oz);
+        const float rad = prims[3 * prim].w;
+        nx = (px - sh.x) / rad;
+        ny = (py - sh.y) / rad;
+        nz = (pz - sh.z) / rad;
+    }
+    if (!(fdot(r.dx, r.dy, r.dz, nx, ny, nz) < 0.0f)) {
+        nx = -nx;
+        ny = -ny;
+        nz = -nz;
+    }
+    return __float_as_int(mats[2 * (mw & ~kShadeSphere)].w);
+}
+
+// One connection from the Lambertian vertex p (faced normal n, throughput t* after the scatter): picks a
+// light and a point on it from `rng`, and returns whether a shadow ray is to be traced; then (wx, wy, wz)
+// is its unit direction, (l0, l1, l2) what the light adds if the ray's closest hit is primitive `lk`
+// (leaf order).  The draws are consumed either way.
+__device__ __forceinline__ bool light_connect(const int *lights, int numLights, const float4 *shade, const float4 *prims,
+                                              const float4 *mats, float px, float py, float pz, float nx, float ny,
+                                              float nz, float tr, float tg, float tb, uint32_t &rng, unsigned *pc,
+                                              float &wx, float &wy, float &wz, float &l0, float &l1, float &l2, int &lk) {
+    const float nl = float(numLights);
+    lk = lights[min(int(rand01(rng) * nl), numLights - 1)];
+    const float4 sh = shade[lk];
+    const float4 A = prims[3 * lk], B = prims[3 * lk + 1];
+    const int mw = __float_as_int(sh.w);
+    const float4 le = mats[2 * (mw & ~kShadeSphere)];
+    float qx, qy, qz, lx, ly, lz, area;
+    bool flip = false, sphere = (mw & kShadeSphere) != 0;
+    if (sphere) {  // (centre, r): c + r * unit(random_in_unit_sphere), the Lambertian scatter's draw
+        float ux, uy, uz;
+        const float inv = rsqrt_unit_draw(rius<false, -1>(rng, ux, uy, uz, pc));
+        lx = ux * inv, ly = uy * inv, lz = uz * inv;
+        const float rad = A.w;
+        qx = fmaf(rad, lx, sh.x), qy = fmaf(rad, ly, sh.y), qz = fmaf(rad, lz, sh.z);
+        area = (12.566371f * rad) * rad;
+        const float ox = px - sh.x, oy = py - sh.y, oz = pz - sh.z;
+        flip = fdot(ox, oy, oz, ox, oy, oz) >= rad * rad;  // seen from outside: the near side emits
+    } else {  // (v0, e1, e2): uniform by folding the unit square
+        float a = rand01(rng), b = rand01(rng);
+        if (a + b > 1.0f) {
+            a = 1.0f - a;
+            b = 1.0f - b;
+        }
+        const float e1x = A.w, e1y = B.x, e1z = B.y;
+        const float e2x = B.z, e2y = B.w, e2z = prims[3 * lk + 2].x;
+        qx = fmaf(b, e2x, fmaf(a, e1x, A.x)), qy = fmaf(b, e2y, fmaf(a, e1y, A.y)), qz = fmaf(b, e2z, fmaf(a, e1z, A.z));
+        const float cx = fmaf(e1y, e2z, -(e1z * e2y)), cy = fmaf(e1z, e2x, -(e1x * e2z)), cz = fmaf(e1x, e2y, -(e1y * e2x));
+        area = 0.5f * sqrtf(fdot(cx, cy, cz, cx, cy, cz));
+        lx = sh.x, ly = sh.y, lz = sh.z;
+    }
+    const float dx = qx - px, dy = qy - py, dz = qz - pz;
+    const float d2 = fdot(dx, dy, dz, dx, dy, dz);
+    const float il = rsqrt_rn(d2);
+    wx = dx * il, wy = dy * il, wz = dz * il;
+    const float cosS = fdot(nx, ny, nz, wx, wy, wz);
+    const float sL = fdot(lx, ly, lz, wx, wy, wz);
+    const float cosL = sphere ? (flip ? -sL : sL) : fabsf(sL);
+    if (!(cosS > 0.0f) || !(cosL > 0.0f) || !(d2 > 0.0f) || !(area > 0.0f)) return false;
+    const float g = (((cosS * cosL) * area) * nl) / (3.14159274f * d2);
+    l0 = (tr * le.x) * g;
+    l1 = (tg * le.y) * g;
+    l2 = (tb * le.z) * g;
+    return true;
+}
+
+// path_kernel with light sampling, for scenes that hold a light (general kernels only: FULL).  A lane's
+// path gains a shadow phase: after a Lambertian scatter that connects, the lane first traverses the shadow
+// ray (p, w) from the scattered ray's origin, keeping the scattered direction, the connection's radiance
+// and the light's index; when that traversal ends it adds the radiance if the closest hit is the light and
+// goes on along the scattered ray.  Shadow and path segments share the traversal rounds.
+// CAMERA: the renderer's samples in place of the caller's rays (NeeParams).
+template <bool LDS_SCENE, bool WIDE, bool CAMERA>
+__global__ __launch_bounds__(kMeshBlock) void nee_kernel(NeeParams N) {
+    constexpr bool FULL = true;
+    const PathParams &P = N.p;
+    const QueryParams &Q = P.q;
+    const Staged sc = stage_scene<LDS_SCENE, WIDE>(Q.nodes, Q.tris, Q.numNodes, Q.numTris, Q.stackDepth, Q.topBytes);
+    const SpillArea S = lane_spill(Q.spill, Q.spillCap, Q.stackCap);
+    const unsigned per = ((Q.numRays + kQueryShards * 64u - 1u) / (kQueryShards * 64u)) * 64u;
+    unsigned fs = blockIdx.x % kQueryShards, left = kQueryShards;
+    unsigned fsBase = min(fs * per, Q.numRays), fsCount = min((fs + 1u) * per, Q.numRays) - fsBase;
+    unsigned poolNext = 0, poolEnd = 0;
+    unsigned idx = kNone;
+    bool need = true;
+    QueryRay r{};
+    float tmin = 0.0f;
+    const float M = scene_M(Q.pad);
+    uint32_t rng = 0;
+    float tr = 1.0f, tg = 1.0f, tb = 1.0f;
+    int depth = 0, nseg = 0;
+    bool hit0 = false;
+    // light sampling: the radiance gathered so far, whether a light met next emits (the last scatter was
+    // not Lambertian), and the shadow phase's kept values
+    float la0 = 0.0f, la1 = 0.0f, la2 = 0.0f;
+    bool spec = true, shadow = false;
+    float sdx = 0.0f, sdy = 0.0f, sdz = 0.0f, ld0 = 0.0f, ld1 = 0.0f, ld2 = 0.0f;
+    int lk = -1;
+    unsigned long long segsAll = 0, samplesAll = 0;  // CAMERA: the launch counters' share of this lane
+    unsigned shadowAll = 0;                          // (the shadow segments among segsAll)
+    Trav T;
+    begin(T);
+    T.cur = kDone;
+    unsigned long long nvis = 0, ntest = 0;
+    unsigned pc[kProfSlots] = {};
+    for (;;) {
+        while (left && __ballot(need)) {
+            const unsigned qi =
+                wave_fetch(need, poolNext, poolEnd, &Q.counter[fs * kQueryCtrStride], Q.chunk, fsCount);
+            if (need && qi != kNone) {
+                need = false;
+                idx = fsBase + qi;
+                float tmax;
+                bool valid;
+                if (CAMERA) {
+                    camera_sample(Q.cam, Q.firstItem + idx, r, rng);
+                    tmin = 0.001f;
+                    tmax = INFINITY;
+                    valid = query_ray_valid(r, tmin, tmax);
+                } else {
+                    rng = P.seeds[idx];
+                    valid = load_query_ray(Q.rays, idx, r, tmin, tmax);
+                }
+                tr = tg = tb = 1.0f;
+                la0 = la1 = la2 = 0.0f;
+                depth = nseg = 0;
+                hit0 = false;
+                spec = true;
+                shadow = false;
+                begin(T);
+                T.bestO = -1;
+                if (valid) {
+                    prepare_query<FULL, WIDE>(r, M);
+                    T.bestT = tmax;
+                } else {
+                    T.cur = kDone;
+                    depth = -1;
+                }
+            }
+            if (__ballot(need)) {
+                fs = fs + 1 == kQueryShards ? 0u : fs + 1;
+                fsBase = min(fs * per, Q.numRays);
+                fsCount = min((fs + 1u) * per, Q.numRays) - fsBase;
+                poolNext = poolEnd = 0;
+                --left;
+            }
+        }
+        need = false;
+        if (!__any(idx != kNone)) break;
+        if (__any(busy(T))) {
+            do {
+                traverse_step<LDS_SCENE, FULL, WIDE>(T, r, tmin, sc, Q, S, nvis, ntest, pc);
+            } while (__popcll(__ballot(busy(T))) > unsigned(Q.waveThreshold));
+        }
+        if (idx != kNone && !busy(T)) {
+            float L0 = 0.0f, L1 = 0.0f, L2 = 0.0f;
+            bool finished = true;
+            if (shadow) {  // the shadow segment: visible iff its closest hit is the light itself
+                ++nseg;
+                if (CAMERA) ++shadowAll;
+                if (T.bestI == lk) {
+                    la0 += ld0;
+                    la1 += ld1;
+                    la2 += ld2;
+                }
+                shadow = false;
+                finished = false;
+                r.dx = sdx, r.dy = sdy, r.dz = sdz;  // on along the scattered ray
+                prepare_segment(r);
+                begin(T);
+            } else if (depth < 0) {
+                // invalid ray
+            } else if (T.bestI < 0) {
+                sky(r, tr, tg, tb, L0, L1, L2);
+                ++nseg;
+            } else {
+                hit0 = true;
+                ++depth;
+                ++nseg;
+                if (emitted(T.bestI, Q.shade, P.mats, tr, tg, tb, L0, L1, L2)) {
+                    // a light: it emits unless the vertex before it sampled the lights itself
+                    if (!spec) L0 = L1 = L2 = 0.0f;
+                } else if (depth < P.maxDepth) {
+                    float nx, ny, nz;
+                    const int kind = hit_normal_kind(r, T.bestT, T.bestI, Q.shade, sc.tris, P.mats, nx, ny, nz);
+                    if (scatter<FULL, false, -1>(r, T.bestT, T.bestI, Q.shade, sc.tris, P.mats, rng, tr, tg, tb, pc)) {
+                        finished = false;
+                        spec = kind != kLambertian;
+                        float wx, wy, wz;
+                        if (!spec && light_connect(N.lights, N.numLights, Q.shade, sc.tris, P.mats, r.ox, r.oy, r.oz, nx, ny,
+                                                   nz, tr, tg, tb, rng, pc, wx, wy, wz, ld0, ld1, ld2, lk)) {
+                            shadow = true;
+                            sdx = r.dx, sdy = r.dy, sdz = r.dz;
+                            r.dx = wx, r.dy = wy, r.dz = wz;
+                        }
+                        prepare_segment(r);
+                        begin(T);
+                        tmin = 0.001f;
+                    }
+                }
+            }
+            if (finished) {
+                L0 = la0 + L0;
+                L1 = la1 + L1;
+                L2 = la2 + L2;
+                if (CAMERA) {
+                    store_radiance(N.scratch, idx, L0, L1, L2);
+                    segsAll += unsigned(nseg);
+                    ++samplesAll;
+                } else {
+                    P.radiance[idx] = float4{L0, L1, L2, hit0 ? 1.0f : 0.0f};
+                    if (P.segments) P.segments[idx] = nseg;
+                }
+                idx = kNone;
+                need = true;
+            }
+        }
+    }
+    if (CAMERA) {
+        segsAll = wave_sum(segsAll);
+        samplesAll = wave_sum(samplesAll);
+        const unsigned long long shadows = wave_sum((unsigned long long)shadowAll);
+        if (__lane_id() == 0) {
+            unsigned long long *const st = stat_slot(N.stats);
+            atomicAdd(&st[0], segsAll);
+            atomicAdd(&st[1], samplesAll);
+            atomicAdd(&st[kStatShadowRays], shadows);
+        }
+    }
+}
+
+using NeeFn = void (*)(NeeParams);
+template <bool CAMERA>
+NeeFn nee_fn_of(const QueryParams &q) {
+    switch ((q.ldsScene ? 2 : 0) | (q.wide ? 1 : 0)) {
+    case 0: return nee_kernel<false, false, CAMERA>;
+    case 1: return nee_kernel<false, true, CAMERA>;
+    case 2: return nee_kernel<true, false, CAMERA>;
+    default: return nee_kernel<true, true, CAMERA>;
+    }
+}
+NeeFn nee_fn(const NeeParams &p) { return p.scratch ? nee_fn_of<true>(p.p.q) : nee_fn_of<false>(p.p.q); }
+
 constexpr int kCameraRaysBlock = 256;
 __global__ __launch_bounds__(kCameraRaysBlock) void camera_rays_kernel(CameraRaysParams P) {
     const unsigned i = blockIdx.x * unsigned(kCameraRaysBlock) + threadIdx.x;
@@ -156,6 +409,19 @@ hipError_t launch_path(const PathParams &p, int blocks, hipStream_t s) {
 }
 
 int path_blocks_per_cu(const PathParams &p) { return ray_kernel_blocks_per_cu(path_fn(p.q), p.q); }
+
+hipError_t launch_nee(const NeeParams &p, int blocks, hipStream_t s) {
+    const QueryParams &q = p.p.q;
+    if (!query_params_ok(q, blocks)) return hipErrorInvalidValue;
+    if (!q.shade || !p.p.mats || !q.full || !p.lights || p.numLights < 1 || p.p.maxDepth < 1) return hipErrorInvalidValue;
+    if (p.scratch ? !p.stats
+                  : (!q.rays || !p.p.seeds || !p.p.radiance || reinterpret_cast<uintptr_t>(q.rays) % 16 ||
+                     reinterpret_cast<uintptr_t>(p.p.radiance) % 16))
+        return hipErrorInvalidValue;
+    return launch_ray_kernel(nee_fn(p), q, p, blocks, s);
+}
+
+int nee_blocks_per_cu(const NeeParams &p) { return ray_kernel_blocks_per_cu(nee_fn(p), p.p.q); }
 
 hipError_t launch_camera_rays(const CameraRaysParams &p, hipStream_t s) {
     if ((!p.rays && !p.seeds) || p.numRays == 0 || p.numRays > (1u << 31) || reinterpret_cast<uintptr_t>(p.rays) % 16)

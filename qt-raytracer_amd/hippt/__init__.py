@@ -63,6 +63,7 @@ OPT_QUERY_SLICE = 33
 OPT_RENDER_PAD = 34
 OPT_SKY_RECT = 35
 OPT_DENOISE_TIMING = 36
+OPT_LIGHT_SAMPLING = 37  # next-event estimation at Lambertian vertices (include/hippt.h; 0 default)
 OPT_PIXEL_FORMAT = 25
 PIXEL_ARGB = 0
 PIXEL_RGBA8 = 1
@@ -73,6 +74,8 @@ INFO_CHAIN_CAP = 103
 INFO_UPDATE_DROPPED = 104
 INFO_RENDER_PAD = 105
 INFO_SKY_RECT_PIXELS = 106
+INFO_LIGHTS = 107  # emissive primitives in the uploaded scene
+INFO_LIGHT_SAMPLING = 108  # 1 if the last render took the light-sampling route
 INFO_DENOISE_NS = 200
 RAYS_DEVICE = 1
 HIT_SPHERE = 1 << 30
@@ -696,6 +699,8 @@ class PathTracer:
         out["culled_by_best_t"] = v[25]
         # node visits served by the LDS copy of the top of a global-memory tree
         out["lds_top_visits"] = v[26] if len(v) > 26 else 0
+        # shadow rays among `segments` (renders under OPT_LIGHT_SAMPLING)
+        out["shadow_rays"] = v[27] if len(v) > 27 else 0
         return out
 
     def resetStats(self) -> None:  # noqa: N802

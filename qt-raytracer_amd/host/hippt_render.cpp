@@ -5,7 +5,7 @@
 //   hippt_render [--backend cuda|vulkan|gl] [--mesh FILE.obj|.ply] [--albedo r,g,b[;r,g,b...]]
 //                [--emit NAME=r,g,b[;NAME=r,g,b...]] [--width W] [--height H] [--spp N] [--depth D] [--per-frame] [--present]
 //                [--out FILE] [--ppm FILE.ppm] [--pick X,Y] [--denoise PASSES]
-//                [--radiance-in FILE|camera --radiance-out FILE]
+//                [--radiance-in FILE|camera --radiance-out FILE] [--light-sampling]
 //
 // --backend cuda (default): HipPathTracer, the CudaPathTracer interface.  Without --mesh: the
 // reference kernel's built-in 4-sphere scene, one renderFrame per frame (the CUDA backend's
@@ -13,6 +13,8 @@
 // frames in one renderFrames call, or one call per frame with --per-frame, or through the
 // non-blocking hand-off with --present.
 // --emit (with --mesh): the named OBJ `usemtl` groups are area lights of that radiance (HIPPT_MAT_EMISSIVE).
+// --light-sampling: HIPPT_OPT_LIGHT_SAMPLING 1 (next-event estimation towards those lights) for the render
+// and --radiance-out.
 // --backend vulkan: HipVulkanPathTracer, one renderFrame(depth) per frame (the app's "vulkan"
 // branch, RayTracerFboItem.cpp:576-600).  --backend gl: HipGpuPathTracer, initialize + resize,
 // then renderFrame(N, depth) once (or per frame with --per-frame), as the GL branch calls it.
@@ -48,7 +50,7 @@ int usage() {
                  "                    [--emit NAME=r,g,b[;...]]\n"
                  "                    [--height H] [--spp N] [--depth D] [--per-frame] [--present] [--out FILE]\n"
                  "                    [--ppm FILE.ppm] [--pick X,Y] [--update-mesh FILE] [--denoise PASSES]\n"
-                 "                    [--radiance-in FILE|camera --radiance-out FILE]\n");
+                 "                    [--radiance-in FILE|camera --radiance-out FILE] [--light-sampling]\n");
     return 2;
 }
 
@@ -71,13 +73,14 @@ std::vector<float> parse_floats(const std::string &s) {
 int main(int argc, char **argv) {
     std::string mesh, out, ppm, albedoArg, emitArg, pickArg, updateMesh, radianceIn, radianceOut, backend = "cuda";
     int width = 320, height = 180, spp = 16, depth = 8, denoise = -1;
-    bool perFrame = false, present = false;
+    bool perFrame = false, present = false, lightSampling = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char * { return i + 1 < argc ? argv[++i] : nullptr; };
         const char *v = nullptr;
         if (a == "--per-frame") perFrame = true;
         else if (a == "--present") present = true;
+        else if (a == "--light-sampling") lightSampling = true;
         else if ((v = next()) == nullptr) return usage();
         else if (a == "--backend") backend = v;
         else if (a == "--mesh") mesh = v;
@@ -98,6 +101,7 @@ int main(int argc, char **argv) {
     }
     if (backend != "cuda" && backend != "vulkan" && backend != "gl") return usage();
     HipPathTracer tracer;
+    hipptSetOption(HIPPT_OPT_LIGHT_SAMPLING, lightSampling ? 1 : 0);
     if (!mesh.empty()) {
         // the scene is the library's (shared by every interface)
         const double from[3] = {278, 278, -800}, at[3] = {278, 278, 0}, up[3] = {0, 1, 0};
