@@ -101,8 +101,11 @@ struct OccKey {
     int version = -1, stackDepth = 0, fmt = 0, poolWords = 0;
     unsigned topBytes = 0;
     bool ldsScene = false, full = false, spills = false;
-    int variant = 0;  // queries: the QueryMode, 8 for a path query
+    int variant = 0;  // ray-per-lane launches: the QueryMode, or a path kernel's route (kVariantPath ...)
 };
+// The path kernel's routes as OccKey variants, after the QueryModes: plain paths, light-sampled path
+// queries, the light-sampling render route.
+constexpr int kVariantPath = 8, kVariantLitPath = 9, kVariantLitRender = 10;
 
 bool same_key(const OccKey &a, const OccKey &b) {
     return a.version == b.version && a.stackDepth == b.stackDepth && a.fmt == b.fmt && a.poolWords == b.poolWords &&
@@ -131,6 +134,17 @@ struct CostJob {
         std::unique_lock<std::mutex> g(mu);
         cv.wait(g, [this] { return done; });
     }
+};
+
+// What the ray-per-lane launches of one route (hippt_ray_loop.h) keep on a context: the resident blocks
+// per CU of the route's kernel, the launch's claim counters and the 4-wide traversal's spill area.
+// Allocated on first use (ensure_ray_launch), freed with the context.
+struct RayLaunch {
+    OccKey occKey;  // of blocksPerCu
+    int blocksPerCu = 0;
+    unsigned *ctr = nullptr;
+    int *spill = nullptr;
+    size_t spillBytes = 0;
 };
 
 struct Ctx {
@@ -252,23 +266,15 @@ struct Ctx {
     // their own (a render's may be in use by launches queued before the query, and growing it would
     // wait for them), the staging buffers of one slice of a host-memory batch (rays in, results out),
     // and the event a call waits on.  Allocated on first use, freed with the context.
-    unsigned *qCtr = nullptr;
-    int *qSpill = nullptr;
-    size_t qSpillBytes = 0;
+    RayLaunch qLaunch;
     void *qStage = nullptr;
     size_t qStageBytes = 0;
     hipEvent_t qDone = nullptr;
-    OccKey qOccKey;  // of qBlocksPerCu
-    int qBlocksPerCu = 0;
     // Light sampling (HIPPT_OPT_LIGHT_SAMPLING): the scene's light list (SceneHost::lights; a scene buffer),
     // and what the render route's launches take in place of the queries' (an asynchronous render may still
-    // be in flight when a query grows qSpill): claim counters, spill area, resident blocks per CU.
+    // be in flight when a query grows qLaunch.spill): claim counters, spill area, resident blocks per CU.
     int *lights = nullptr;
-    unsigned *neeCtr = nullptr;
-    int *neeSpill = nullptr;
-    size_t neeSpillBytes = 0;
-    OccKey neeOccKey;  // of neeBlocksPerCu
-    int neeBlocksPerCu = 0;
+    RayLaunch litLaunch;
     // Denoiser (hipptDenoise, hippt_denoise.h): one buffer of 80 bytes per pixel (the guide sample's hit
     // records, two colour buffers, the guide), allocated at first use, reused while large enough and
     // freed with the context; the stages' timing events (HIPPT_OPT_DENOISE_TIMING), created on use.
@@ -797,10 +803,10 @@ void destroy_ctx(Ctx &c, bool keep) {
     drop(c.spill, c.spillBytes);
     c.spill = nullptr;
     c.spillBytes = 0;
-    (void)hipFree(c.qCtr);
-    (void)hipFree(c.qSpill);
-    (void)hipFree(c.neeCtr);
-    (void)hipFree(c.neeSpill);
+    for (RayLaunch *r : {&c.qLaunch, &c.litLaunch}) {
+        (void)hipFree(r->ctr);
+        (void)hipFree(r->spill);
+    }
     (void)hipFree(c.qStage);
     if (c.qDone) (void)hipEventDestroy(c.qDone);
     (void)hipFree(c.dnBuf);
@@ -866,6 +872,27 @@ bool next_events(Ctx &c, EventPair &ev, const char **err) {
     ev = c.freeEv.back();
     c.freeEv.pop_back();
     return true;
+}
+
+// One launch on c.stream between a pair of timing events, to be accounted as `kind` (0 trace / 1 combine)
+// once it has finished.  `what`: the launch's expression, for the failure text (as HIP_TRY's).
+template <class F>
+bool timed_launch(Ctx &c, int kind, const char *what, const char **err, F launch) {
+    EventPair ev;
+    if (!next_events(c, ev, err)) return false;
+    HIP_TRY(hipEventRecord(ev.a, c.stream));
+    const hipError_t e = launch();
+    if (e != hipSuccess) return fail(err, std::string(what) + ": " + hipGetErrorString(e));
+    HIP_TRY(hipEventRecord(ev.b, c.stream));
+    c.pending.push_back({kind, ev});
+    return true;
+}
+#define TIMED_LAUNCH(c, kind, expr) timed_launch(c, kind, #expr, err, [&] { return (expr); })
+
+// Blocks of a persistent launch of kMeshBlock threads over `items` items: what is resident at
+// blocksPerCu blocks per CU, no more than the items fill, at least one.
+long long ray_blocks(const Ctx &c, int blocksPerCu, long long items) {
+    return std::max(1LL, std::min<long long>((long long)c.cus * blocksPerCu, (items + hippt::kMeshBlock - 1) / hippt::kMeshBlock));
 }
 
 // Adds a finished launch's event time to the stats and recycles its events.
@@ -1418,13 +1445,7 @@ bool flush_chain(Ctx &c, const char **err) {
         a.hdr[11] = ch.seq > hippt::kAuditBatches ? ch.seq - hippt::kAuditBatches : 0u;
         a.closed = true;
     }
-    EventPair ev;
-    if (!next_events(c, ev, err)) return false;
-    HIP_TRY(hipEventRecord(ev.a, c.stream));
-    HIP_TRY(hippt::launch_chain_flush(f, c.stream));
-    HIP_TRY(hipEventRecord(ev.b, c.stream));
-    c.pending.push_back({1, ev});
-    return true;
+    return TIMED_LAUNCH(c, 1, hippt::launch_chain_flush(f, c.stream));
 }
 
 // The deferred combine of a context as a launch of its own (see Ctx::deferred), or the open chain
@@ -1434,12 +1455,7 @@ bool flush_deferred(Ctx &c, const char **err) {
     if (!c.hasDeferred) return true;
     c.hasDeferred = false;
     HIP_TRY(hipSetDevice(c.device));
-    EventPair ev;
-    if (!next_events(c, ev, err)) return false;
-    HIP_TRY(hipEventRecord(ev.a, c.stream));
-    HIP_TRY(hippt::launch_combine(c.deferred, c.stream, c.deferredHost));
-    HIP_TRY(hipEventRecord(ev.b, c.stream));
-    c.pending.push_back({1, ev});
+    if (!TIMED_LAUNCH(c, 1, hippt::launch_combine(c.deferred, c.stream, c.deferredHost))) return false;
     c.deferredHost = hippt::HostFrame{};
     return true;
 }
@@ -1594,14 +1610,9 @@ bool launch_chained(Ctx &c, hippt::MeshParams &p, const char **err) {
     ch.pendN = 0;
     if (!c.chainStartEv) HIP_TRY(hipEventCreateWithFlags(&c.chainStartEv, hipEventDisableTiming));
     if (!c.chainEndEv) HIP_TRY(hipEventCreateWithFlags(&c.chainEndEv, hipEventDisableTiming));
-    EventPair ev;
-    if (!next_events(c, ev, err)) return false;
     HIP_TRY(hipEventRecord(c.chainStartEv, c.stream));
-    HIP_TRY(hipEventRecord(ev.a, c.stream));
-    HIP_TRY(hippt::launch_mesh(p, int(ch.blocks), false, c.stream));
-    HIP_TRY(hipEventRecord(ev.b, c.stream));
+    if (!TIMED_LAUNCH(c, 0, hippt::launch_mesh(p, int(ch.blocks), false, c.stream))) return false;
     HIP_TRY(hipEventRecord(c.chainEndEv, c.stream));
-    c.pending.push_back({0, ev});
     return true;
 }
 
@@ -1816,13 +1827,7 @@ bool enqueue_sphere4(Ctx &c, int firstFrame, int count, int maxDepth, bool copy,
         p.hostOut = host_frame_on_device(dst);
         *copied = p.hostOut != nullptr;  // else the copy after the kernel
     }
-    EventPair ev;
-    if (!next_events(c, ev, err)) return false;
-    HIP_TRY(hipEventRecord(ev.a, c.stream));
-    HIP_TRY(hippt::launch_sphere4(p, c.stream));
-    HIP_TRY(hipEventRecord(ev.b, c.stream));
-    c.pending.push_back({0, ev});
-    return true;
+    return TIMED_LAUNCH(c, 0, hippt::launch_sphere4(p, c.stream));
 }
 
 // HIPPT_OPT_LIGHT_SAMPLING as applied: on, and the scene holds an emissive primitive (else the option-off
@@ -2010,9 +2015,7 @@ bool enqueue_mesh(Ctx &c, const CameraF &cam, int firstFrame, int count, int max
             if (s.knobs.pathMode == 1) {
                 if (!run_wavefront(c, p, cnt, L.spills, L.spillCap, err)) return false;
             } else {
-                long long blocks = (long long)c.cus * (chained && s.blocksPerCu <= 0 ? c.meshBlocksPerCuChain : bpc);
-                blocks = std::min<long long>(blocks, (total + hippt::kMeshBlock - 1) / hippt::kMeshBlock);
-                blocks = std::max<long long>(blocks, 1);
+                const long long blocks = ray_blocks(c, chained && s.blocksPerCu <= 0 ? c.meshBlocksPerCuChain : bpc, total);
                 if (!ensure_spill(c, p, blocks, L.spills, L.spillCap, err)) return false;
                 s.activeChunk = int(p.chunk);
                 s.activeChainCap = 0;
@@ -2030,12 +2033,7 @@ bool enqueue_mesh(Ctx &c, const CameraF &cam, int firstFrame, int count, int max
                     }
                     p.combCtr = c.queue + kCombCtrWord;
                 }
-                EventPair ev;
-                if (!next_events(c, ev, err)) return false;
-                HIP_TRY(hipEventRecord(ev.a, c.stream));
-                HIP_TRY(hippt::launch_mesh(p, int(blocks), cnt, c.stream));
-                HIP_TRY(hipEventRecord(ev.b, c.stream));
-                c.pending.push_back({0, ev});
+                if (!TIMED_LAUNCH(c, 0, hippt::launch_mesh(p, int(blocks), cnt, c.stream))) return false;
             }
         }
         if (chained && maxDepth > 0) continue;  // its combine belongs to the run (Ctx::chain)
@@ -2236,48 +2234,61 @@ plan::Layout query_scene_params(Ctx &c, hippt::QueryParams &q) {
     return L;
 }
 
+// The camera sample's arguments for `cam` over the image rows y0, y0 + rowStride, ... (bandPixels pixels
+// of them), items frame-major from firstFrame.
+hippt::QueryCam query_cam(const CameraF &cam, int y0, int rowStride, unsigned bandPixels, int firstFrame) {
+    State &s = S();
+    hippt::QueryCam k{};
+    k.cam = cam;
+    k.invW = 1.0f / float(std::max(1, s.width - 1));
+    k.invH = 1.0f / float(std::max(1, s.height - 1));
+    k.width = s.width;
+    k.y0 = y0;
+    k.rowStride = rowStride;
+    k.firstFrame = firstFrame;
+    k.bandPixels = bandPixels;
+    k.rcpBandPixels = 1.0f / float(bandPixels);
+    k.rcpWidth = 1.0f / float(s.width);
+    return k;
+}
+
+// Makes `r` ready for launches of kernel `variant` (a QueryMode or kVariantPath ...) over q, the current
+// scene's parameters under layout L (query_scene_params): the kernel's resident blocks per CU, the claim
+// counters and, a 4-wide tree, a spill area for every resident lane, set in q.
+bool ensure_ray_launch(Ctx &c, RayLaunch &r, const plan::Layout &L, int variant, hippt::QueryParams &q, const char **err) {
+    OccKey occKey;
+    occKey.version = S().scene.version, occKey.stackDepth = L.stackDepth, occKey.fmt = L.fmt, occKey.topBytes = L.topBytes;
+    occKey.ldsScene = L.ldsScene, occKey.full = q.full != 0;
+    occKey.variant = variant;
+    if (!same_key(r.occKey, occKey)) {
+        // (the pointers select the kernel: any non-null scratch the render route's)
+        const hippt::PathParams pp{q, c.mats, nullptr, nullptr, nullptr, 1, variant >= kVariantLitPath ? c.lights : nullptr, 1,
+                                   variant == kVariantLitRender ? reinterpret_cast<float *>(c.stats) : nullptr, nullptr};
+        r.blocksPerCu = variant >= kVariantPath ? hippt::path_blocks_per_cu(pp)
+                                                : hippt::query_blocks_per_cu(q, hippt::QueryMode(variant));
+        r.occKey = occKey;
+    }
+    if (!r.ctr) HIP_TRY(hipMalloc(&r.ctr, hippt::kQueryCtrBytes));
+    if (L.wide) {
+        const size_t bytes = size_t(c.cus) * size_t(r.blocksPerCu) * hippt::kMeshBlock * size_t(q.spillCap) * sizeof(int);
+        // a render route's earlier batches use the old area (no query is in flight: every call waits for its own)
+        if (&r == &c.litLaunch && r.spillBytes < bytes) HIP_TRY(hipStreamSynchronize(c.stream));
+        if (!grow(reinterpret_cast<void **>(&r.spill), &r.spillBytes, bytes, "hipMalloc(&r.spill, bytes)", err)) return false;
+        q.spill = r.spill;
+    }
+    q.counter = r.ctr;
+    return true;
+}
+
 bool query_setup(Ctx &c, const QueryCall &call, hippt::QueryParams &q, const char **err) {
     State &s = S();
     const plan::Layout L = query_scene_params(c, q);
-    const plan::Facts f = scene_facts(s.scene);
-    if (call.camera()) {
-        hippt::QueryCam &k = q.cam;
-        k.cam = current_camera();
-        k.invW = 1.0f / float(std::max(1, s.width - 1));
-        k.invH = 1.0f / float(std::max(1, s.height - 1));
-        k.width = s.width;
-        k.y0 = 0;
-        k.rowStride = 1;
-        k.firstFrame = call.frame;
-        k.bandPixels = unsigned(s.width) * unsigned(s.height);
-        k.rcpBandPixels = 1.0f / float(k.bandPixels);
-        k.rcpWidth = 1.0f / float(s.width);
-    }
+    if (call.camera()) q.cam = query_cam(current_camera(), 0, 1, unsigned(s.width) * unsigned(s.height), call.frame);
     HIP_TRY(hipSetDevice(c.device));
     if (!c.qDone) HIP_TRY(hipEventCreateWithFlags(&c.qDone, hipEventDisableTiming));
     if (call.camRays) return true;  // no traversal: the camera alone
-    OccKey occKey;
-    occKey.version = s.scene.version, occKey.stackDepth = L.stackDepth, occKey.fmt = L.fmt, occKey.topBytes = L.topBytes;
-    occKey.ldsScene = L.ldsScene, occKey.full = f.full;
-    const bool nee = call.path && light_sampling_applies();
-    occKey.variant = call.path ? (nee ? 9 : 8) : int(call.mode);
-    if (!same_key(c.qOccKey, occKey)) {
-        const hippt::PathParams pp{q, c.mats, nullptr, nullptr, nullptr, 1};
-        c.qBlocksPerCu = nee         ? hippt::nee_blocks_per_cu(hippt::NeeParams{pp, c.lights, 1, nullptr, nullptr})
-                         : call.path ? hippt::path_blocks_per_cu(pp)
-                                     : hippt::query_blocks_per_cu(q, call.mode);
-        c.qOccKey = occKey;
-    }
-    if (!c.qCtr) HIP_TRY(hipMalloc(&c.qCtr, hippt::kQueryCtrBytes));
-    if (L.wide) {
-        const size_t bytes = size_t(c.cus) * size_t(c.qBlocksPerCu) * hippt::kMeshBlock * size_t(q.spillCap) * sizeof(int);
-        // (no query is in flight: every call waits for its own)
-        if (!grow(reinterpret_cast<void **>(&c.qSpill), &c.qSpillBytes, bytes, "hipMalloc(&c.qSpill, bytes)", err))
-            return false;
-        q.spill = c.qSpill;
-    }
-    q.counter = c.qCtr;
-    return true;
+    const int variant = !call.path ? int(call.mode) : light_sampling_applies() ? kVariantLitPath : kVariantPath;
+    return ensure_ray_launch(c, c.qLaunch, L, variant, q, err);
 }
 
 // The light-sampling render route (HIPPT_OPT_LIGHT_SAMPLING on a scene with a light): each
@@ -2291,39 +2302,13 @@ bool enqueue_mesh_lights(Ctx &c, const CameraF &cam, int firstFrame, int count, 
     const BatchSize size = frames_per_batch(bandPixels, count);
     hippt::QueryParams q;
     const plan::Layout L = query_scene_params(c, q);
-    hippt::QueryCam &k = q.cam;
-    k.cam = cam;
-    k.invW = 1.0f / float(std::max(1, s.width - 1));
-    k.invH = 1.0f / float(std::max(1, s.height - 1));
-    k.width = s.width;
-    k.y0 = c.y0;
-    k.rowStride = c.stride;
-    k.bandPixels = bandPixels;
-    k.rcpBandPixels = 1.0f / float(bandPixels);
-    k.rcpWidth = 1.0f / float(s.width);
-    hippt::NeeParams np{hippt::PathParams{q, c.mats, nullptr, nullptr, nullptr, maxDepth}, c.lights,
-                        int(s.scene.lights.size()), nullptr, c.stats};
-    OccKey occKey;
-    occKey.version = s.scene.version, occKey.stackDepth = L.stackDepth, occKey.fmt = L.fmt, occKey.topBytes = L.topBytes;
-    occKey.ldsScene = L.ldsScene, occKey.full = true;
-    occKey.variant = 10;
-    if (!same_key(c.neeOccKey, occKey)) {
-        np.scratch = reinterpret_cast<float *>(c.stats);  // (any non-null pointer: selects the camera kernels)
-        c.neeBlocksPerCu = hippt::nee_blocks_per_cu(np);
-        c.neeOccKey = occKey;
-    }
-    if (!c.neeCtr) HIP_TRY(hipMalloc(&c.neeCtr, hippt::kQueryCtrBytes));
-    if (L.wide) {
-        const size_t bytes = size_t(c.cus) * size_t(c.neeBlocksPerCu) * hippt::kMeshBlock * size_t(q.spillCap) * sizeof(int);
-        if (c.neeSpillBytes < bytes) HIP_TRY(hipStreamSynchronize(c.stream));  // earlier batches use the old one
-        if (!grow(reinterpret_cast<void **>(&c.neeSpill), &c.neeSpillBytes, bytes, "hipMalloc(&c.neeSpill, bytes)", err))
-            return false;
-        np.p.q.spill = c.neeSpill;
-    }
-    np.p.q.counter = c.neeCtr;
+    q.cam = query_cam(cam, c.y0, c.stride, bandPixels, firstFrame);
+    RayLaunch &R = c.litLaunch;
+    if (!ensure_ray_launch(c, R, L, kVariantLitRender, q, err)) return false;
+    hippt::PathParams np{q, c.mats, nullptr, nullptr, nullptr, maxDepth, c.lights, int(s.scene.lights.size()), nullptr, c.stats};
     s.activeWidth = L.wide ? 4 : 2;
     s.activeTopBytes = L.topBytes;
-    s.activeBlocksPerCu = c.neeBlocksPerCu;
+    s.activeBlocksPerCu = R.blocksPerCu;
     s.activeChainCap = 0;
     s.activeRenderPad = 0;
     s.activeSkyPixels = 0;
@@ -2335,21 +2320,15 @@ bool enqueue_mesh_lights(Ctx &c, const CameraF &cam, int firstFrame, int count, 
         float *scratch = nullptr;
         if (!batch_scratch(c, size.need, &scratch, err)) return false;
         np.scratch = scratch;
-        hippt::QueryParams &bq = np.p.q;
+        hippt::QueryParams &bq = np.q;
         bq.cam.firstFrame = firstFrame + b;
         bq.numRays = total;
         bq.firstItem = 0;
         bq.chunk = plan::query_chunk(total);
         s.activeChunk = int(bq.chunk);
-        const long long blocks = std::max(
-            1LL, std::min<long long>((long long)c.cus * c.neeBlocksPerCu, (total + hippt::kMeshBlock - 1) / hippt::kMeshBlock));
-        HIP_TRY(hipMemsetAsync(c.neeCtr, 0, hippt::kQueryCtrBytes, c.stream));
-        EventPair ev;
-        if (!next_events(c, ev, err)) return false;
-        HIP_TRY(hipEventRecord(ev.a, c.stream));
-        HIP_TRY(hippt::launch_nee(np, int(blocks), c.stream));
-        HIP_TRY(hipEventRecord(ev.b, c.stream));
-        c.pending.push_back({0, ev});
+        const long long blocks = ray_blocks(c, R.blocksPerCu, total);
+        HIP_TRY(hipMemsetAsync(R.ctr, 0, hippt::kQueryCtrBytes, c.stream));
+        if (!TIMED_LAUNCH(c, 0, hippt::launch_path(np, int(blocks), c.stream))) return false;
         c.deferred = hippt::CombineParams{c.accum, c.out, scratch, bandPixels, total, firstFrame + b, nf, s.pixelFormat};
         c.hasDeferred = true;
     }
@@ -2367,19 +2346,17 @@ bool query_enqueue(Ctx &c, hippt::QueryParams q, unsigned first, unsigned m, con
     q.numRays = m;
     q.firstItem = first;
     q.chunk = plan::query_chunk(m);
-    const long long blocks =
-        std::max(1LL, std::min<long long>((long long)c.cus * c.qBlocksPerCu, (m + hippt::kMeshBlock - 1) / hippt::kMeshBlock));
-    HIP_TRY(hipMemsetAsync(c.qCtr, 0, hippt::kQueryCtrBytes, c.stream));
-    if (call.path && light_sampling_applies())
-        HIP_TRY(hippt::launch_nee(
-            hippt::NeeParams{hippt::PathParams{q, c.mats, pp.seeds, pp.radiance, pp.segments, call.maxDepth}, c.lights,
-                             int(S().scene.lights.size()), nullptr, nullptr},
-            int(blocks), c.stream));
-    else if (call.path)
-        HIP_TRY(hippt::launch_path(hippt::PathParams{q, c.mats, pp.seeds, pp.radiance, pp.segments, call.maxDepth}, int(blocks),
-                                   c.stream));
-    else
+    const long long blocks = ray_blocks(c, c.qLaunch.blocksPerCu, m);
+    HIP_TRY(hipMemsetAsync(c.qLaunch.ctr, 0, hippt::kQueryCtrBytes, c.stream));
+    if (call.path) {
+        const bool lit = light_sampling_applies();
+        HIP_TRY(hippt::launch_path(hippt::PathParams{q, c.mats, pp.seeds, pp.radiance, pp.segments, call.maxDepth,
+                                                     lit ? c.lights : nullptr, lit ? int(S().scene.lights.size()) : 0, nullptr,
+                                                     nullptr},
+                                   int(blocks), c.stream));
+    } else {
         HIP_TRY(hippt::launch_query(q, int(blocks), call.mode, c.stream));
+    }
     return true;
 }
 

@@ -225,7 +225,7 @@ size_t mesh_lds_scene_limit();
 // wave's end-of-launch atomics on one cache line: ~50 us of each megakernel launch's tail
 // (7168 waves x 2), and ~0.3 ms of a 1080p legacy frame (32k waves).
 constexpr int kStatWords = 32, kStatSlots = 64;
-// [27]: shadow rays among word 0's segments (the light-sampling render route, hippt_path.hip nee_kernel)
+// [27]: shadow rays among word 0's segments (the light-sampling render route, hippt_path.hip path_kernel)
 constexpr int kStatShadowRays = 27;
 // megakernel work queues (one per XCD; hippt_trace.h queue_start splits the items evenly)
 constexpr unsigned kMeshQueues = 8;

@@ -11,6 +11,14 @@ namespace hippt {
 // launch (hippt_query.h: scene, rays, claim counters, spill area, layout, shade records) whose result
 // pointers (t, prim, occluded, hits) and camera are not used.  Every pointer is device memory of the
 // launch's device.
+//
+// Light sampling (HIPPT_OPT_LIGHT_SAMPLING; DESIGN.md §2 "Light sampling", §16): with `lights` the launch
+// makes one connection to a light at every Lambertian vertex (null: plain paths).  `lights`: the leaf-order
+// indices of the scene's emissive primitives in ascending uploaded id, numLights >= 1 of them; q.full is
+// set.  With `scratch` null it is a path query as above; with `scratch` (light sampling only) it is a
+// render batch: sample i is camera_sample(q.cam, q.firstItem + i), its radiance goes to
+// scratch[3 i .. 3 i + 2] (the combine's layout) and the segments and samples are added to `stats`
+// (hippt_device.h kStatWords).
 struct PathParams {
     QueryParams q;
     const float4 *mats;     // MeshParams::mats
@@ -18,27 +26,14 @@ struct PathParams {
     float4 *radiance;
     int *segments;
     int maxDepth;
-};
-
-hipError_t launch_path(const PathParams &p, int blocks, hipStream_t s);
-int path_blocks_per_cu(const PathParams &p);
-
-// Light sampling (HIPPT_OPT_LIGHT_SAMPLING; DESIGN.md §2 "Light sampling", §16): the same launch with one
-// connection to a light at every Lambertian vertex.  `lights`: the leaf-order indices of the scene's
-// emissive primitives in ascending uploaded id, numLights >= 1 of them.  With `scratch` null it is a path
-// query (p.q.rays, p.seeds in, p.radiance, p.segments out); with `scratch` it is a render batch: sample i
-// is camera_sample(p.q.cam, p.q.firstItem + i), its radiance goes to scratch[3 i .. 3 i + 2] (the
-// combine's layout) and the segments and samples are added to `stats` (hippt_device.h kStatWords).
-struct NeeParams {
-    PathParams p;
     const int *lights;
     int numLights;
     float *scratch;
     unsigned long long *stats;
 };
 
-hipError_t launch_nee(const NeeParams &p, int blocks, hipStream_t s);
-int nee_blocks_per_cu(const NeeParams &p);
+hipError_t launch_path(const PathParams &p, int blocks, hipStream_t s);
+int path_blocks_per_cu(const PathParams &p);
 
 // Writes camera_sample's ray of pixels firstItem .. firstItem + numRays - 1 of the image (cam: one frame,
 // the whole image as one band) as (origin, 0.001) (direction, +inf) to rays[2 i], rays[2 i + 1] and the

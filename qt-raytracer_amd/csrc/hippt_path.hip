@@ -16,6 +16,10 @@
 // loop once at most Q.waveThreshold lanes are still traversing, and all lanes whose traversal has
 // finished shade together.  scatter's unit-sphere draw is the plain per-lane loop (TAIL = -1, as the
 // wavefront shade kernel): it is called under per-lane control flow (hit, depth, material).
+//
+// Light sampling (HIPPT_OPT_LIGHT_SAMPLING) and the renderer's own camera start are compile-time flags
+// of the same kernel (NEE, CAMERA): one persistent loop serves plain paths, light-sampled path queries
+// and the light-sampling render route.
 #include "hippt_path.h"
 
 #include "hippt_ray_loop.h"
@@ -23,111 +27,6 @@
 namespace hippt {
 namespace {
 using namespace rayloop;
-
-// LDS_SCENE: the scene copy in LDS (else the tree in global memory, the top of a 4-wide one in LDS);
-// FULL: spheres or materials other than Lambertian present; WIDE: the 4-wide tree.
-template <bool LDS_SCENE, bool FULL, bool WIDE>
-__global__ __launch_bounds__(kMeshBlock) void path_kernel(PathParams P) {
-    const QueryParams &Q = P.q;
-    const Staged sc = stage_scene<LDS_SCENE, WIDE>(Q.nodes, Q.tris, Q.numNodes, Q.numTris, Q.stackDepth, Q.topBytes);
-    const SpillArea S = lane_spill(Q.spill, Q.spillCap, Q.stackCap);
-    // shard k: rays [k * per, (k + 1) * per) below numRays, `per` a multiple of 64 (whole lines)
-    const unsigned per = ((Q.numRays + kQueryShards * 64u - 1u) / (kQueryShards * 64u)) * 64u;
-    unsigned fs = blockIdx.x % kQueryShards, left = kQueryShards;  // the wave's shard; shards not yet found drained
-    unsigned fsBase = min(fs * per, Q.numRays), fsCount = min((fs + 1u) * per, Q.numRays) - fsBase;
-    unsigned poolNext = 0, poolEnd = 0;
-    unsigned idx = kNone;  // this lane's ray
-    bool need = true;
-    QueryRay r{};
-    float tmin = 0.0f;
-    const float M = scene_M(Q.pad);
-    // the path's state: RNG, throughput, segments traced so far that hit (-1: an invalid ray), and
-    // whether segment 0 hit
-    uint32_t rng = 0;
-    float tr = 1.0f, tg = 1.0f, tb = 1.0f;
-    int depth = 0;
-    bool hit0 = false;
-    Trav T;
-    begin(T);
-    T.cur = kDone;
-    unsigned long long nvis = 0, ntest = 0;
-    unsigned pc[kProfSlots] = {};  // phase profile slots (not reported by the queries)
-    for (;;) {
-        while (left && __ballot(need)) {
-            const unsigned qi =
-                wave_fetch(need, poolNext, poolEnd, &Q.counter[fs * kQueryCtrStride], Q.chunk, fsCount);
-            if (need && qi != kNone) {  // a new path: segment 0 starts as a ray query's ray
-                need = false;
-                idx = fsBase + qi;
-                float tmax;
-                rng = P.seeds[idx];  // (before the ray: the three loads are in flight together)
-                const bool valid = load_query_ray(Q.rays, idx, r, tmin, tmax);
-                tr = tg = tb = 1.0f;
-                depth = 0;
-                hit0 = false;
-                // begin_query_ray, with the mark of hipptTraceRays' invalid rays (no segment, (0, 0, 0, 0))
-                // in its branch: set after it, the mark costs path_kernel<false, false, false> 2 VGPRs
-                begin(T);
-                T.bestO = -1;  // a hit at exactly t == tmax loses the tie on the id: tmax is exclusive
-                if (valid) {
-                    prepare_query<FULL, WIDE>(r, M);  // segment 0 may start anywhere
-                    T.bestT = tmax;
-                } else {
-                    T.cur = kDone;
-                    depth = -1;
-                }
-            }
-            if (__ballot(need)) {  // a requesting lane got none: this shard is drained
-                fs = fs + 1 == kQueryShards ? 0u : fs + 1;
-                fsBase = min(fs * per, Q.numRays);
-                fsCount = min((fs + 1u) * per, Q.numRays) - fsBase;
-                poolNext = poolEnd = 0;
-                --left;
-            }
-        }
-        need = false;
-        if (!__any(idx != kNone)) break;
-        if (__any(busy(T))) {
-            do {
-                traverse_step<LDS_SCENE, FULL, WIDE>(T, r, tmin, sc, Q, S, nvis, ntest, pc);
-            } while (__popcll(__ballot(busy(T))) > unsigned(Q.waveThreshold));
-        }
-        if (idx != kNone && !busy(T)) {  // the segment's traversal is finished: po_mesh_sample's loop body
-            float L0 = 0.0f, L1 = 0.0f, L2 = 0.0f;
-            int segs = 0;
-            bool finished = true;
-            if (depth < 0) {
-                // invalid ray
-            } else if (T.bestI < 0) {  // miss: the sky of the segment's direction
-                sky(r, tr, tg, tb, L0, L1, L2);
-                segs = depth + 1;
-            } else {
-                hit0 = true;
-                segs = ++depth;
-                if (FULL && emitted(T.bestI, Q.shade, P.mats, tr, tg, tb, L0, L1, L2)) {
-                    // ends at a light with throughput x emission, whatever the depth
-                } else if (depth < P.maxDepth &&  // depth exhausted or absorbed: contributes 0
-                    scatter<FULL, false, -1>(r, T.bestT, T.bestI, Q.shade, sc.tris, P.mats, rng, tr, tg, tb, pc)) {
-                    finished = false;
-                    prepare_segment(r);  // on a surface of the scene: the renderer's test
-                    begin(T);
-                    tmin = 0.001f;
-                }
-            }
-            if (finished) {
-                P.radiance[idx] = float4{L0, L1, L2, hit0 ? 1.0f : 0.0f};
-                if (P.segments) P.segments[idx] = segs;
-                idx = kNone;
-                need = true;
-            }
-        }
-    }
-}
-
-using PathFn = void (*)(PathParams);
-PathFn path_fn(const QueryParams &q) {
-    return for_scene_layout(q, [](auto lds, auto full, auto wide) -> PathFn { return path_kernel<lds(), full(), wide()>; });
-}
 
 // ---- light sampling (DESIGN.md §2 "Light sampling", §16; tests/nee_ref.py is the statement of record) ----
 // The faced normal scatter() forms at the hit of primitive `prim` at t, and the material's kind: asked
@@ -205,34 +104,42 @@ __device__ __forceinline__ bool light_connect(const int *lights, int numLights, 
     return true;
 }
 
-// path_kernel with light sampling, for scenes that hold a light (general kernels only: FULL).  A lane's
-// path gains a shadow phase: after a Lambertian scatter that connects, the lane first traverses the shadow
-// ray (p, w) from the scattered ray's origin, keeping the scattered direction, the connection's radiance
-// and the light's index; when that traversal ends it adds the radiance if the closest hit is the light and
-// goes on along the scattered ray.  Shadow and path segments share the traversal rounds.
-// CAMERA: the renderer's samples in place of the caller's rays (NeeParams).
-template <bool LDS_SCENE, bool WIDE, bool CAMERA>
-__global__ __launch_bounds__(kMeshBlock) void nee_kernel(NeeParams N) {
-    constexpr bool FULL = true;
-    const PathParams &P = N.p;
+// LDS_SCENE: the scene copy in LDS (else the tree in global memory, the top of a 4-wide one in LDS);
+// FULL: spheres or materials other than Lambertian present; WIDE: the 4-wide tree.
+// NEE: light sampling, for scenes that hold a light (general kernels only: FULL).  A lane's path gains a
+// shadow phase: after a Lambertian scatter that connects, the lane first traverses the shadow ray (p, w)
+// from the scattered ray's origin, keeping the scattered direction, the connection's radiance and the
+// light's index; when that traversal ends it adds the radiance if the closest hit is the light and goes on
+// along the scattered ray.  Shadow and path segments share the traversal rounds.  Everything it adds is
+// under the flag: without it the kernel holds none of the state below "light sampling".
+// CAMERA (with NEE): the renderer's samples in place of the caller's rays (PathParams::scratch).
+template <bool LDS_SCENE, bool FULL, bool WIDE, bool NEE, bool CAMERA>
+__global__ __launch_bounds__(kMeshBlock) void path_kernel(PathParams P) {
+    static_assert(FULL || !NEE, "light sampling has general kernels only");
+    static_assert(NEE || !CAMERA, "the camera start belongs to the light-sampling render route");
     const QueryParams &Q = P.q;
     const Staged sc = stage_scene<LDS_SCENE, WIDE>(Q.nodes, Q.tris, Q.numNodes, Q.numTris, Q.stackDepth, Q.topBytes);
     const SpillArea S = lane_spill(Q.spill, Q.spillCap, Q.stackCap);
+    // shard k: rays [k * per, (k + 1) * per) below numRays, `per` a multiple of 64 (whole lines)
     const unsigned per = ((Q.numRays + kQueryShards * 64u - 1u) / (kQueryShards * 64u)) * 64u;
-    unsigned fs = blockIdx.x % kQueryShards, left = kQueryShards;
+    unsigned fs = blockIdx.x % kQueryShards, left = kQueryShards;  // the wave's shard; shards not yet found drained
     unsigned fsBase = min(fs * per, Q.numRays), fsCount = min((fs + 1u) * per, Q.numRays) - fsBase;
     unsigned poolNext = 0, poolEnd = 0;
-    unsigned idx = kNone;
+    unsigned idx = kNone;  // this lane's ray
     bool need = true;
     QueryRay r{};
     float tmin = 0.0f;
     const float M = scene_M(Q.pad);
+    // the path's state: RNG, throughput, segments traced so far that hit (-1: an invalid ray), and
+    // whether segment 0 hit
     uint32_t rng = 0;
     float tr = 1.0f, tg = 1.0f, tb = 1.0f;
-    int depth = 0, nseg = 0;
+    int depth = 0;
     bool hit0 = false;
-    // light sampling: the radiance gathered so far, whether a light met next emits (the last scatter was
-    // not Lambertian), and the shadow phase's kept values
+    // light sampling: the segments traced so far (shadow segments too), the radiance gathered so far,
+    // whether a light met next emits (the last scatter was not Lambertian), and the shadow phase's kept
+    // values
+    int nseg = 0;
     float la0 = 0.0f, la1 = 0.0f, la2 = 0.0f;
     bool spec = true, shadow = false;
     float sdx = 0.0f, sdy = 0.0f, sdz = 0.0f, ld0 = 0.0f, ld1 = 0.0f, ld2 = 0.0f;
@@ -243,12 +150,12 @@ __global__ __launch_bounds__(kMeshBlock) void nee_kernel(NeeParams N) {
     begin(T);
     T.cur = kDone;
     unsigned long long nvis = 0, ntest = 0;
-    unsigned pc[kProfSlots] = {};
+    unsigned pc[kProfSlots] = {};  // phase profile slots (not reported by the queries)
     for (;;) {
         while (left && __ballot(need)) {
             const unsigned qi =
                 wave_fetch(need, poolNext, poolEnd, &Q.counter[fs * kQueryCtrStride], Q.chunk, fsCount);
-            if (need && qi != kNone) {
+            if (need && qi != kNone) {  // a new path: segment 0 starts as a ray query's ray
                 need = false;
                 idx = fsBase + qi;
                 float tmax;
@@ -259,26 +166,32 @@ __global__ __launch_bounds__(kMeshBlock) void nee_kernel(NeeParams N) {
                     tmax = INFINITY;
                     valid = query_ray_valid(r, tmin, tmax);
                 } else {
-                    rng = P.seeds[idx];
+                    rng = P.seeds[idx];  // (before the ray: the three loads are in flight together)
                     valid = load_query_ray(Q.rays, idx, r, tmin, tmax);
                 }
                 tr = tg = tb = 1.0f;
-                la0 = la1 = la2 = 0.0f;
-                depth = nseg = 0;
+                depth = 0;
                 hit0 = false;
-                spec = true;
-                shadow = false;
+                if (NEE) {
+                    la0 = la1 = la2 = 0.0f;
+                    nseg = 0;
+                    spec = true;
+                    shadow = false;
+                }
+                // begin_query_ray, with the mark of hipptTraceRays' invalid rays (no segment, (0, 0, 0, 0))
+                // in its branch: set after it, the mark costs path_kernel<false, false, false, false, false>
+                // 2 VGPRs
                 begin(T);
-                T.bestO = -1;
+                T.bestO = -1;  // a hit at exactly t == tmax loses the tie on the id: tmax is exclusive
                 if (valid) {
-                    prepare_query<FULL, WIDE>(r, M);
+                    prepare_query<FULL, WIDE>(r, M);  // segment 0 may start anywhere
                     T.bestT = tmax;
                 } else {
                     T.cur = kDone;
                     depth = -1;
                 }
             }
-            if (__ballot(need)) {
+            if (__ballot(need)) {  // a requesting lane got none: this shard is drained
                 fs = fs + 1 == kQueryShards ? 0u : fs + 1;
                 fsBase = min(fs * per, Q.numRays);
                 fsCount = min((fs + 1u) * per, Q.numRays) - fsBase;
@@ -293,10 +206,11 @@ __global__ __launch_bounds__(kMeshBlock) void nee_kernel(NeeParams N) {
                 traverse_step<LDS_SCENE, FULL, WIDE>(T, r, tmin, sc, Q, S, nvis, ntest, pc);
             } while (__popcll(__ballot(busy(T))) > unsigned(Q.waveThreshold));
         }
-        if (idx != kNone && !busy(T)) {
+        if (idx != kNone && !busy(T)) {  // the segment's traversal is finished: po_mesh_sample's loop body
             float L0 = 0.0f, L1 = 0.0f, L2 = 0.0f;
+            int segs = 0;
             bool finished = true;
-            if (shadow) {  // the shadow segment: visible iff its closest hit is the light itself
+            if (NEE && shadow) {  // the shadow segment: visible iff its closest hit is the light itself
                 ++nseg;
                 if (CAMERA) ++shadowAll;
                 if (T.bestI == lk) {
@@ -311,46 +225,54 @@ __global__ __launch_bounds__(kMeshBlock) void nee_kernel(NeeParams N) {
                 begin(T);
             } else if (depth < 0) {
                 // invalid ray
-            } else if (T.bestI < 0) {
+            } else if (T.bestI < 0) {  // miss: the sky of the segment's direction
                 sky(r, tr, tg, tb, L0, L1, L2);
-                ++nseg;
+                segs = depth + 1;
+                if (NEE) ++nseg;
             } else {
                 hit0 = true;
-                ++depth;
-                ++nseg;
-                if (emitted(T.bestI, Q.shade, P.mats, tr, tg, tb, L0, L1, L2)) {
-                    // a light: it emits unless the vertex before it sampled the lights itself
-                    if (!spec) L0 = L1 = L2 = 0.0f;
-                } else if (depth < P.maxDepth) {
-                    float nx, ny, nz;
-                    const int kind = hit_normal_kind(r, T.bestT, T.bestI, Q.shade, sc.tris, P.mats, nx, ny, nz);
+                segs = ++depth;
+                if (NEE) ++nseg;
+                if (FULL && emitted(T.bestI, Q.shade, P.mats, tr, tg, tb, L0, L1, L2)) {
+                    // ends at a light with throughput x emission, whatever the depth; light
+                    // sampling: unless the vertex before it sampled the lights itself
+                    if (NEE && !spec) L0 = L1 = L2 = 0.0f;
+                } else if (depth < P.maxDepth) {  // depth exhausted or absorbed: contributes 0
+                    float nx = 0.0f, ny = 0.0f, nz = 0.0f;
+                    int kind = kLambertian;
+                    if (NEE) kind = hit_normal_kind(r, T.bestT, T.bestI, Q.shade, sc.tris, P.mats, nx, ny, nz);
                     if (scatter<FULL, false, -1>(r, T.bestT, T.bestI, Q.shade, sc.tris, P.mats, rng, tr, tg, tb, pc)) {
                         finished = false;
-                        spec = kind != kLambertian;
-                        float wx, wy, wz;
-                        if (!spec && light_connect(N.lights, N.numLights, Q.shade, sc.tris, P.mats, r.ox, r.oy, r.oz, nx, ny,
-                                                   nz, tr, tg, tb, rng, pc, wx, wy, wz, ld0, ld1, ld2, lk)) {
-                            shadow = true;
-                            sdx = r.dx, sdy = r.dy, sdz = r.dz;
-                            r.dx = wx, r.dy = wy, r.dz = wz;
+                        if (NEE) {
+                            spec = kind != kLambertian;
+                            float wx, wy, wz;
+                            if (!spec && light_connect(P.lights, P.numLights, Q.shade, sc.tris, P.mats, r.ox, r.oy, r.oz, nx,
+                                                       ny, nz, tr, tg, tb, rng, pc, wx, wy, wz, ld0, ld1, ld2, lk)) {
+                                shadow = true;
+                                sdx = r.dx, sdy = r.dy, sdz = r.dz;
+                                r.dx = wx, r.dy = wy, r.dz = wz;
+                            }
                         }
-                        prepare_segment(r);
+                        prepare_segment(r);  // on a surface of the scene: the renderer's test
                         begin(T);
                         tmin = 0.001f;
                     }
                 }
             }
             if (finished) {
-                L0 = la0 + L0;
-                L1 = la1 + L1;
-                L2 = la2 + L2;
+                if (NEE) {  // (not for plain paths: 0 + L is not L for L = -0)
+                    L0 = la0 + L0;
+                    L1 = la1 + L1;
+                    L2 = la2 + L2;
+                    segs = nseg;
+                }
                 if (CAMERA) {
-                    store_radiance(N.scratch, idx, L0, L1, L2);
-                    segsAll += unsigned(nseg);
+                    store_radiance(P.scratch, idx, L0, L1, L2);
+                    segsAll += unsigned(segs);
                     ++samplesAll;
                 } else {
                     P.radiance[idx] = float4{L0, L1, L2, hit0 ? 1.0f : 0.0f};
-                    if (P.segments) P.segments[idx] = nseg;
+                    if (P.segments) P.segments[idx] = segs;
                 }
                 idx = kNone;
                 need = true;
@@ -362,7 +284,7 @@ __global__ __launch_bounds__(kMeshBlock) void nee_kernel(NeeParams N) {
         samplesAll = wave_sum(samplesAll);
         const unsigned long long shadows = wave_sum((unsigned long long)shadowAll);
         if (__lane_id() == 0) {
-            unsigned long long *const st = stat_slot(N.stats);
+            unsigned long long *const st = stat_slot(P.stats);
             atomicAdd(&st[0], segsAll);
             atomicAdd(&st[1], samplesAll);
             atomicAdd(&st[kStatShadowRays], shadows);
@@ -370,17 +292,20 @@ __global__ __launch_bounds__(kMeshBlock) void nee_kernel(NeeParams N) {
     }
 }
 
-using NeeFn = void (*)(NeeParams);
-template <bool CAMERA>
-NeeFn nee_fn_of(const QueryParams &q) {
-    switch ((q.ldsScene ? 2 : 0) | (q.wide ? 1 : 0)) {
-    case 0: return nee_kernel<false, false, CAMERA>;
-    case 1: return nee_kernel<false, true, CAMERA>;
-    case 2: return nee_kernel<true, false, CAMERA>;
-    default: return nee_kernel<true, true, CAMERA>;
-    }
+// The kernel of p's scene layout and route: plain paths in all eight layouts, light sampling in the four
+// general ones (whatever p.q.full says), for a query or a render batch.
+using PathFn = void (*)(PathParams);
+PathFn path_fn(const PathParams &p) {
+    QueryParams q = p.q;
+    if (p.lights) q.full = 1;
+    return for_scene_layout(q, [&p](auto lds, auto full, auto wide) -> PathFn {
+        constexpr bool L = decltype(lds)::value, F = decltype(full)::value, W = decltype(wide)::value;
+        if constexpr (F) {
+            if (p.lights) return p.scratch ? path_kernel<L, F, W, true, true> : path_kernel<L, F, W, true, false>;
+        }
+        return path_kernel<L, F, W, false, false>;
+    });
 }
-NeeFn nee_fn(const NeeParams &p) { return p.scratch ? nee_fn_of<true>(p.p.q) : nee_fn_of<false>(p.p.q); }
 
 constexpr int kCameraRaysBlock = 256;
 __global__ __launch_bounds__(kCameraRaysBlock) void camera_rays_kernel(CameraRaysParams P) {
@@ -401,27 +326,17 @@ __global__ __launch_bounds__(kCameraRaysBlock) void camera_rays_kernel(CameraRay
 hipError_t launch_path(const PathParams &p, int blocks, hipStream_t s) {
     const QueryParams &q = p.q;
     if (!query_params_ok(q, blocks)) return hipErrorInvalidValue;
-    // the path's own pointers; rays and records are read and stored whole
-    if (!q.shade || !q.rays || !p.mats || !p.seeds || !p.radiance || p.maxDepth < 1 ||
-        reinterpret_cast<uintptr_t>(q.rays) % 16 || reinterpret_cast<uintptr_t>(p.radiance) % 16)
-        return hipErrorInvalidValue;
-    return launch_ray_kernel(path_fn(q), q, p, blocks, s);
-}
-
-int path_blocks_per_cu(const PathParams &p) { return ray_kernel_blocks_per_cu(path_fn(p.q), p.q); }
-
-hipError_t launch_nee(const NeeParams &p, int blocks, hipStream_t s) {
-    const QueryParams &q = p.p.q;
-    if (!query_params_ok(q, blocks)) return hipErrorInvalidValue;
-    if (!q.shade || !p.p.mats || !q.full || !p.lights || p.numLights < 1 || p.p.maxDepth < 1) return hipErrorInvalidValue;
+    if (!q.shade || !p.mats || p.maxDepth < 1) return hipErrorInvalidValue;
+    if (p.lights ? (!q.full || p.numLights < 1) : p.scratch != nullptr) return hipErrorInvalidValue;
+    // a render batch's counters; a query's own pointers: rays and records are read and stored whole
     if (p.scratch ? !p.stats
-                  : (!q.rays || !p.p.seeds || !p.p.radiance || reinterpret_cast<uintptr_t>(q.rays) % 16 ||
-                     reinterpret_cast<uintptr_t>(p.p.radiance) % 16))
+                  : (!q.rays || !p.seeds || !p.radiance || reinterpret_cast<uintptr_t>(q.rays) % 16 ||
+                     reinterpret_cast<uintptr_t>(p.radiance) % 16))
         return hipErrorInvalidValue;
-    return launch_ray_kernel(nee_fn(p), q, p, blocks, s);
+    return launch_ray_kernel(path_fn(p), q, p, blocks, s);
 }
 
-int nee_blocks_per_cu(const NeeParams &p) { return ray_kernel_blocks_per_cu(nee_fn(p), p.p.q); }
+int path_blocks_per_cu(const PathParams &p) { return ray_kernel_blocks_per_cu(path_fn(p), p.q); }
 
 hipError_t launch_camera_rays(const CameraRaysParams &p, hipStream_t s) {
     if ((!p.rays && !p.seeds) || p.numRays == 0 || p.numRays > (1u << 31) || reinterpret_cast<uintptr_t>(p.rays) % 16)

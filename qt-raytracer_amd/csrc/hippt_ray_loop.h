@@ -4,10 +4,15 @@
 // its own persistent loop: stage; then claim ray indices from the shard counters, start the claimed
 // rays, traverse until at most waveThreshold lanes are busy, finish the lanes whose traversal has ended.
 //
-// The walk over the shards and the loop itself stay written out in both kernels.  Moved here (the walk
-// as a small struct, the loop as an inlined function over two hooks) they compile to other register
-// counts than the code they replace: the walk +1 or +2 VGPRs in seven 2-wide query kernels, the loop up
-// to +11 in the 2-wide path kernels.  Device code only.
+// The loop is written out twice: once in query_kernel, once in path_kernel.  path_kernel's copy serves
+// plain paths, light-sampled path queries and the light-sampling render route: what those add sits
+// behind the compile-time flags NEE and CAMERA of the one template, and every instantiation has the
+// VGPRs, SGPRs and scratch of the separately written kernels it replaced
+// (profiles/path_merge/regs.txt).  Sharing between query_kernel and path_kernel is another matter: the
+// walk over the shards and the loop moved here (the walk as a small struct, the loop as an inlined
+// function over two hooks) compile to other register counts than the code they replace: the walk +1
+// or +2 VGPRs in seven 2-wide query kernels, the loop up to +11 in the 2-wide path kernels.  So those
+// two stay written out in both kernels.  Device code only.
 #pragma once
 
 #include <algorithm>

@@ -2,11 +2,12 @@
 """Parent against change, per kernel, from two hipcc -S device assembly files of one source file: VGPRs, SGPRs,
 scratch bytes (the .amdhsa_ metadata, as tools/kregs.py) and the instruction count of the kernel's text.
 
-usage: python tools/kcompare.py parent.s change.s
+usage: python tools/kcompare.py parent.s change.s [pairs.txt]
 
 A kernel of the change whose template arguments end in one more `false` than the parent's (a flag added with that
 default) is compared with the parent's kernel; one that ends in one more `true` is a new variant and is listed
-against the parent's kernel of the other arguments (its twin).
+against the parent's kernel of the other arguments (its twin).  A renamed kernel is paired by pairs.txt: lines of
+"parent-name change-name" (mangled); such pairs are listed with both figures whether or not they differ.
 """
 import re
 import sys
@@ -47,8 +48,10 @@ def waves(vgpr):
     return min(8, 512 // ((vgpr + 7) // 8 * 8))
 
 
-def twin(name, parent):
+def twin(name, parent, told):
     """(the parent's name of this kernel, whether it is a new variant)"""
+    if name in told:
+        return told[name], False
     if name in parent:
         return name, False
     m = re.search(r"I((?:Lb[01]E)+)E", name)
@@ -60,12 +63,15 @@ def twin(name, parent):
     return None, True
 
 
-def main(a_path, b_path):
+def main(a_path, b_path, pairs_path=None):
     a, b = parse(a_path), parse(b_path)
+    told = dict(reversed(line.split()) for line in open(pairs_path) if line.strip()) if pairs_path else {}
     short = lambda k: re.sub(r"_ZN5hippt12_GLOBAL__N_1\d+", "", k)
-    same, diff, new = 0, [], []
+    same, diff, new, paired = 0, [], [], []
     for k in sorted(b):
-        p, variant = twin(k, a)
+        p, variant = twin(k, a, told)
+        if k in told:
+            paired.append(f"  {short(p)} {a[p]} -> {short(k)} {b[k]}")
         if p is None:
             new.append(f"  {short(k)}: new {b[k]}")
         elif variant:
@@ -77,8 +83,8 @@ def main(a_path, b_path):
         else:
             diff.append(f"  {short(p)}: {a[p]} -> {b[k]}")
     print(f"{len(a)} kernels of the parent, {same} with identical figures, {len(diff)} that differ; {len(new)} new variants")
-    print("\n".join(diff + (["new variants:"] + new if new else [])))
+    print("\n".join(diff + (["new variants:"] + new if new else []) + (["told pairs:"] + paired if paired else [])))
 
 
 if __name__ == "__main__":
-    main(sys.argv[1], sys.argv[2])
+    main(*sys.argv[1:4])
