@@ -487,7 +487,17 @@ enum {
                                        are traced by a ray-per-lane kernel into the batch scratch and
                                        combined by the deferred combine: no chaining, sky rectangle, render
                                        pad or item order (their HIPPT_INFO_* read 0), and
-                                       HIPPT_OPT_COUNT_TRAVERSAL's counts are not reported */
+                                       HIPPT_OPT_COUNT_TRAVERSAL's counts are not reported.  Accepts 0 and 1
+                                       only, as it always did; it is the on/off form of
+                                       HIPPT_OPT_LIGHT_SAMPLING_MODE, sets the same word and reads it (so it
+                                       reads 2 while the mode is HIPPT_LIGHT_SAMPLING_MIS) */
+    , HIPPT_OPT_LIGHT_SAMPLING_MODE = 38 /* the light-sampling mode: 0 and 1 as HIPPT_OPT_LIGHT_SAMPLING;
+                                       HIPPT_LIGHT_SAMPLING_MIS (2): the same connection and the light hit
+                                       after a Lambertian scatter each weighted against the other (the second
+                                       rule below), which bounds what one connection can add.  Everything
+                                       said of HIPPT_OPT_LIGHT_SAMPLING 1 holds for 2: the render route, the
+                                       next call without an upload, the option-off code for a scene without
+                                       an emissive primitive */
 };
 /* Light sampling (HIPPT_OPT_LIGHT_SAMPLING 1; this library's own, as the emissive rule is; tests/nee_ref.py
  * restates it in numpy float32 and the GPU matches that bit for bit).  A path carries
@@ -508,11 +518,39 @@ enum {
  *     g = (((cosS * cosL) * A) * float(nLights)) / (3.14159274f * d2); Ld.c = (thr'.c * Le.c) * g
  *     the shadow ray (p, om), tmin 0.001, no tmax, is a closest-hit query: if its hit is light k,
  *     Lacc.c += Ld.c.  The path goes on along the scattered ray.
- * No MIS; one light per vertex, uniform over the list.  maxDepth means what it meant: the connection at
+ * No MIS under 1 (HIPPT_LIGHT_SAMPLING_MIS below adds it); one light per vertex, uniform over the list.  maxDepth means what it meant: the connection at
  * vertex d stands for the light hit of segment d + 1 and is made exactly when that segment would exist.
  * segments (hipptTraceRadiance, hipptGetStats) count every closest-hit query traced, shadow rays included. */
+enum { HIPPT_LIGHT_SAMPLING_MIS = 2 /* a value of HIPPT_OPT_LIGHT_SAMPLING_MODE */ };
+/* Light sampling with multiple importance sampling (HIPPT_OPT_LIGHT_SAMPLING_MODE HIPPT_LIGHT_SAMPLING_MIS; the
+ * power heuristic, beta = 2, between the connection and the Lambertian scatter sample, whose solid-angle
+ * density is exactly cos / pi; tests/mis_ref.py restates it in numpy float32 and the GPU matches that bit for
+ * bit).  A path is the rule's above, with these changes.  It carries a float cb in place of
+ * spec; cb = -1: the last scatter was not Lambertian, or there was none yet.
+ *   Lambertian scatter: the renderer's scatter first, as above; then, with sd the scattered direction as the
+ *     renderer stores it and n the faced normal, cb = fdot(n, sd) * (1 / sqrtf(fdot(sd, sd))).
+ *     Metal, Dielectric: cb = -1.
+ *   connection: the draws, k, q, A, cosS, cosL, d2, the skip conditions and g are the rule's above; one more
+ *     skip condition: no shadow ray unless g < +inf; then Ld.c = (thr'.c * Le.c) * (g / fmaf(g, g, 1.0f)).
+ *     (g = p_b / p_l with p_b = cosS / pi and p_l = d2 / (cosL * A * nLights); the weight
+ *     p_l^2 / (p_l^2 + p_b^2) = 1 / (1 + g^2), so g / (1 + g^2) <= 0.5 and Ld.c <= thr'.c * Le.c / 2.)
+ *   light hit with cb < 0 (segment 0, or after Metal or Dielectric): L = Lacc + thr * Le.
+ *   light hit with cb >= 0, at t on the segment with direction d from the vertex:
+ *     dd = fdot(d, d); d2 = (t * t) * dd; om = d * (1 / sqrtf(dd))
+ *     nl = the triangle's stored unit normal, or the sphere's (hit point - c) / r as hipptHit forms it
+ *     cosL = |fdot(nl, om)|; A as in the connection (a sphere: (12.566371f * r) * r)
+ *     if cb > 0, cosL > 0, d2 > 0 and A > 0: gh = (((cb * cosL) * A) * float(nLights)) / (3.14159274f * d2),
+ *       s = gh * gh, and if also s < +inf: wb = s / fmaf(gh, gh, 1.0f)
+ *     in every other case wb = 1 (light sampling could not have produced that point)
+ *     L.c = Lacc.c + (thr.c * Le.c) * wb.  The hit ends the path before the depth check, as before.
+ * Everything else is the rule's above: miss, depth, absorbed paths, the segment counts with the shadow rays,
+ * tmin 0.001, "is the closest hit light k", maxDepth.  Each product, sum, quotient and square root is one
+ * float32 operation in the association written; 1 / sqrtf(x) is the quotient of 1 and the correctly rounded
+ * root.  With maxDepth segments a path returns at most Le_max * (1 + (maxDepth - 1) / 2) when the sky is no
+ * brighter than the lights: every connection adds at most thr' * Le / 2. */
 enum { HIPPT_INFO_LIGHTS = 107          /* emissive primitives in the uploaded scene */,
-       HIPPT_INFO_LIGHT_SAMPLING = 108  /* 1 if the last render took the light-sampling route, else 0 */ };
+       HIPPT_INFO_LIGHT_SAMPLING = 108  /* the value of HIPPT_OPT_LIGHT_SAMPLING_MODE (1 or 2) that the last render
+                                           applied if it took the light-sampling route, else 0 */ };
 /* Records of the chained runs closed since the last call (HIPPT_OPT_CHAIN_AUDIT), as 32-bit words:
  * per run a 16-word header  [0] 0xC4A1D17 [1] run id [2] device [3] batch 0's first frame [4] frames
  * from one batch to the next (-1: one batch) [5] frames per batch [6] band pixels [7] items per batch

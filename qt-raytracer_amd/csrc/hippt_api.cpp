@@ -105,7 +105,7 @@ struct OccKey {
 };
 // The path kernel's routes as OccKey variants, after the QueryModes: plain paths, light-sampled path
 // queries, the light-sampling render route.
-constexpr int kVariantPath = 8, kVariantLitPath = 9, kVariantLitRender = 10;
+constexpr int kVariantPath = 8, kVariantLitPath = 9, kVariantLitRender = 10, kVariantMisPath = 11, kVariantMisRender = 12;
 
 bool same_key(const OccKey &a, const OccKey &b) {
     return a.version == b.version && a.stackDepth == b.stackDepth && a.fmt == b.fmt && a.poolWords == b.poolWords &&
@@ -354,8 +354,8 @@ struct State {
     bool chainAudit = false;            // HIPPT_OPT_CHAIN_AUDIT
     long long querySlice = 0;           // rays per staged slice of a host-memory query (HIPPT_OPT_QUERY_SLICE; 0 automatic)
     bool denoiseTiming = false;         // HIPPT_OPT_DENOISE_TIMING
-    bool lightSampling = false;         // HIPPT_OPT_LIGHT_SAMPLING
-    int activeLightSampling = 0;        // the last render took the light-sampling route (HIPPT_INFO_LIGHT_SAMPLING)
+    int lightSampling = 0;              // HIPPT_OPT_LIGHT_SAMPLING_MODE: 0, 1 or HIPPT_LIGHT_SAMPLING_MIS
+    int activeLightSampling = 0;        // the mode of the light-sampling route if the last render took it (HIPPT_INFO_LIGHT_SAMPLING)
     long long denoiseNs[hippt::kDenoiseStages] = {};  // HIPPT_INFO_DENOISE_NS + k of the last timed hipptDenoise
     std::vector<unsigned> auditWords;   // closed runs' audit words not yet read (hipptChainAudit)
     std::vector<std::pair<int, uint32_t *>> rngTables;  // per device, built on first use
@@ -1830,11 +1830,11 @@ bool enqueue_sphere4(Ctx &c, int firstFrame, int count, int maxDepth, bool copy,
     return TIMED_LAUNCH(c, 0, hippt::launch_sphere4(p, c.stream));
 }
 
-// HIPPT_OPT_LIGHT_SAMPLING as applied: on, and the scene holds an emissive primitive (else the option-off
-// code runs).
-bool light_sampling_applies() {
+// HIPPT_OPT_LIGHT_SAMPLING_MODE as applied: its value (1, or 2 with MIS) if the scene holds an emissive primitive,
+// else 0 (the option-off code runs).
+int light_sampling_applies() {
     const State &s = S();
-    return s.lightSampling && s.scene.kind == HIPPT_SCENE_MESH && !s.scene.lights.empty();
+    return s.scene.kind == HIPPT_SCENE_MESH && !s.scene.lights.empty() ? s.lightSampling : 0;
 }
 
 // A mesh call's batches on a context: as many frames per batch as the sample scratch budget
@@ -1970,13 +1970,14 @@ bool fill_mesh_params(Ctx &c, const plan::Facts &f, const plan::Layout &L, const
 // A mesh scene's frames on context c, in batches: each a megakernel launch (on its own, or a batch of
 // the context's chained run), or the wavefront's launches; its combine deferred into the next batch's
 // launch, or flushed.
-bool enqueue_mesh_lights(Ctx &c, const CameraF &cam, int firstFrame, int count, int maxDepth, const char **err);
+bool enqueue_mesh_lights(Ctx &c, const CameraF &cam, int firstFrame, int count, int maxDepth, int mode, const char **err);
 
 bool enqueue_mesh(Ctx &c, const CameraF &cam, int firstFrame, int count, int maxDepth, bool copy, const char **err) {
     State &s = S();
     if (!ensure_scene(c, err)) return false;
     s.activeLightSampling = 0;
-    if (maxDepth > 0 && light_sampling_applies()) return enqueue_mesh_lights(c, cam, firstFrame, count, maxDepth, err);
+    if (const int mode = light_sampling_applies(); maxDepth > 0 && mode)
+        return enqueue_mesh_lights(c, cam, firstFrame, count, maxDepth, mode, err);
     const unsigned bandPixels = unsigned(c.rows) * unsigned(s.width);
     const BatchSize size = frames_per_batch(bandPixels, count);
     const bool cnt = s.knobs.countTraversal;
@@ -2262,8 +2263,10 @@ bool ensure_ray_launch(Ctx &c, RayLaunch &r, const plan::Layout &L, int variant,
     occKey.variant = variant;
     if (!same_key(r.occKey, occKey)) {
         // (the pointers select the kernel: any non-null scratch the render route's)
+        const bool render = variant == kVariantLitRender || variant == kVariantMisRender;
         const hippt::PathParams pp{q, c.mats, nullptr, nullptr, nullptr, 1, variant >= kVariantLitPath ? c.lights : nullptr, 1,
-                                   variant == kVariantLitRender ? reinterpret_cast<float *>(c.stats) : nullptr, nullptr};
+                                   variant >= kVariantMisPath ? 2 : 1, render ? reinterpret_cast<float *>(c.stats) : nullptr,
+                                   nullptr};
         r.blocksPerCu = variant >= kVariantPath ? hippt::path_blocks_per_cu(pp)
                                                 : hippt::query_blocks_per_cu(q, hippt::QueryMode(variant));
         r.occKey = occKey;
@@ -2287,7 +2290,8 @@ bool query_setup(Ctx &c, const QueryCall &call, hippt::QueryParams &q, const cha
     HIP_TRY(hipSetDevice(c.device));
     if (!c.qDone) HIP_TRY(hipEventCreateWithFlags(&c.qDone, hipEventDisableTiming));
     if (call.camRays) return true;  // no traversal: the camera alone
-    const int variant = !call.path ? int(call.mode) : light_sampling_applies() ? kVariantLitPath : kVariantPath;
+    const int lit = light_sampling_applies();
+    const int variant = !call.path ? int(call.mode) : lit == 2 ? kVariantMisPath : lit ? kVariantLitPath : kVariantPath;
     return ensure_ray_launch(c, c.qLaunch, L, variant, q, err);
 }
 
@@ -2296,7 +2300,7 @@ bool query_setup(Ctx &c, const QueryCall &call, hippt::QueryParams &q, const cha
 // (QueryCam: the context's rows of the image, frame-major items as the combine reads them), into the batch
 // scratch, combined by the deferred combine.  No chaining, sky rectangle, render pad or item order.  Its
 // counters and spill area are the route's own: a batch may still be in flight when a query is made.
-bool enqueue_mesh_lights(Ctx &c, const CameraF &cam, int firstFrame, int count, int maxDepth, const char **err) {
+bool enqueue_mesh_lights(Ctx &c, const CameraF &cam, int firstFrame, int count, int maxDepth, int mode, const char **err) {
     State &s = S();
     const unsigned bandPixels = unsigned(c.rows) * unsigned(s.width);
     const BatchSize size = frames_per_batch(bandPixels, count);
@@ -2304,15 +2308,16 @@ bool enqueue_mesh_lights(Ctx &c, const CameraF &cam, int firstFrame, int count, 
     const plan::Layout L = query_scene_params(c, q);
     q.cam = query_cam(cam, c.y0, c.stride, bandPixels, firstFrame);
     RayLaunch &R = c.litLaunch;
-    if (!ensure_ray_launch(c, R, L, kVariantLitRender, q, err)) return false;
-    hippt::PathParams np{q, c.mats, nullptr, nullptr, nullptr, maxDepth, c.lights, int(s.scene.lights.size()), nullptr, c.stats};
+    if (!ensure_ray_launch(c, R, L, mode == 2 ? kVariantMisRender : kVariantLitRender, q, err)) return false;
+    hippt::PathParams np{q,    c.mats,  nullptr, nullptr, nullptr, maxDepth, c.lights, int(s.scene.lights.size()),
+                         mode, nullptr, c.stats};
     s.activeWidth = L.wide ? 4 : 2;
     s.activeTopBytes = L.topBytes;
     s.activeBlocksPerCu = R.blocksPerCu;
     s.activeChainCap = 0;
     s.activeRenderPad = 0;
     s.activeSkyPixels = 0;
-    s.activeLightSampling = 1;
+    s.activeLightSampling = mode;
     for (int b = 0; b < count; b += size.frames) {
         const int nf = std::min(size.frames, count - b);
         const unsigned total = bandPixels * unsigned(nf);
@@ -2349,10 +2354,10 @@ bool query_enqueue(Ctx &c, hippt::QueryParams q, unsigned first, unsigned m, con
     const long long blocks = ray_blocks(c, c.qLaunch.blocksPerCu, m);
     HIP_TRY(hipMemsetAsync(c.qLaunch.ctr, 0, hippt::kQueryCtrBytes, c.stream));
     if (call.path) {
-        const bool lit = light_sampling_applies();
+        const int lit = light_sampling_applies();
         HIP_TRY(hippt::launch_path(hippt::PathParams{q, c.mats, pp.seeds, pp.radiance, pp.segments, call.maxDepth,
-                                                     lit ? c.lights : nullptr, lit ? int(S().scene.lights.size()) : 0, nullptr,
-                                                     nullptr},
+                                                     lit ? c.lights : nullptr, lit ? int(S().scene.lights.size()) : 0, lit,
+                                                     nullptr, nullptr},
                                    int(blocks), c.stream));
     } else {
         HIP_TRY(hippt::launch_query(q, int(blocks), call.mode, c.stream));
@@ -3499,9 +3504,13 @@ bool set_option_locked(int key, long long value) {
         if (value != 0 && value != 1) return false;
         s.denoiseTiming = value == 1;
         return true;
-    case HIPPT_OPT_LIGHT_SAMPLING:
+    case HIPPT_OPT_LIGHT_SAMPLING:  // the on/off form: 0 and 1 only, as before the mode existed
         if (value != 0 && value != 1) return false;
-        s.lightSampling = value == 1;
+        s.lightSampling = int(value);
+        return true;
+    case HIPPT_OPT_LIGHT_SAMPLING_MODE:
+        if (value != 0 && value != 1 && value != HIPPT_LIGHT_SAMPLING_MIS) return false;
+        s.lightSampling = int(value);
         return true;
     default: return false;
     }
@@ -3562,7 +3571,8 @@ long long get_option_locked(int key) {
     case HIPPT_INFO_CHAIN_CAP: return s.activeChainCap;
     case HIPPT_INFO_RENDER_PAD: return s.activeRenderPad;
     case HIPPT_OPT_DENOISE_TIMING: return s.denoiseTiming ? 1 : 0;
-    case HIPPT_OPT_LIGHT_SAMPLING: return s.lightSampling ? 1 : 0;
+    case HIPPT_OPT_LIGHT_SAMPLING:
+    case HIPPT_OPT_LIGHT_SAMPLING_MODE: return s.lightSampling;
     case HIPPT_INFO_LIGHTS: return s.scene.kind == HIPPT_SCENE_MESH ? (long long)s.scene.lights.size() : 0;
     case HIPPT_INFO_LIGHT_SAMPLING: return s.activeLightSampling;
     case HIPPT_INFO_SKY_RECT_PIXELS: return s.activeSkyPixels;

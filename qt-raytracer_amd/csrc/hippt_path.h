@@ -18,7 +18,8 @@ namespace hippt {
 // set.  With `scratch` null it is a path query as above; with `scratch` (light sampling only) it is a
 // render batch: sample i is camera_sample(q.cam, q.firstItem + i), its radiance goes to
 // scratch[3 i .. 3 i + 2] (the combine's layout) and the segments and samples are added to `stats`
-// (hippt_device.h kStatWords).
+// (hippt_device.h kStatWords).  lightMode 2 (HIPPT_LIGHT_SAMPLING_MIS) weights the connection
+// and the light met after a Lambertian scatter by the power heuristic; the routes are the same.
 struct PathParams {
     QueryParams q;
     const float4 *mats;     // MeshParams::mats
@@ -28,6 +29,7 @@ struct PathParams {
     int maxDepth;
     const int *lights;
     int numLights;
+    int lightMode;  // with `lights`: 1 plain, 2 with MIS (HIPPT_LIGHT_SAMPLING_MIS)
     float *scratch;
     unsigned long long *stats;
 };

@@ -17,9 +17,10 @@
 // finished shade together.  scatter's unit-sphere draw is the plain per-lane loop (TAIL = -1, as the
 // wavefront shade kernel): it is called under per-lane control flow (hit, depth, material).
 //
-// Light sampling (HIPPT_OPT_LIGHT_SAMPLING) and the renderer's own camera start are compile-time flags
-// of the same kernel (NEE, CAMERA): one persistent loop serves plain paths, light-sampled path queries
-// and the light-sampling render route.
+// Light sampling (HIPPT_OPT_LIGHT_SAMPLING, HIPPT_OPT_LIGHT_SAMPLING_MODE), its weighting against the scatter sample
+// (HIPPT_LIGHT_SAMPLING_MIS) and the renderer's own camera start are compile-time flags of the same kernel
+// (NEE, MIS, CAMERA): one persistent loop serves plain paths, light-sampled path queries and the
+// light-sampling render route.
 #include "hippt_path.h"
 
 #include "hippt_ray_loop.h"
@@ -51,10 +52,24 @@ __device__ __forceinline__ int hit_normal_kind(const Ray &r, float t, int prim, 
     return __float_as_int(mats[2 * (mw & ~kShadeSphere)].w);
 }
 
+// The area of light `k` (leaf order) as both techniques form it: a triangle's from its edges (v0, e1, e2), a
+// sphere's from its radius.
+__device__ __forceinline__ float light_area(const float4 *prims, int k, bool sphere) {
+    const float4 A = prims[3 * k];
+    if (sphere) return (12.566371f * A.w) * A.w;
+    const float4 B = prims[3 * k + 1];
+    const float e1x = A.w, e1y = B.x, e1z = B.y;
+    const float e2x = B.z, e2y = B.w, e2z = prims[3 * k + 2].x;
+    const float cx = fmaf(e1y, e2z, -(e1z * e2y)), cy = fmaf(e1z, e2x, -(e1x * e2z)), cz = fmaf(e1x, e2y, -(e1y * e2x));
+    return 0.5f * sqrtf(fdot(cx, cy, cz, cx, cy, cz));
+}
+
 // One connection from the Lambertian vertex p (faced normal n, throughput t* after the scatter): picks a
 // light and a point on it from `rng`, and returns whether a shadow ray is to be traced; then (wx, wy, wz)
 // is its unit direction, (l0, l1, l2) what the light adds if the ray's closest hit is primitive `lk`
-// (leaf order).  The draws are consumed either way.
+// (leaf order).  The draws are consumed either way.  MIS: the power heuristic's weight against the scatter
+// sample, 1 / (1 + g^2), is in (l0, l1, l2), and a g that is not below +inf makes no shadow ray.
+template <bool MIS>
 __device__ __forceinline__ bool light_connect(const int *lights, int numLights, const float4 *shade, const float4 *prims,
                                               const float4 *mats, float px, float py, float pz, float nx, float ny,
                                               float nz, float tr, float tg, float tb, uint32_t &rng, unsigned *pc,
@@ -73,7 +88,7 @@ __device__ __forceinline__ bool light_connect(const int *lights, int numLights, 
         lx = ux * inv, ly = uy * inv, lz = uz * inv;
         const float rad = A.w;
         qx = fmaf(rad, lx, sh.x), qy = fmaf(rad, ly, sh.y), qz = fmaf(rad, lz, sh.z);
-        area = (12.566371f * rad) * rad;
+        area = light_area(prims, lk, true);
         const float ox = px - sh.x, oy = py - sh.y, oz = pz - sh.z;
         flip = fdot(ox, oy, oz, ox, oy, oz) >= rad * rad;  // seen from outside: the near side emits
     } else {  // (v0, e1, e2): uniform by folding the unit square
@@ -85,8 +100,7 @@ __device__ __forceinline__ bool light_connect(const int *lights, int numLights, 
         const float e1x = A.w, e1y = B.x, e1z = B.y;
         const float e2x = B.z, e2y = B.w, e2z = prims[3 * lk + 2].x;
         qx = fmaf(b, e2x, fmaf(a, e1x, A.x)), qy = fmaf(b, e2y, fmaf(a, e1y, A.y)), qz = fmaf(b, e2z, fmaf(a, e1z, A.z));
-        const float cx = fmaf(e1y, e2z, -(e1z * e2y)), cy = fmaf(e1z, e2x, -(e1x * e2z)), cz = fmaf(e1x, e2y, -(e1y * e2x));
-        area = 0.5f * sqrtf(fdot(cx, cy, cz, cx, cy, cz));
+        area = light_area(prims, lk, false);
         lx = sh.x, ly = sh.y, lz = sh.z;
     }
     const float dx = qx - px, dy = qy - py, dz = qz - pz;
@@ -97,11 +111,44 @@ __device__ __forceinline__ bool light_connect(const int *lights, int numLights, 
     const float sL = fdot(lx, ly, lz, wx, wy, wz);
     const float cosL = sphere ? (flip ? -sL : sL) : fabsf(sL);
     if (!(cosS > 0.0f) || !(cosL > 0.0f) || !(d2 > 0.0f) || !(area > 0.0f)) return false;
-    const float g = (((cosS * cosL) * area) * nl) / (3.14159274f * d2);
+    float g = (((cosS * cosL) * area) * nl) / (3.14159274f * d2);
+    if (MIS) {
+        if (!(g < INFINITY)) return false;
+        g = g / fmaf(g, g, 1.0f);
+    }
     l0 = (tr * le.x) * g;
     l1 = (tg * le.y) * g;
     l2 = (tb * le.z) * g;
     return true;
+}
+
+// MIS: the weight wb of the emission of light `prim`, met at t on the segment r that a Lambertian scatter
+// with cosine cb to its normal started: the scatter's density against light sampling's at that point,
+// squared (the power heuristic); 1 where light sampling could not have produced the point.
+__device__ __forceinline__ float light_hit_weight(const Ray &r, float t, int prim, const float4 *shade, const float4 *prims,
+                                                  float cb, int numLights) {
+    const float4 sh = shade[prim];
+    const bool sphere = (__float_as_int(sh.w) & kShadeSphere) != 0;
+    const float dd = fdot(r.dx, r.dy, r.dz, r.dx, r.dy, r.dz);
+    const float d2 = (t * t) * dd;
+    const float inv = rsqrt_rn(dd);
+    float nx = sh.x, ny = sh.y, nz = sh.z;
+    if (sphere) {
+        const float px = fmaf(t, r.dx, r.ox), py = fmaf(t, r.dy, r.oy), pz = fmaf(t, r.dz, r.oz);
+        const float rad = prims[3 * prim].w;
+        nx = (px - sh.x) / rad;
+        ny = (py - sh.y) / rad;
+        nz = (pz - sh.z) / rad;
+    }
+    const float cosL = fabsf(fdot(nx, ny, nz, r.dx * inv, r.dy * inv, r.dz * inv));
+    const float area = light_area(prims, prim, sphere);
+    float wb = 1.0f;
+    if (cb > 0.0f && cosL > 0.0f && d2 > 0.0f && area > 0.0f) {
+        const float gh = (((cb * cosL) * area) * float(numLights)) / (3.14159274f * d2);
+        const float s = gh * gh;
+        if (s < INFINITY) wb = s / fmaf(gh, gh, 1.0f);
+    }
+    return wb;
 }
 
 // LDS_SCENE: the scene copy in LDS (else the tree in global memory, the top of a 4-wide one in LDS);
@@ -113,10 +160,14 @@ __device__ __forceinline__ bool light_connect(const int *lights, int numLights, 
 // along the scattered ray.  Shadow and path segments share the traversal rounds.  Everything it adds is
 // under the flag: without it the kernel holds none of the state below "light sampling".
 // CAMERA (with NEE): the renderer's samples in place of the caller's rays (PathParams::scratch).
-template <bool LDS_SCENE, bool FULL, bool WIDE, bool NEE, bool CAMERA>
+// MIS (with NEE): HIPPT_LIGHT_SAMPLING_MIS (tests/mis_ref.py is the statement of record).  In
+// place of `spec` the path carries cb, the cosine of the last scatter if it was Lambertian, else -1; the
+// connection and a light met after a Lambertian scatter are each weighted against the other technique.
+template <bool LDS_SCENE, bool FULL, bool WIDE, bool NEE, bool CAMERA, bool MIS>
 __global__ __launch_bounds__(kMeshBlock) void path_kernel(PathParams P) {
     static_assert(FULL || !NEE, "light sampling has general kernels only");
     static_assert(NEE || !CAMERA, "the camera start belongs to the light-sampling render route");
+    static_assert(NEE || !MIS, "the weights belong to light sampling");
     const QueryParams &Q = P.q;
     const Staged sc = stage_scene<LDS_SCENE, WIDE>(Q.nodes, Q.tris, Q.numNodes, Q.numTris, Q.stackDepth, Q.topBytes);
     const SpillArea S = lane_spill(Q.spill, Q.spillCap, Q.stackCap);
@@ -142,6 +193,7 @@ __global__ __launch_bounds__(kMeshBlock) void path_kernel(PathParams P) {
     int nseg = 0;
     float la0 = 0.0f, la1 = 0.0f, la2 = 0.0f;
     bool spec = true, shadow = false;
+    float cb = -1.0f;  // (MIS: in place of spec)
     float sdx = 0.0f, sdy = 0.0f, sdz = 0.0f, ld0 = 0.0f, ld1 = 0.0f, ld2 = 0.0f;
     int lk = -1;
     unsigned long long segsAll = 0, samplesAll = 0;  // CAMERA: the launch counters' share of this lane
@@ -176,10 +228,11 @@ __global__ __launch_bounds__(kMeshBlock) void path_kernel(PathParams P) {
                     la0 = la1 = la2 = 0.0f;
                     nseg = 0;
                     spec = true;
+                    cb = -1.0f;
                     shadow = false;
                 }
                 // begin_query_ray, with the mark of hipptTraceRays' invalid rays (no segment, (0, 0, 0, 0))
-                // in its branch: set after it, the mark costs path_kernel<false, false, false, false, false>
+                // in its branch: set after it, the mark costs path_kernel<false, false, false, false, false, false>
                 // 2 VGPRs
                 begin(T);
                 T.bestO = -1;  // a hit at exactly t == tmax loses the tie on the id: tmax is exclusive
@@ -235,8 +288,18 @@ __global__ __launch_bounds__(kMeshBlock) void path_kernel(PathParams P) {
                 if (NEE) ++nseg;
                 if (FULL && emitted(T.bestI, Q.shade, P.mats, tr, tg, tb, L0, L1, L2)) {
                     // ends at a light with throughput x emission, whatever the depth; light
-                    // sampling: unless the vertex before it sampled the lights itself
-                    if (NEE && !spec) L0 = L1 = L2 = 0.0f;
+                    // sampling: unless the vertex before it sampled the lights itself; with MIS: then with the
+                    // scatter sample's weight
+                    if (MIS) {
+                        if (!(cb < 0.0f)) {
+                            const float wb = light_hit_weight(r, T.bestT, T.bestI, Q.shade, sc.tris, cb, P.numLights);
+                            L0 *= wb;
+                            L1 *= wb;
+                            L2 *= wb;
+                        }
+                    } else if (NEE && !spec) {
+                        L0 = L1 = L2 = 0.0f;
+                    }
                 } else if (depth < P.maxDepth) {  // depth exhausted or absorbed: contributes 0
                     float nx = 0.0f, ny = 0.0f, nz = 0.0f;
                     int kind = kLambertian;
@@ -245,9 +308,13 @@ __global__ __launch_bounds__(kMeshBlock) void path_kernel(PathParams P) {
                         finished = false;
                         if (NEE) {
                             spec = kind != kLambertian;
+                            if (MIS)
+                                cb = spec ? -1.0f
+                                          : fdot(nx, ny, nz, r.dx, r.dy, r.dz) *
+                                                rsqrt_rn(fdot(r.dx, r.dy, r.dz, r.dx, r.dy, r.dz));
                             float wx, wy, wz;
-                            if (!spec && light_connect(P.lights, P.numLights, Q.shade, sc.tris, P.mats, r.ox, r.oy, r.oz, nx,
-                                                       ny, nz, tr, tg, tb, rng, pc, wx, wy, wz, ld0, ld1, ld2, lk)) {
+                            if (!spec && light_connect<MIS>(P.lights, P.numLights, Q.shade, sc.tris, P.mats, r.ox, r.oy, r.oz,
+                                                            nx, ny, nz, tr, tg, tb, rng, pc, wx, wy, wz, ld0, ld1, ld2, lk)) {
                                 shadow = true;
                                 sdx = r.dx, sdy = r.dy, sdz = r.dz;
                                 r.dx = wx, r.dy = wy, r.dz = wz;
@@ -292,8 +359,8 @@ __global__ __launch_bounds__(kMeshBlock) void path_kernel(PathParams P) {
     }
 }
 
-// The kernel of p's scene layout and route: plain paths in all eight layouts, light sampling in the four
-// general ones (whatever p.q.full says), for a query or a render batch.
+// The kernel of p's scene layout and route: plain paths in all eight layouts, light sampling (plain or with
+// MIS: p.lightMode) in the four general ones (whatever p.q.full says), for a query or a render batch.
 using PathFn = void (*)(PathParams);
 PathFn path_fn(const PathParams &p) {
     QueryParams q = p.q;
@@ -301,9 +368,12 @@ PathFn path_fn(const PathParams &p) {
     return for_scene_layout(q, [&p](auto lds, auto full, auto wide) -> PathFn {
         constexpr bool L = decltype(lds)::value, F = decltype(full)::value, W = decltype(wide)::value;
         if constexpr (F) {
-            if (p.lights) return p.scratch ? path_kernel<L, F, W, true, true> : path_kernel<L, F, W, true, false>;
+            if (p.lights && p.lightMode == 2)
+                return p.scratch ? path_kernel<L, F, W, true, true, true> : path_kernel<L, F, W, true, false, true>;
+            if (p.lights)
+                return p.scratch ? path_kernel<L, F, W, true, true, false> : path_kernel<L, F, W, true, false, false>;
         }
-        return path_kernel<L, F, W, false, false>;
+        return path_kernel<L, F, W, false, false, false>;
     });
 }
 
@@ -327,7 +397,8 @@ hipError_t launch_path(const PathParams &p, int blocks, hipStream_t s) {
     const QueryParams &q = p.q;
     if (!query_params_ok(q, blocks)) return hipErrorInvalidValue;
     if (!q.shade || !p.mats || p.maxDepth < 1) return hipErrorInvalidValue;
-    if (p.lights ? (!q.full || p.numLights < 1) : p.scratch != nullptr) return hipErrorInvalidValue;
+    if (p.lights ? (!q.full || p.numLights < 1 || p.lightMode < 1 || p.lightMode > 2) : p.scratch != nullptr)
+        return hipErrorInvalidValue;
     // a render batch's counters; a query's own pointers: rays and records are read and stored whole
     if (p.scratch ? !p.stats
                   : (!q.rays || !p.seeds || !p.radiance || reinterpret_cast<uintptr_t>(q.rays) % 16 ||

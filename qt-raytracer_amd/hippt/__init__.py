@@ -64,6 +64,8 @@ OPT_RENDER_PAD = 34
 OPT_SKY_RECT = 35
 OPT_DENOISE_TIMING = 36
 OPT_LIGHT_SAMPLING = 37  # next-event estimation at Lambertian vertices (include/hippt.h; 0 default)
+OPT_LIGHT_SAMPLING_MODE = 38  # the same word with all its values: 0, 1 and LIGHT_SAMPLING_MIS (37 takes 0 and 1 only)
+LIGHT_SAMPLING_MIS = 2  # light sampling with MIS (the power heuristic with the scatter sample)
 OPT_PIXEL_FORMAT = 25
 PIXEL_ARGB = 0
 PIXEL_RGBA8 = 1
@@ -75,7 +77,7 @@ INFO_UPDATE_DROPPED = 104
 INFO_RENDER_PAD = 105
 INFO_SKY_RECT_PIXELS = 106
 INFO_LIGHTS = 107  # emissive primitives in the uploaded scene
-INFO_LIGHT_SAMPLING = 108  # 1 if the last render took the light-sampling route
+INFO_LIGHT_SAMPLING = 108  # OPT_LIGHT_SAMPLING_MODE's value (1 or 2) if the last render took the light-sampling route
 INFO_DENOISE_NS = 200
 RAYS_DEVICE = 1
 HIT_SPHERE = 1 << 30

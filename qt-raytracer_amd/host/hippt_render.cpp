@@ -5,7 +5,7 @@
 //   hippt_render [--backend cuda|vulkan|gl] [--mesh FILE.obj|.ply] [--albedo r,g,b[;r,g,b...]]
 //                [--emit NAME=r,g,b[;NAME=r,g,b...]] [--width W] [--height H] [--spp N] [--depth D] [--per-frame] [--present]
 //                [--out FILE] [--ppm FILE.ppm] [--pick X,Y] [--denoise PASSES]
-//                [--radiance-in FILE|camera --radiance-out FILE] [--light-sampling]
+//                [--radiance-in FILE|camera --radiance-out FILE] [--light-sampling] [--mis]
 //
 // --backend cuda (default): HipPathTracer, the CudaPathTracer interface.  Without --mesh: the
 // reference kernel's built-in 4-sphere scene, one renderFrame per frame (the CUDA backend's
@@ -14,7 +14,8 @@
 // non-blocking hand-off with --present.
 // --emit (with --mesh): the named OBJ `usemtl` groups are area lights of that radiance (HIPPT_MAT_EMISSIVE).
 // --light-sampling: HIPPT_OPT_LIGHT_SAMPLING 1 (next-event estimation towards those lights) for the render
-// and --radiance-out.
+// and --radiance-out.  --mis: HIPPT_OPT_LIGHT_SAMPLING_MODE HIPPT_LIGHT_SAMPLING_MIS (light sampling with the scatter sample weighed in by
+// the power heuristic); it implies --light-sampling.
 // --backend vulkan: HipVulkanPathTracer, one renderFrame(depth) per frame (the app's "vulkan"
 // branch, RayTracerFboItem.cpp:576-600).  --backend gl: HipGpuPathTracer, initialize + resize,
 // then renderFrame(N, depth) once (or per frame with --per-frame), as the GL branch calls it.
@@ -50,7 +51,7 @@ int usage() {
                  "                    [--emit NAME=r,g,b[;...]]\n"
                  "                    [--height H] [--spp N] [--depth D] [--per-frame] [--present] [--out FILE]\n"
                  "                    [--ppm FILE.ppm] [--pick X,Y] [--update-mesh FILE] [--denoise PASSES]\n"
-                 "                    [--radiance-in FILE|camera --radiance-out FILE] [--light-sampling]\n");
+                 "                    [--radiance-in FILE|camera --radiance-out FILE] [--light-sampling] [--mis]\n");
     return 2;
 }
 
@@ -73,7 +74,7 @@ std::vector<float> parse_floats(const std::string &s) {
 int main(int argc, char **argv) {
     std::string mesh, out, ppm, albedoArg, emitArg, pickArg, updateMesh, radianceIn, radianceOut, backend = "cuda";
     int width = 320, height = 180, spp = 16, depth = 8, denoise = -1;
-    bool perFrame = false, present = false, lightSampling = false;
+    bool perFrame = false, present = false, lightSampling = false, mis = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char * { return i + 1 < argc ? argv[++i] : nullptr; };
@@ -81,6 +82,7 @@ int main(int argc, char **argv) {
         if (a == "--per-frame") perFrame = true;
         else if (a == "--present") present = true;
         else if (a == "--light-sampling") lightSampling = true;
+        else if (a == "--mis") mis = true;
         else if ((v = next()) == nullptr) return usage();
         else if (a == "--backend") backend = v;
         else if (a == "--mesh") mesh = v;
@@ -101,7 +103,7 @@ int main(int argc, char **argv) {
     }
     if (backend != "cuda" && backend != "vulkan" && backend != "gl") return usage();
     HipPathTracer tracer;
-    hipptSetOption(HIPPT_OPT_LIGHT_SAMPLING, lightSampling ? 1 : 0);
+    hipptSetOption(HIPPT_OPT_LIGHT_SAMPLING_MODE, mis ? HIPPT_LIGHT_SAMPLING_MIS : lightSampling ? 1 : 0);
     if (!mesh.empty()) {
         // the scene is the library's (shared by every interface)
         const double from[3] = {278, 278, -800}, at[3] = {278, 278, 0}, up[3] = {0, 1, 0};

@@ -4,13 +4,14 @@ oracle and no reference tree: it measures, it does not check.
 
 Per scene (hippt.scenes.cornell_lit of a base scene; a child process of its own, ended after --limit seconds;
 the tool stops at the first child that fails), at 1920x1080 and depth 8:
-  frame time    hipptRenderFrames(f, 1) with no host copy, the option off (the render megakernel) and on (the
-                light-sampling route), alternating call by call after --warmup untimed rounds, each timed by a
-                host clock around the blocking call; the median of --runs calls
+  frame time    hipptRenderFrames(f, 1) with no host copy, the option off (the render megakernel), on (the
+                light-sampling route) and, with --modes 0,1,2 (the default), with MIS (HIPPT_LIGHT_SAMPLING_MIS, the
+                same route), alternating call by call after --warmup untimed rounds, each timed by a host clock
+                around the blocking call; the median of --runs calls
   segments      per frame from hipptGetStats, and with the option on the shadow rays among them (counter 27)
   equal time    a reference image of --ref-spp samples with the option off; then, per entry n of --spp, n frames
                 with the option on and as many frames with it off as take the same time (n * ms_on / ms_off,
-                rounded, at least 1), each from an empty accumulation, timed again; the mean squared error of
+                rounded, at least 1) and n frames with MIS, each from an empty accumulation, timed again; the mean squared error of
                 the accumulated rgb against the reference, the same without the 0.1 % of pixels that err most, and
                 the largest absolute error of a channel.  The reference holds the option-off render's own
                 samples (frames 0..): a share of n / ref-spp of it.
@@ -45,7 +46,7 @@ def child(args):
 
     def render(on, frames):
         """(seconds, segments, shadow rays) of `frames` frames from an empty accumulation."""
-        pt.setOption(hippt.OPT_LIGHT_SAMPLING, on)
+        pt.setOption(hippt.OPT_LIGHT_SAMPLING_MODE, on)
         if not pt.resetAccumulation():
             raise SystemExit(pt.lastError())
         pt.resetStats()
@@ -59,13 +60,15 @@ def child(args):
             raise SystemExit(f"{args.scene}: the render did not take the route asked for")
         return dt, int(c["segments"]), int(c["shadow_rays"])
 
+    modes = tuple(int(x) for x in args.modes.split(","))
+    key = {0: "off", 1: "on", 2: "mis"}
     for _ in range(args.warmup):
-        for on in (0, 1):
+        for on in modes:
             render(on, 1)
-    ms = {0: [], 1: []}
+    ms = {on: [] for on in modes}
     segs, shadow = {}, {}
     for _ in range(args.runs):
-        for on in (0, 1):
+        for on in modes:
             dt, segs[on], shadow[on] = render(on, 1)
             ms[on].append(dt * 1e3)
     med = {on: statistics.median(v) for on, v in ms.items()}
@@ -76,11 +79,11 @@ def child(args):
     for n_on in [int(x) for x in args.spp.split(",")]:
         n_off = max(1, int(round(n_on * med[1] / med[0])))
         row = {}
-        for on, n in ((1, n_on), (0, n_off)):
+        for on, n in ((1, n_on), (0, n_off)) + (((2, n_on),) if 2 in modes else ()):
             dt, s, _ = render(on, n)
             img = pt.readback()[1][..., :3].astype(np.float64)
             err = np.sort(((img - ref) ** 2).mean(axis=-1).ravel())  # per pixel
-            row["on" if on else "off"] = {"frames": n, "ms": round(dt * 1e3, 3), "segments": s, "mse": float(err.mean()),
+            row[key[on]] = {"frames": n, "ms": round(dt * 1e3, 3), "segments": s, "mse": float(err.mean()),
                                           # where the error sits: without the 0.1 % of pixels that err most
                                           "mse_without_worst_permille": float(err[:len(err) - len(err) // 1000].mean()),
                                           "max_abs_error": float(np.abs(img - ref).max())}
@@ -89,12 +92,12 @@ def child(args):
     out = {"scene": sc.name, "primitives": sc.num_tris + sc.num_spheres, "lights": int(lib.hipptGetOption(hippt.INFO_LIGHTS)),
            "width": W, "height": H, "max_depth": DEPTH, "warmup": args.warmup, "runs": args.runs,
            "device": torch.cuda.get_device_name(torch.device("cuda", args.device)),
-           "order": "off, on alternating per call",
-           "ms": {"off": [round(x, 4) for x in ms[0]], "on": [round(x, 4) for x in ms[1]]},
-           "median_ms": {"off": round(med[0], 4), "on": round(med[1], 4)},
-           "segments_per_frame": {"off": segs[0], "on": segs[1]},
+           "order": ", ".join(key[on] for on in modes) + " alternating per call",
+           "ms": {key[on]: [round(x, 4) for x in ms[on]] for on in modes},
+           "median_ms": {key[on]: round(med[on], 4) for on in modes},
+           "segments_per_frame": {key[on]: segs[on] for on in modes},
            "shadow_rays_per_frame": shadow[1], "shadow_share": round(shadow[1] / max(1, segs[1]), 4),
-           "gsegments_per_s": {"off": round(segs[0] / med[0] / 1e6, 3), "on": round(segs[1] / med[1] / 1e6, 3)},
+           "gsegments_per_s": {key[on]: round(segs[on] / med[on] / 1e6, 3) for on in modes},
            "reference": {"spp": args.ref_spp, "option": 0, "seconds": round(t_ref, 3)},
            "equal_time": equal}
     lib.cudaPathTracerShutdown()
@@ -109,6 +112,7 @@ def main():
     ap.add_argument("--runs", type=int, default=9)
     ap.add_argument("--ref-spp", type=int, default=16384)
     ap.add_argument("--spp", default="1,4,16,64", help="frames with the option on of the equal-time comparisons")
+    ap.add_argument("--modes", default="0,1,2", help="values of the option to time: 0,1 or 0,1,2")
     ap.add_argument("--limit", type=float, default=500.0, help="seconds a scene's child process may take")
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "light_sampling"))
     ap.add_argument("--scene", help=argparse.SUPPRESS)  # the child's
@@ -118,7 +122,8 @@ def main():
     os.makedirs(args.out, exist_ok=True)
     for name in args.scenes.split(","):
         cmd = [sys.executable, os.path.abspath(__file__), "--scene", name, "--device", str(args.device), "--warmup",
-               str(args.warmup), "--runs", str(args.runs), "--ref-spp", str(args.ref_spp), "--spp", args.spp]
+               str(args.warmup), "--runs", str(args.runs), "--ref-spp", str(args.ref_spp), "--spp", args.spp, "--modes",
+               args.modes]
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.limit)
         except subprocess.TimeoutExpired:
@@ -130,11 +135,13 @@ def main():
             json.dump(res, fo, indent=1)
             fo.write("\n")
         m = res["median_ms"]
-        eq = "  ".join(f"{e['on']['frames']}v{e['off']['frames']}: {e['on']['mse']:.4g}/{e['off']['mse']:.4g} "
-                       f"({e['on']['mse_without_worst_permille']:.4g}/{e['off']['mse_without_worst_permille']:.4g})"
-                       for e in res["equal_time"])
-        print(f"{res['scene']:18s} off {m['off']:7.3f} ms  on {m['on']:7.3f} ms  shadow share {res['shadow_share']:.3f}  "
-              f"mse on/off at equal time, frames on v off (without the worst 0.1 % of pixels): {eq}", flush=True)
+        cols = [k for k in ("on", "off", "mis") if k in res["equal_time"][0]]
+        eq = "  ".join(f"{e['on']['frames']}v{e['off']['frames']}: " + "/".join(f"{e[k]['mse']:.4g}" for k in cols) + " (" +
+                       "/".join(f"{e[k]['mse_without_worst_permille']:.4g}" for k in cols) + ") max " +
+                       "/".join(f"{e[k]['max_abs_error']:.4g}" for k in cols) for e in res["equal_time"])
+        print(f"{res['scene']:18s} " + "  ".join(f"{k} {v:7.3f} ms" for k, v in m.items()) +
+              f"  shadow share {res['shadow_share']:.3f}  mse {'/'.join(cols)} at equal time, frames on v off (without the "
+              f"worst 0.1 % of pixels) and the largest error: {eq}", flush=True)
 
 
 if __name__ == "__main__":
