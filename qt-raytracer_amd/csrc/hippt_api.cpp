@@ -34,6 +34,7 @@
 
 #include "bvh_builder.h"
 #include "mesh_io.h"
+#include "hippt_chain_logic.h"
 #include "hippt_denoise.h"
 #include "hippt_device.h"
 #include "hippt_path.h"
@@ -217,25 +218,19 @@ struct Ctx {
     int meshBlocksPerCuChain = 0;  // the chained-batch kernel's
     // Chained batches (HIPPT_OPT_CHAIN; MeshParams::chain*, hippt_trace.h): the open run.  Its launches
     // share a ring of `slots` scratch slots and work-counter blocks (chainCtl, zeroed when a run
-    // starts); the host posts each batch in the mailbox (run << 33 | consecutive << 32 | batch) before
+    // starts); the host posts each batch in the mailbox (chain::box_word: run, consecutive frames, batch) before
     // its launch is enqueued, and the run's last combines are a flush before anything reads or
-    // resets the image (flush_deferred).
+    // resets the image (flush_deferred).  The run's integers and every decision over them (continue,
+    // hold, group, post, close) are hippt_chain_logic.h's HostRun and host_* rules, which the protocol
+    // model drives too; here is what is the library's own.
     struct Chain {
-        bool live = false;   // a run is open
-        unsigned run = 0;    // its id
-        unsigned seq = 0;    // the next batch's number in the run
-        unsigned epoch = 0;  // the next launch's number in the run
-        int firstFrame = 0;  // batch 0's first frame
-        int step = -1;       // frames from one batch to the next (-1: one batch so far)
-        unsigned slots = 0, shift = 0, cap = 0;
+        hippt::chain::HostRun host;  // live, run, seq, epoch, firstFrame, step, cap, slots, the held group
+        unsigned shift = 0;
         hippt::MeshParams key{};  // what every batch of the run shares (chain_same)
         long long blocks = 0;
-        unsigned lastOwn = 0;     // the batch of the run's last enqueued launch
         unsigned geomRev = 0;     // SceneHost::geomRev of the run's batches (MeshParams' pointers do not
                                   // change across hipptUpdateVertices)
-        // batches held for one group launch while the run's last launch has not started (chain_batch):
-        // the first one's parameters and their count; flush_chain launches them if the run ends first
-        unsigned pendN = 0;
+        // the first held batch's parameters (host.pendN of them wait for one group launch)
         hippt::MeshParams pendP{};
         unsigned *audit = nullptr;  // the run's audit records (HIPPT_OPT_CHAIN_AUDIT), or null
     } chain;
@@ -553,10 +548,10 @@ void build_camera(const double lookfrom[3], const double lookat[3], const double
     out.reserved = 0.0f;
 }
 
-// The held batches of the open chain run (Ctx::chain.pendN) launched now as one group: before
+// The held batches of the open chain run (Ctx::chain.host.pendN) launched now as one group: before
 // anything frees or replaces a buffer their parameters (Ctx::chain.pendP) point at — scene buffers,
 // node layouts, item tables, the spill area (a held group launched after the free read
-// freed memory).  The run stays open.
+// freed memory).  The run stays open (chain::host_launch_held).
 bool launch_held(Ctx &c, const char **err);
 
 // Item tables no launch reads any more are freed; with `all`, after waiting for the stream.
@@ -1419,30 +1414,33 @@ bool copy_rows_async(Ctx &c, void *dstFrame, const void *src, size_t bytes, cons
 
 // The open chain run's last combines (Ctx::chain): every batch no launch combined, in order; the run
 // ends (the next chained batch starts a new one).
-bool launch_chained(Ctx &c, hippt::MeshParams &p, const char **err);
+bool launch_chained(Ctx &c, hippt::MeshParams &p, const hippt::chain::HostLaunch &l, const char **err);
 
 bool flush_chain(Ctx &c, const char **err) {
     Ctx::Chain &ch = c.chain;
-    if (!ch.live) return true;
+    if (!ch.host.live) return true;
     HIP_TRY(hipSetDevice(c.device));
-    if (!launch_held(c, err)) return false;  // the held batches' group launch, before the run closes
-    ch.live = false;
+    hippt::chain::HostClose cl;
+    hippt::chain::host_close(ch.host, cl);
+    // The held batches' group launch, before the flush.  (The run counts as closed from here on even if
+    // this launch fails: a HIP error of a launch is fatal to the context, and no batch joins the run.)
+    if (cl.held && !launch_chained(c, ch.pendP, cl.launch, err)) return false;
     hippt::ChainFlushParams f{};
     f.comb = ch.key.comb;
     f.scratch = c.chainScratch;
     f.ctl = c.chainCtl;
-    f.epoch = ch.epoch;  // the run's launches were epochs 0 .. epoch - 1
-    f.lastSeq = ch.seq - 1u;
-    f.slots = ch.slots;
+    f.epoch = cl.epoch;
+    f.lastSeq = cl.lastSeq;
+    f.slots = ch.host.slots;
     f.shift = ch.shift;
-    f.step = std::max(ch.step, 0);
+    f.step = cl.step;
     f.audit = ch.audit;
     if (ch.audit && !c.auditRuns.empty()) {  // the run's header: what it asked for
         Ctx::AuditRun &a = c.auditRuns.back();
-        a.hdr[4] = unsigned(ch.step);
-        a.hdr[8] = ch.seq;
-        a.hdr[9] = ch.epoch;
-        a.hdr[11] = ch.seq > hippt::kAuditBatches ? ch.seq - hippt::kAuditBatches : 0u;
+        a.hdr[4] = unsigned(ch.host.step);
+        a.hdr[8] = cl.lastSeq + 1u;
+        a.hdr[9] = cl.epoch;
+        a.hdr[11] = a.hdr[8] > hippt::kAuditBatches ? a.hdr[8] - hippt::kAuditBatches : 0u;
         a.closed = true;
     }
     return TIMED_LAUNCH(c, 1, hippt::launch_chain_flush(f, c.stream));
@@ -1498,53 +1496,11 @@ constexpr bool kChainGroups = HIPPT_CHAIN_GROUPS != 0;
 #endif
 constexpr bool kChainHoldRunning = HIPPT_CHAIN_HOLD_RUNNING != 0;
 
-// The automatic cap's ceiling: 16 for trees in global memory, 8 for LDS-resident scenes.  A bigger
-// cap makes a burst's groups bigger (a 1/8 row share's 20 steps: 3 launches instead of 4), and the
-// launch after a group combines the whole group: hidden behind a global tree's slower batches
-// (blob70k 1/8 share 2.538/2.539 -> 2.497/2.493 ms, 1/4 share 4.799/4.778 -> 4.754/4.754), exposed
-// beside Cornell's (1/8 share 0.991/0.989 -> 1.025/1.015: the last launch's 16-batch combine adds
-// ~0.9 ms), r6n.
-// Batches of more than 2^26 samples (whole 1080p/64 spp images) take cap 8 (r6aw/r6ax: blob70k 22,302 ->
-// 22,391 M/s against cap 3, cornell_mixed 35,314 -> 35,422, Cornell chained at 8 as above; cap 2 and 6
-// lower or equal); the ring (16 slots) stays within the scratch budget (ring_plan) or the cap shrinks.
-unsigned chain_cap(long long option, unsigned total, bool ldsScene) {
-    if (option > 0) return unsigned(std::min<long long>(option, 16));
-    const double c = total > plan::kWholeImageItems ? 8.0 : std::round(4e8 / double(std::max(1u, total)));
-    return unsigned(std::clamp(c, 2.0, ldsScene ? 8.0 : 16.0));
-}
-
-// The ring of a run of `total`-item batches: 2^shift samples per slot (the slot bits above them in
-// an item), at least 2 x cap slots (a launch traces up to cap batches while up to cap batches before
-// its own wait for its combine), 12 bytes per sample.  The ring stays within the sample-scratch
-// budget (HIPPT_OPT_SCRATCH_MB): the cap shrinks until it fits, and a batch whose smallest ring
-// (2 slots) does not fit runs unchained (bytes = 0).  (blob70k at 1080p/64 spp and cap 8
-// asked for 25.8 GB whatever the budget.)
-struct RingPlan {
-    unsigned cap = 0, slots = 0, shift = 0;
-    size_t bytes = 0;
-};
-RingPlan ring_plan(unsigned total, long long option, bool ldsScene, size_t budget) {
-    RingPlan r;
-    r.shift = 6;
-    while ((1u << r.shift) < total) ++r.shift;
-    const size_t slotBytes = (size_t(1) << r.shift) * 3 * sizeof(float);
-    for (unsigned cap = chain_cap(option, total, ldsScene); cap >= 1; --cap) {
-        unsigned slots = 2;
-        while (slots < 2 * cap) slots <<= 1;
-        slots = std::min(slots, hippt::kChainSlotsMax);
-        if (size_t(slots) * slotBytes <= budget) {
-            r.cap = cap;
-            r.slots = slots;
-            r.bytes = size_t(slots) * slotBytes;
-            return r;
-        }
-    }
-    return r;
-}
+// (the cap and the ring of a run: hippt_plan.h chain_cap, ring_slots, ring_plan)
 
 // The ring's buffers for plan `r` (allocated, or grown after the open run's last combines); *ok =
 // false when the device has no memory for them (the batch then runs unchained).
-bool ensure_ring(Ctx &c, const RingPlan &r, bool *ok, const char **err) {
+bool ensure_ring(Ctx &c, const plan::RingPlan &r, bool *ok, const char **err) {
     *ok = true;
     if (!c.chainCtl) HIP_TRY(hipMalloc(&c.chainCtl, hippt::kChainCtlWords * sizeof(unsigned)));
     if (!c.chainBox) {
@@ -1601,32 +1557,32 @@ bool chain_same(const hippt::MeshParams &a, const hippt::MeshParams &b) {
            a.skyRect.x1 == b.skyRect.x1 && a.skyRect.y1 == b.skyRect.y1;
 }
 
-// Enqueues the launch of chained batch p (its chain fields set by chain_batch but the epoch): the run's
-// next launch number, and the start event chain_batch's skip test queries.
-bool launch_chained(Ctx &c, hippt::MeshParams &p, const char **err) {
-    Ctx::Chain &ch = c.chain;
-    p.chainEpoch = ch.epoch++;
-    ch.lastOwn = p.chainSeq;
-    ch.pendN = 0;
+// Enqueues launch `l` of the run (chain::host_add, host_launch_held, host_close) with batch p's
+// parameters, between the start and end events chain_batch's hold test queries.
+bool launch_chained(Ctx &c, hippt::MeshParams &p, const hippt::chain::HostLaunch &l, const char **err) {
+    p.chainSeq = l.own;
+    p.chainGroup = l.group;
+    p.chainPosted = l.posted;
+    p.chainEpoch = l.epoch;
     if (!c.chainStartEv) HIP_TRY(hipEventCreateWithFlags(&c.chainStartEv, hipEventDisableTiming));
     if (!c.chainEndEv) HIP_TRY(hipEventCreateWithFlags(&c.chainEndEv, hipEventDisableTiming));
     HIP_TRY(hipEventRecord(c.chainStartEv, c.stream));
-    if (!TIMED_LAUNCH(c, 0, hippt::launch_mesh(p, int(ch.blocks), false, c.stream))) return false;
+    if (!TIMED_LAUNCH(c, 0, hippt::launch_mesh(p, int(c.chain.blocks), false, c.stream))) return false;
     HIP_TRY(hipEventRecord(c.chainEndEv, c.stream));
     return true;
 }
 
 bool launch_held(Ctx &c, const char **err) {
     Ctx::Chain &ch = c.chain;
-    if (!ch.live || !ch.pendN) return true;
+    if (!hippt::chain::host_has_held(ch.host)) return true;
     HIP_TRY(hipSetDevice(c.device));
-    ch.pendP.chainGroup = ch.pendN;
-    ch.pendP.chainPosted = ch.seq - 1u;
+    hippt::chain::HostLaunch l;
+    hippt::chain::host_launch_held(ch.host, l);
 #ifdef HIPPT_CHAIN_TRACE
-    std::fprintf(stderr, "chain run %u group launched early: own %u batches %u epoch %u\n", ch.run, ch.pendP.chainSeq,
-                 ch.pendN, ch.epoch);
+    std::fprintf(stderr, "chain run %u group launched early: own %u batches %u epoch %u\n", ch.host.run, l.own, l.group,
+                 l.epoch);
 #endif
-    return launch_chained(c, ch.pendP, err);
+    return launch_chained(c, ch.pendP, l, err);
 }
 
 // The closed runs' audit records to State::auditWords (the context's stream finished past their
@@ -1662,36 +1618,20 @@ void harvest_audit(Ctx &c) {
 // of async batches gets one launch per group instead of one per batch (each a ~21 us launch that
 // finds its batch taken, plus the gap between launches; r5j).  A batch launched on its own is posted
 // in the mailbox, so that a running launch may go on with it (chained batches); held batches are
-// not, so no launch but their group's takes them.
-bool chain_batch(Ctx &c, hippt::MeshParams &p, long long blocks, const RingPlan &ring, const char **err) {
+// not, so no launch but their group's takes them.  Every decision here is hippt_chain_logic.h's
+// (host_continues, host_open, host_add); this function does the HIP work around them.
+bool chain_batch(Ctx &c, hippt::MeshParams &p, long long blocks, const plan::RingPlan &ring, const char **err) {
+    namespace chain = hippt::chain;
     Ctx::Chain &ch = c.chain;
+    chain::HostRun &run = ch.host;
     p.comb = hippt::CombineParams{c.accum, c.out, nullptr, p.bandPixels, p.totalItems, 0, p.frames, p.comb.format};
-    bool same = ch.live && blocks == ch.blocks && ch.geomRev == S().scene.geomRev && chain_same(p, ch.key);
-    if (same && ch.seq == 1) {  // the run's frame pattern: every batch the same frames, or the next ones
-        const int d = p.firstFrame - ch.firstFrame;
-        if (d == 0 || d == p.frames)
-            ch.step = d;
-        else
-            same = false;
-    } else if (same && p.firstFrame != ch.firstFrame + int(ch.seq) * ch.step) {
-        same = false;
-    }
-    if (!same) {
+    const bool same = run.live && blocks == ch.blocks && ch.geomRev == S().scene.geomRev && chain_same(p, ch.key);
+    if (!chain::host_continues(run, same, p.firstFrame, p.frames)) {
         if (!flush_deferred(c, err)) return false;  // the old run's (or an unchained batch's) combines
         // (the ring's buffers: ensure_ring, before the batch was chained)
-        const unsigned shift = ring.shift, cap = ring.cap, slots = ring.slots;
         HIP_TRY(hipMemsetAsync(c.chainCtl, 0, hippt::kChainCtlWords * sizeof(unsigned), c.stream));
-        ch.live = true;
-        ch.run = (ch.run + 1u) & 0x7fffffffu;
-        ch.seq = 0;
-        ch.epoch = 0;
-        ch.lastOwn = 0;
-        ch.pendN = 0;
-        ch.firstFrame = p.firstFrame;
-        ch.step = -1;
-        ch.slots = slots;
-        ch.shift = shift;
-        ch.cap = cap;
+        chain::host_open(run, p.firstFrame, ring.cap, ring.slots);
+        ch.shift = ring.shift;
         ch.blocks = blocks;
         ch.geomRev = S().scene.geomRev;
         p.comb.scratch = c.chainScratch;
@@ -1711,14 +1651,14 @@ bool chain_batch(Ctx &c, hippt::MeshParams &p, long long blocks, const RingPlan 
             HIP_TRY(hipMemsetAsync(ch.audit, 0, hippt::kAuditRunWords * sizeof(unsigned), c.stream));
             Ctx::AuditRun a{};
             a.hdr[0] = 0xC4A1D17u;
-            a.hdr[1] = ch.run;
+            a.hdr[1] = run.run;
             a.hdr[2] = unsigned(c.device);
             a.hdr[3] = unsigned(p.firstFrame);
             a.hdr[4] = ~0u;
             a.hdr[5] = unsigned(p.frames);
             a.hdr[6] = p.bandPixels;
             a.hdr[7] = p.totalItems;
-            a.hdr[10] = ch.slots;
+            a.hdr[10] = run.slots;
             a.slab = slab;
             a.closed = false;
             c.auditRuns.push_back(a);
@@ -1729,47 +1669,40 @@ bool chain_batch(Ctx &c, hippt::MeshParams &p, long long blocks, const RingPlan 
     p.queue = c.chainCtl;
     p.combCtr = nullptr;
     p.comb.scratch = c.chainScratch;
-    p.comb.firstFrame = ch.firstFrame;
+    p.comb.firstFrame = run.firstFrame;
     p.chainCtl = c.chainCtl;
     p.chainBox = c.chainBoxDev;
-    p.chainSeq = ch.seq;
-    p.chainRun = ch.run;
-    p.chainSlots = ch.slots;
+    p.chainRun = run.run;
+    p.chainSlots = run.slots;
     p.chainShift = ch.shift;
-    p.chainCap = ch.cap;
-    p.chainStep = ch.step;
-    p.chainPosted = ch.seq;
-    p.chainGroup = 1;
+    p.chainCap = run.cap;
+    p.chainStep = run.step;
     c.hostSamples += p.totalItems;
-    const unsigned seq = ch.seq++;
-    // held while the last launch has not started and the group is not full (64-item runs only: the
-    // group interleaves its batches' runs)
-    // (kChainHoldRunning: also while the run's only launch so far is still running — the burst's
-    // second batch then opens the first group instead of being taken by that launch on its own walk
-    // of the item order and leaving its own launch nothing but the combine)
-    const bool hold = kChainGroups && ch.epoch > 0 && ch.pendN + 1u < ch.cap && p.totalItems % 64u == 0 &&
-                      (hipEventQuery(c.chainStartEv) == hipErrorNotReady ||
-                       (kChainHoldRunning && ch.epoch == 1 && hipEventQuery(c.chainEndEv) == hipErrorNotReady));
+    // What host_add reads of the run's last launch, and no more (chain::host_add_reads).  Groups are for
+    // 64-item runs only: a group interleaves its batches' runs.
+    const bool groupable = kChainGroups && p.totalItems % 64u == 0;
+    const unsigned reads = chain::host_add_reads(run, groupable, kChainHoldRunning);
+    const bool started = !(reads & chain::kReadsStarted) || hipEventQuery(c.chainStartEv) != hipErrorNotReady;
+    const bool ended = !(reads & chain::kReadsEnded) || !started || hipEventQuery(c.chainEndEv) != hipErrorNotReady;
+    const chain::HostAdd a = chain::host_add(run, groupable, started, ended, kChainHoldRunning);
 #ifdef HIPPT_CHAIN_TRACE
-    std::fprintf(stderr, "chain run %u seq %u %s (held %u epoch %u cap %u slots %u)\n", ch.run, seq,
-                 hold ? "held" : ch.pendN ? "launched with the held ones" : "launched", ch.pendN, ch.epoch,
-                 ch.cap, ch.slots);
+    std::fprintf(stderr, "chain run %u seq %u %s (held %u epoch %u cap %u slots %u)\n", run.run, a.seq,
+                 a.kind == chain::kAddHeld ? "held" : a.kind == chain::kAddGroup ? "launched with the held ones" : "launched",
+                 a.held, a.launch.epoch, run.cap, run.slots);
 #endif
-    if (hold) {
-        if (!ch.pendN) ch.pendP = p;
-        ++ch.pendN;
+    switch (a.kind) {
+    case chain::kAddHeld:
+        // the group's own batch (chainSeq, chainGroup, chainPosted and chainEpoch: set at its launch)
+        if (!a.held) ch.pendP = p;
         return true;
+    case chain::kAddGroup:  // the held batches and this one: one group launch
+        return launch_chained(c, ch.pendP, a.launch, err);
+    case chain::kAddAlone:
+        // post: one word, so that a launch reads the run, its frame pattern and the last batch together
+        __atomic_store_n(c.chainBox, a.word, __ATOMIC_RELEASE);
+        return launch_chained(c, p, a.launch, err);
     }
-    if (ch.pendN) {  // the held batches and this one: one group launch
-        hippt::MeshParams q = ch.pendP;
-        q.chainGroup = ch.pendN + 1u;
-        q.chainPosted = seq;
-        return launch_chained(c, q, err);
-    }
-    // post: one word, so that a launch reads the run, its frame pattern and the last batch together
-    const unsigned long long consecutive = ch.step > 0 ? 1u : 0u;
-    __atomic_store_n(c.chainBox, ((unsigned long long)ch.run << 33) | (consecutive << 32) | seq, __ATOMIC_RELEASE);
-    return launch_chained(c, p, err);
+    return true;
 }
 
 // The device address of a mapped pinned host frame on the current device, or null where the
@@ -1996,9 +1929,9 @@ bool enqueue_mesh(Ctx &c, const CameraF &cam, int firstFrame, int count, int max
         const plan::Batch B = plan::batch(facts, s.knobs, L, copy, maxDepth, total);
         const bool fuse = B.fuse;
         bool chained = B.mayChain && c.meshBlocksPerCuChain > 0;
-        RingPlan ring;
+        plan::RingPlan ring;
         if (chained) {
-            ring = ring_plan(total, s.knobs.chainBatches, L.ldsScene, size.budget);
+            ring = plan::ring_plan(total, s.knobs.chainBatches, L.ldsScene, size.budget);
             bool ok = ring.bytes != 0;
             if (ok && !ensure_ring(c, ring, &ok, err)) return false;
             chained = ok;
@@ -2023,7 +1956,7 @@ bool enqueue_mesh(Ctx &c, const CameraF &cam, int firstFrame, int count, int max
                 if (chained) {
                     p.comb.format = s.pixelFormat;
                     if (!chain_batch(c, p, blocks, ring, err)) return false;
-                    s.activeChainCap = int(c.chain.cap);
+                    s.activeChainCap = int(c.chain.host.cap);
                     continue;  // launched or taken by the run's last launch; its combine
                                // belongs to the run (Ctx::chain)
                 } else {

@@ -1,8 +1,11 @@
 // hippt_chain_logic.h — the integer rules of chained batches (hippt_trace.h "chained batches",
 // DESIGN.md §7) as pure functions: which batches a launch combines and traces, what its waves learn
-// from the host mailbox, and the frame offset a wave traces a batch with.  The gfx950 kernels call
-// them; tests/native/chain_model.cpp compiles this header with g++ and drives the protocol through
-// adversarial host/device interleavings (tests/test_chain_protocol.py).
+// from the host mailbox, and the frame offset a wave traces a batch with; and, in the last section,
+// the host's side of a run: when a batch continues it, when a batch is held, grouped or posted, what
+// each launch, the mailbox and the final flush are told.  The gfx950 kernels call the device's rules
+// and hippt_api.cpp (chain_batch, launch_held, flush_chain) the host's; tests/native/chain_model.cpp
+// compiles this header with g++ and drives both through adversarial host/device interleavings
+// (tests/test_chain_protocol.py), so its schedules vouch for the code that ships on either side.
 //
 // The anchor is the reference's frame-ordered accumulation: one launch and one sync per frame,
 // every frame's sample blended into the running average in frame order
@@ -20,7 +23,7 @@
 namespace hippt {
 namespace chain {
 
-// ---- the host mailbox word (pinned, coherent; written by chain_batch when a batch is posted) ----
+// ---- the host mailbox word (pinned, coherent; host_add's word, stored by chain_batch) -----------
 // run << 33 | consecutive frames << 32 | last posted batch
 HIPPT_CL unsigned long long box_word(unsigned run, bool consecutive, unsigned last) {
     return ((unsigned long long)run << 33) | ((unsigned long long)(consecutive ? 1u : 0u) << 32) | last;
@@ -132,6 +135,141 @@ HIPPT_CL void group_item(unsigned got, unsigned t, unsigned group, unsigned &raw
     const unsigned blk = got >> 6, q = blk / group;
     raw = (q << 6) | (got & 63u);
     tItem = t + (blk - q * group);
+}
+
+// ---- the host's side of a run -------------------------------------------------------------------
+// What the host decides about a run, as a state machine over integers: whether a batch continues it
+// (host_continues), a new run (host_open), what becomes of a batch (host_add: held for a group
+// launch, launched with the held ones as one group, or posted in the mailbox and launched alone),
+// the held group launched before a host-side wait (host_launch_held), and the final flush
+// (host_close).  hippt_api.cpp (chain_batch, launch_held, flush_chain) does the HIP work around
+// these calls and takes every number of a launch, of the mailbox and of the flush from their
+// results; the model's host calls them in its schedules.  (The ring's slots for a cap:
+// hippt_plan.h plan::ring_slots.)
+struct HostRun {
+    bool live = false;   // a run is open
+    unsigned run = 0;    // its id
+    unsigned seq = 0;    // the next batch's number in the run
+    unsigned epoch = 0;  // the next launch's number in the run
+    int firstFrame = 0;  // batch 0's first frame
+    int step = -1;       // frames from one batch to the next (-1: one batch so far)
+    unsigned cap = 0, slots = 0;
+    // batches held for one group launch: their count and the first one's number (the group's own batch)
+    unsigned pendN = 0, pendSeq = 0;
+};
+
+// A launch's chain fields: chainSeq, chainGroup, chainPosted, chainEpoch.
+struct HostLaunch {
+    unsigned own = 0, group = 1, posted = 0, epoch = 0;
+};
+
+// same: the caller's verdict that everything but the frames is the run's (the launch parameters, the
+// grid, the geometry).  The run's second batch fixes its frame pattern: every batch the same frames
+// (step 0), or the next ones (step = frames); later batches follow it or do not continue the run.
+HIPPT_CL bool host_continues(HostRun &r, bool same, int firstFrame, int frames) {
+    if (!r.live || !same) return false;
+    if (r.seq == 1u) {
+        const int d = firstFrame - r.firstFrame;
+        if (d != 0 && d != frames) return false;
+        r.step = d;
+        return true;
+    }
+    return firstFrame == r.firstFrame + int(r.seq) * r.step;
+}
+
+// A new run (the old one closed first: host_close), of batches from firstFrame on.
+HIPPT_CL void host_open(HostRun &r, int firstFrame, unsigned cap, unsigned slots) {
+    r.live = true;
+    r.run = (r.run + 1u) & 0x7fffffffu;
+    r.seq = r.epoch = r.pendN = r.pendSeq = 0u;
+    r.firstFrame = firstFrame;
+    r.step = -1;
+    r.cap = cap;
+    r.slots = slots;
+}
+
+HIPPT_CL HostLaunch host_take_launch(HostRun &r, unsigned own, unsigned group, unsigned posted) {
+    HostLaunch l;
+    l.own = own, l.group = group, l.posted = posted, l.epoch = r.epoch++;
+    r.pendN = 0u;
+    return l;
+}
+
+// Which answers about the run's last enqueued launch host_add reads for the next batch — the one
+// place that says so: host_add goes by it, and a caller asks the device for no more (the library: one
+// hipEventQuery per answer; an answer that is not read may be anything).  A batch can only be held
+// behind an earlier launch of the run, while the group has room, so otherwise neither is read.
+// groupable: the caller allows groups for this batch (the library: its build knob, and 64-item runs
+// only, since the group interleaves its batches' runs).  holdRunning: the batches that arrive while
+// the run's only launch so far still runs are held too — the burst's second batch then opens the
+// first group instead of being taken by that launch on its own walk of the item order and leaving
+// its own launch nothing but the combine.
+constexpr unsigned kReadsStarted = 1u;  // `started`
+constexpr unsigned kReadsEnded = 2u;    // `ended`, where `started` is true
+HIPPT_CL unsigned host_add_reads(const HostRun &r, bool groupable, bool holdRunning) {
+    if (!(groupable && r.epoch > 0u && r.pendN + 1u < r.cap)) return 0u;
+    return kReadsStarted | (holdRunning && r.epoch == 1u ? kReadsEnded : 0u);
+}
+
+enum HostAddKind { kAddHeld, kAddGroup, kAddAlone };
+struct HostAdd {
+    HostAddKind kind = kAddHeld;
+    unsigned seq = 0;      // the batch's number in the run
+    unsigned held = 0;     // batches held before this one
+    HostLaunch launch;     // kAddGroup, kAddAlone: the launch to enqueue (kAddHeld: epoch = the next launch's)
+    unsigned long long word = 0;  // kAddAlone: the mailbox word to store before the launch is enqueued
+};
+// The next batch of the open run.  started, ended: the run's last enqueued launch has started / has
+// ended on the device (host_add_reads: which of them are read).  Held while
+// that launch has not started and the group is not full; a batch that is not held is launched with
+// the held ones as one group (own: the first held batch; none of them was posted, so no launch but
+// the group's takes them), or posted and launched on its own.
+HIPPT_CL HostAdd host_add(HostRun &r, bool groupable, bool started, bool ended, bool holdRunning) {
+    HostAdd a;
+    a.seq = r.seq++;
+    a.held = r.pendN;
+    a.launch.epoch = r.epoch;
+    const unsigned reads = host_add_reads(r, groupable, holdRunning);
+    if ((reads & kReadsStarted) && (!started || ((reads & kReadsEnded) && !ended))) {
+        if (!r.pendN) r.pendSeq = a.seq;
+        ++r.pendN;
+        return a;
+    }
+    if (r.pendN) {
+        a.kind = kAddGroup;
+        a.launch = host_take_launch(r, r.pendSeq, r.pendN + 1u, a.seq);
+        return a;
+    }
+    a.kind = kAddAlone;
+    a.word = box_word(r.run, r.step > 0, a.seq);
+    a.launch = host_take_launch(r, a.seq, 1u, a.seq);
+    return a;
+}
+
+// The held batches launched now as one group, the run staying open: false when there are none.
+HIPPT_CL bool host_has_held(const HostRun &r) { return r.live && r.pendN != 0u; }
+HIPPT_CL bool host_launch_held(HostRun &r, HostLaunch &l) {
+    if (!host_has_held(r)) return false;
+    l = host_take_launch(r, r.pendSeq, r.pendN, r.seq - 1u);
+    return true;
+}
+
+// The run's end: the held group's launch, if any, and then the final flush's fields (the run's
+// launches were epochs 0 .. epoch - 1; it combines up to lastSeq).
+struct HostClose {
+    bool held = false;  // `launch` is to be enqueued before the flush
+    HostLaunch launch;
+    unsigned epoch = 0, lastSeq = 0;
+    int step = 0;
+};
+HIPPT_CL bool host_close(HostRun &r, HostClose &c) {  // false: no run is open
+    if (!r.live) return false;
+    c.held = host_launch_held(r, c.launch);
+    r.live = false;
+    c.epoch = r.epoch;
+    c.lastSeq = r.seq - 1u;
+    c.step = r.step > 0 ? r.step : 0;
+    return true;
 }
 
 }  // namespace chain

@@ -8,11 +8,14 @@
 //             pool, the top of the tree in LDS, the wave threshold and the two loop exits
 //   batch()   once per batch: claim size, whether the batch may chain, whether it wants the sky
 //             rectangle and the render pad's trim
+//   ring_plan()  once per batch that may chain: the run's cap (chain_cap), its ring's slots
+//             (ring_slots), the slot size and the ring's bytes within the scratch budget
 //
 // The measurement notes (r2w, r3al, r5s, r6ao, ...: DESIGN_LOG.md) stand beside the rule they justify.
 #pragma once
 
 #include <algorithm>
+#include <cmath>
 #include <cstddef>
 
 namespace hippt {
@@ -31,6 +34,8 @@ constexpr unsigned kWaveWords = 22;
 constexpr int kPoolWordsPinhole = 5, kPoolWordsFull = 8;
 // batches of at most 2^kChainMaxShift items chain (the slot bits above them, kNone above all)
 constexpr unsigned kChainMaxShift = 27;
+// the most ring slots of a chained run (hippt_device.h: the control block's slot blocks; plan::ring_slots)
+constexpr unsigned kChainSlotsMax = 32;
 
 // MeshParams::wide
 enum { kWide2 = 0, kWideFloat = 1, kWideQuant = 2, kWideHybrid = 3, kWideHalf = 4 };
@@ -296,8 +301,8 @@ inline Knobs query_knobs(Knobs k) {
 // rays per claim of a query launch of m rays
 inline unsigned query_chunk(unsigned m) { return m >= (1u << 20) ? 256u : 64u; }
 
-// What depends on the batch.  A batch that may chain is chained once its ring is there (hippt_api.cpp
-// ring_plan, ensure_ring); the claim size and the sky rectangle depend on whether it was: [0] for a
+// What depends on the batch.  A batch that may chain is chained once its ring is there (ring_plan
+// below; hippt_api.cpp ensure_ring); the claim size and the sky rectangle depend on whether it was: [0] for a
 // batch launched on its own, [1] for a chained one.
 struct Batch {
     bool fuse = false;      // the megakernel takes the previous batch's combine along; other batches flush it
@@ -337,6 +342,57 @@ inline Batch batch(const Facts &f, const Knobs &k, const Layout &L, bool copy, i
                                !(f.full && L.ldsScene && L.spills && !chained && !cnt);
     }
     return b;
+}
+
+// The automatic cap's ceiling: 16 for trees in global memory, 8 for LDS-resident scenes.  A bigger
+// cap makes a burst's groups bigger (a 1/8 row share's 20 steps: 3 launches instead of 4), and the
+// launch after a group combines the whole group: hidden behind a global tree's slower batches
+// (blob70k 1/8 share 2.538/2.539 -> 2.497/2.493 ms, 1/4 share 4.799/4.778 -> 4.754/4.754), exposed
+// beside Cornell's (1/8 share 0.991/0.989 -> 1.025/1.015: the last launch's 16-batch combine adds
+// ~0.9 ms), r6n.
+// Batches of more than 2^26 samples (whole 1080p/64 spp images) take cap 8 (r6aw/r6ax: blob70k 22,302 ->
+// 22,391 M/s against cap 3, cornell_mixed 35,314 -> 35,422, Cornell chained at 8 as above; cap 2 and 6
+// lower or equal); the ring (16 slots) stays within the scratch budget (ring_plan) or the cap shrinks.
+inline unsigned chain_cap(long long option, unsigned total, bool ldsScene) {
+    if (option > 0) return unsigned(std::min<long long>(option, 16));
+    const double c = total > kWholeImageItems ? 8.0 : std::round(4e8 / double(std::max(1u, total)));
+    return unsigned(std::clamp(c, 2.0, ldsScene ? 8.0 : 16.0));
+}
+
+// The ring slots of a run whose launches trace up to `cap` batches: the power of two >= 2 x cap (a
+// launch traces up to cap batches while up to cap batches before its own wait for its combine), at
+// most kChainSlotsMax.  The one definition: ring_plan and the protocol model (tests/native/
+// chain_model.cpp) size their rings with it.
+inline unsigned ring_slots(unsigned cap) {
+    unsigned slots = 2;
+    while (slots < 2 * cap) slots <<= 1;
+    return std::min(slots, kChainSlotsMax);
+}
+
+// The ring of a run of `total`-item batches: 2^shift samples per slot (the slot bits above them in
+// an item), ring_slots(cap) slots, 12 bytes per sample.  The ring stays within the sample-scratch
+// budget (HIPPT_OPT_SCRATCH_MB): the cap shrinks until it fits, and a batch whose smallest ring
+// (2 slots) does not fit runs unchained (bytes = 0).  (blob70k at 1080p/64 spp and cap 8
+// asked for 25.8 GB whatever the budget.)
+struct RingPlan {
+    unsigned cap = 0, slots = 0, shift = 0;
+    size_t bytes = 0;
+};
+inline RingPlan ring_plan(unsigned total, long long option, bool ldsScene, size_t budget) {
+    RingPlan r;
+    r.shift = 6;
+    while ((1u << r.shift) < total) ++r.shift;
+    const size_t slotBytes = (size_t(1) << r.shift) * 3 * sizeof(float);
+    for (unsigned cap = chain_cap(option, total, ldsScene); cap >= 1; --cap) {
+        const unsigned slots = ring_slots(cap);
+        if (size_t(slots) * slotBytes <= budget) {
+            r.cap = cap;
+            r.slots = slots;
+            r.bytes = size_t(slots) * slotBytes;
+            return r;
+        }
+    }
+    return r;
 }
 
 }  // namespace plan

@@ -2,16 +2,19 @@
 // batches", hippt_api.cpp chain_batch / flush_chain), built and run by
 // tests/test_chain_protocol.py.  Test infrastructure, not product code.
 //
-// The integer rules come from the product's own header (qt-raytracer_amd/csrc/hippt_chain_logic.h:
-// view_merge, view_takes, begin_plan, marker_finished, next_batch, group_item, frame_add, copy_pack);
-// around them this file restates, as small state machines, what runs concurrently on the GPU and the
-// host: the waves of a launch (claiming work units from ring-slot counters, moving to the next batch,
-// asking the block's LDS view and the per-XCD copy of the mailbox in the same micro-steps as
-// chain_ask: two-word reads, the busy claim, the bounded wait, the refresh claim, the two-word
-// write), the combine of [c0, c1], the stream's order (launch, final flush, control-block reset),
-// and the host's chain_batch (new run, held batches, group launches, posting the mailbox word).
-// A seeded scheduler interleaves host calls and device micro-steps adversarially, with a clock that
-// makes views and copies fresh or stale at random.
+// The integer rules come from the product's own header (qt-raytracer_amd/csrc/hippt_chain_logic.h).
+// The device's: view_merge, view_takes, begin_plan, marker_finished, next_batch, group_item,
+// frame_add, copy_pack.  The host's: host_continues, host_open, host_add, host_launch_held,
+// host_close — the very calls hippt_api.cpp's chain_batch / launch_held / flush_chain make (new run,
+// held batches, group launches, the mailbox word, the flush's fields) — and the ring's slots from
+// hippt_plan.h ring_slots.  Around them this file restates, as small state machines, what runs
+// concurrently on the GPU: the waves of a launch (claiming work units from ring-slot counters,
+// moving to the next batch, asking the block's LDS view and the per-XCD copy of the mailbox in the
+// same micro-steps as chain_ask: two-word reads, the busy claim, the bounded wait, the refresh claim,
+// the two-word write), the combine of [c0, c1] and the stream's order (launch, final flush,
+// control-block reset); and it keeps the books: what the host asked for and what was traced and
+// combined.  A seeded scheduler interleaves host calls and device micro-steps adversarially, with a
+// clock that makes views and copies fresh or stale at random.
 //
 // The anchor is the reference's accumulation: every frame's sample blended once, in frame order
 // (CudaPathTracerKernel.cu:157-178, 246-265).  Checked, per run and batch: every work unit traced
@@ -19,7 +22,8 @@
 // combined; every batch combined exactly once, in order, only after it is fully traced, with its own
 // frames; every wave of a launch computes the same plan; a wave's known step never changes.
 //
-// usage: chain_model fixed|legacy|small-ring|own-markers SEEDS [FIRST_SEED]   -> "violations N scenarios S ..." (exit 0)
+// usage: chain_model fixed|legacy|small-ring|own-markers|drop-held|fixed-early SEEDS [FIRST_SEED]
+//                                                      -> "violations N scenarios S ..." (exit 0)
 //        chain_model directed                          -> the GPUTEST_r05 interleaving, step by step
 #include <cstdint>
 #include <cstdio>
@@ -31,6 +35,7 @@
 #include <vector>
 
 #include "hippt_chain_logic.h"
+#include "hippt_plan.h"
 
 using namespace hippt::chain;
 
@@ -62,11 +67,17 @@ static const Rules kFixed{"fixed", true, view_merge, view_takes, view_flags_at_s
 static const Rules kLegacy{"legacy", false, legacy_view_merge, legacy_takes, legacy_start_flags};
 
 // Mutants of the fixed rules (the model must catch each; tests/test_chain_protocol.py):
-// "small-ring": a ring of fewer than 2 x cap slots (chain_batch sizes it 2 x cap: a launch traces
+// "small-ring": a ring of fewer than 2 x cap slots (plan::ring_slots sizes it 2 x cap: a launch traces
 // up to cap batches while the batches before its own, up to cap of them, wait for its combine);
 // "own-markers": a launch counts the batches its own waves have moved into as finished.
 static const Rules kSmallRing{"small-ring", true, view_merge, view_takes, view_flags_at_start};
 static const Rules kOwnMarkers{"own-markers", true, view_merge, view_takes, view_flags_at_start};
+// "drop-held": a host mutant — the run is closed without the held group's launch (host_close's
+// `held` ignored).
+static const Rules kDropHeld{"drop-held", true, view_merge, view_takes, view_flags_at_start};
+// Not a mutant: the fixed rules with one more host operation, the held group launched early while
+// the run stays open (host_launch_held; the library does it before host-side waits).
+static const Rules kFixedEarly{"fixed-early", true, view_merge, view_takes, view_flags_at_start};
 
 // ---- seeded randomness -------------------------------------------------------------------------------
 struct Rng {
@@ -145,15 +156,14 @@ struct Model {
     unsigned long long now = 1000000;
     // host
     unsigned long long box = 0;
-    struct HostRun {
-        bool live = false;
-        unsigned run = 0, seq = 0, epoch = 0, pendN = 0;
-        long firstFrame = 0;
-        int step = -1, frames = 1, key = 0;
-        Item pendP{kLaunch};
-        int lastLaunch = -1;  // stream index of the run's last enqueued launch
-    } H;
+    HostRun H;  // the product's run state (hippt_chain_logic.h "the host's side of a run")
+    // the model's own: the run's key (what the library's chain_same compares) and frames per batch, the
+    // first held batch's item, the stream index of the run's last enqueued launch
+    int runFrames = 1, runKey = 0;
+    Item pendP{kLaunch};
+    int lastLaunch = -1;
     int key = 0;
+    long earlyLaunches = 0;  // fixed-early: held groups launched before the run closed
     long lastFF = 0;
     // truth: frames of (run, batch) and what happened to them
     std::map<std::pair<unsigned, unsigned>, long> truth;
@@ -183,9 +193,9 @@ struct Model {
 
     Model(const Rules &r, uint64_t seed, Violations &v) : R(r), rng(seed), V(v) {
         cap = 1 + rng.below(rng.chance(0.25) ? 16 : 8);
-        slots = 2;
-        while (slots < (&R == &kSmallRing ? cap : 2 * cap)) slots <<= 1;
-        if (slots > 32) slots = 32;
+        slots = hippt::plan::ring_slots(cap);
+        if (&R == &kSmallRing)  // the mutant's own ring: the power of two >= cap
+            for (slots = 2; slots < cap;) slots <<= 1;
         blocks = 1 + rng.below(4);
         wavesPerBlock = 1 + rng.below(3);
         units = 1 + rng.below(12);
@@ -209,67 +219,51 @@ struct Model {
         return b;
     }
 
-    // ---- host: chain_batch / flush_chain (hippt_api.cpp) ------------------------------------------
-    bool lastLaunchStarted() const { return H.lastLaunch < 0 || stream[size_t(H.lastLaunch)].started; }
+    // ---- host: the product's rules (host_continues, host_open, host_add, host_launch_held,
+    // host_close) with the stream, the mailbox and the truth around them, as hippt_api.cpp's
+    // chain_batch / launch_held / flush_chain have the HIP work ----------------------------------
+    bool lastLaunchStarted() const { return lastLaunch < 0 || stream[size_t(lastLaunch)].started; }
     // the run's last launch has ended: the device is past it in the stream
-    bool lastLaunchFinished() const {
-        return H.lastLaunch < 0 || head > size_t(H.lastLaunch);
-    }
-    void enqueueLaunch(Item p) {
-        p.epoch = H.epoch++;
-        H.pendN = 0;
+    bool lastLaunchFinished() const { return lastLaunch < 0 || head > size_t(lastLaunch); }
+    void enqueueLaunch(Item p, const HostLaunch &l) {
+        p.own = l.own, p.group = l.group, p.posted = l.posted, p.epoch = l.epoch;
         stream.push_back(p);
-        H.lastLaunch = int(stream.size() - 1);
+        lastLaunch = int(stream.size() - 1);
     }
     void flushChain() {
-        if (!H.live) return;
-        if (H.pendN) {
-            Item q = H.pendP;
-            q.group = H.pendN;
-            q.posted = H.seq - 1u;
-            enqueueLaunch(q);
-        }
-        H.live = false;
+        HostClose cl;
+        if (!host_close(H, cl)) return;
+        if (cl.held && &R != &kDropHeld) enqueueLaunch(pendP, cl.launch);
         Item f{kFlush};
         f.run = H.run;
-        f.epoch = H.epoch;
-        f.lastSeq = H.seq - 1u;
+        f.epoch = cl.epoch;
+        f.lastSeq = cl.lastSeq;
         f.slots = slots;
-        f.step = H.step > 0 ? H.step : 0;
+        f.step = cl.step;
         f.runFirst = H.firstFrame;
-        f.frames = H.frames;
+        f.frames = runFrames;
         f.units = int(units);
         stream.push_back(f);
-        lastSeqOf[H.run] = H.seq - 1u;
+        lastSeqOf[H.run] = cl.lastSeq;
+    }
+    void launchHeldEarly() {  // the library's launch_held before a host-side wait: the run stays open
+        HostLaunch l;
+        if (!host_launch_held(H, l)) return;
+        enqueueLaunch(pendP, l);
+        ++earlyLaunches;
     }
     void render(long ff, int frames, int k) {
-        bool same = H.live && H.key == k && H.frames == frames;
-        if (same && H.seq == 1) {
-            const long d = ff - H.firstFrame;
-            if (d == 0 || d == frames)
-                H.step = int(d);
-            else
-                same = false;
-        } else if (same && ff != H.firstFrame + long(H.seq) * H.step) {
-            same = false;
-        }
-        if (!same) {
+        if (!host_continues(H, runKey == k && runFrames == frames, int(ff), frames)) {
             flushChain();
             stream.push_back(Item{kReset});
-            H.live = true;
-            H.run = (H.run + 1u) & 0x7fffffffu;
-            H.seq = H.epoch = H.pendN = 0;
-            H.firstFrame = ff;
-            H.step = -1;
-            H.frames = frames;
-            H.key = k;
-            H.lastLaunch = -1;
+            host_open(H, int(ff), cap, slots);
+            runFrames = frames;
+            runKey = k;
+            lastLaunch = -1;
             nextCombine[H.run] = 0;
         }
         Item p{kLaunch};
         p.run = H.run;
-        p.own = H.seq;
-        p.posted = H.seq;
         p.step = H.step;
         p.cap = cap;
         p.slots = slots;
@@ -279,33 +273,28 @@ struct Model {
         p.runFirst = H.firstFrame;
         truth[{H.run, H.seq}] = ff;
         traced[{H.run, H.seq}] = std::vector<int>(units, 0);
-        const unsigned seq = H.seq++;
-        // hippt_api.cpp chain_batch: held while the run's last launch has not started, and (kChainHoldRunning)
-        // while the run's only launch so far still runs
-        const bool hold = H.epoch > 0 && H.pendN + 1u < cap &&
-                          (!lastLaunchStarted() || (holdRunning && H.epoch == 1 && !lastLaunchFinished()));
-        if (hold) {
-            if (!H.pendN) H.pendP = p;
-            ++H.pendN;
-            return;
+        // as the library asks: only for the answers host_add reads (the others: "true", which it must ignore)
+        const unsigned reads = host_add_reads(H, true, holdRunning);
+        const bool started = !(reads & kReadsStarted) || lastLaunchStarted();
+        const bool ended = !(reads & kReadsEnded) || !started || lastLaunchFinished();
+        const HostAdd a = host_add(H, true, started, ended, holdRunning);
+        if (a.kind == kAddHeld) {
+            if (!a.held) pendP = p;
+        } else if (a.kind == kAddGroup) {
+            enqueueLaunch(pendP, a.launch);
+        } else {
+            box = a.word;
+            enqueueLaunch(p, a.launch);
         }
-        if (H.pendN) {
-            Item q = H.pendP;
-            q.group = H.pendN + 1u;
-            q.posted = seq;
-            enqueueLaunch(q);
-            return;
-        }
-        box = box_word(H.run, H.step > 0, seq);
-        enqueueLaunch(p);
     }
 
     void hostOp() {
         // per scenario: how often the host leaves the run (burst of progressive batches, then a
         // camera move) and how often it reads the image
+        if (&R == &kFixedEarly && rng.chance(0.2)) return launchHeldEarly();
         unsigned r = rng.below(100);
         if (r >= 55 && r < 92 && !rng.chance(leaveRate)) r = 0;
-        const int frames = H.live ? H.frames : 1 + int(rng.below(2));
+        const int frames = H.live ? runFrames : 1 + int(rng.below(2));
         if (r < 55) {
             const long ff = H.live ? H.firstFrame + long(H.seq) * (H.step < 0 ? frames : H.step) : lastFF;
             render(ff, frames, key);
@@ -738,10 +727,10 @@ static int directed() {
 int main(int argc, char **argv) {
     if (argc >= 2 && std::strcmp(argv[1], "directed") == 0) return directed();
     if (argc < 3) {
-        std::fprintf(stderr, "usage: chain_model fixed|legacy|small-ring|own-markers SEEDS [FIRST_SEED] | directed\n");
+        std::fprintf(stderr, "usage: chain_model fixed|legacy|small-ring|own-markers|drop-held|fixed-early SEEDS [FIRST_SEED] | directed\n");
         return 2;
     }
-    const Rules *rules[] = {&kFixed, &kLegacy, &kSmallRing, &kOwnMarkers};
+    const Rules *rules[] = {&kFixed, &kLegacy, &kSmallRing, &kOwnMarkers, &kDropHeld, &kFixedEarly};
     const Rules *pick = nullptr;
     for (const Rules *r : rules)
         if (std::strcmp(argv[1], r->name) == 0) pick = r;
@@ -753,7 +742,7 @@ int main(int argc, char **argv) {
     const long seeds = std::atol(argv[2]);
     const long first = argc > 3 ? std::atol(argv[3]) : 1;
     Violations V;
-    long scenarios = 0, launches = 0, batches = 0, st[4] = {0, 0, 0, 0};
+    long scenarios = 0, launches = 0, batches = 0, early = 0, st[4] = {0, 0, 0, 0};
     for (long s = first; s < first + seeds; ++s) {
         const long before = V.total();
         Model m(R, uint64_t(s), V);
@@ -762,11 +751,13 @@ int main(int argc, char **argv) {
         ++scenarios;
         for (auto &it : m.stream) launches += it.kind == kLaunch;
         batches += long(m.truth.size());
+        early += m.earlyLaunches;
         for (int k = 0; k < 4; ++k) st[k] += m.stats[k];
     }
     std::printf("rules %s violations %ld scenarios %ld launches %ld batches %ld", R.name, V.total(), scenarios,
                 launches, batches);
     std::printf(" closed_merges %ld closed_answers %ld closed_takes %ld", st[0], st[1], st[2]);
+    if (&R == &kFixedEarly) std::printf(" early_launches %ld", early);
     for (auto &kv : V.n) std::printf(" %s=%ld", kv.first.c_str(), kv.second);
     std::printf("\n");
     if (!V.first.empty()) std::printf("first: %s\n", V.first.c_str());

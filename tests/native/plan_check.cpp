@@ -12,6 +12,9 @@
 //            synthetic facts x knobs: every plan satisfies what launch_mesh (hippt_kernels.hip) and
 //            launch_query (hippt_query.hip) check before they launch.  Prints the number of plans and
 //            of violations (the first few in words); exit status 1 on any.
+//        plan_check ring FILE
+//            one case per line of FILE, integers: total option ldsScene budgetBytes.  Prints ring_plan's
+//            answer for each: cap slots shift bytes.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -55,6 +58,19 @@ int run_rows(const char *path) {
                     L.poolOffset, L.refBits, L.waveThreshold, L.leafExit, L.nodeExit, int(b.fuse), int(b.mayChain),
                     int(b.trimWanted), b.chunk[0], b.chunk[1], int(b.skyWanted[0]), int(b.skyWanted[1]),
                     int(plan::wants_half(a, k, lim)));
+    }
+    std::fclose(f);
+    return 0;
+}
+
+int run_ring(const char *path) {
+    FILE *f = std::fopen(path, "r");
+    if (!f) return 2;
+    long long total, option, lds;
+    unsigned long long budget;
+    while (std::fscanf(f, "%lld %lld %lld %llu", &total, &option, &lds, &budget) == 4) {
+        const plan::RingPlan r = plan::ring_plan(unsigned(total), option, lds != 0, size_t(budget));
+        std::printf("%u %u %u %llu\n", r.cap, r.slots, r.shift, (unsigned long long)r.bytes);
     }
     std::fclose(f);
     return 0;
@@ -165,7 +181,8 @@ int run_sweep(size_t sceneLimit, size_t blockBudget) {
 
 int main(int argc, char **argv) {
     if (argc == 3 && !std::strcmp(argv[1], "rows")) return run_rows(argv[2]);
+    if (argc == 3 && !std::strcmp(argv[1], "ring")) return run_ring(argv[2]);
     if (argc == 4 && !std::strcmp(argv[1], "sweep")) return run_sweep(size_t(std::atoll(argv[2])), size_t(std::atoll(argv[3])));
-    std::fprintf(stderr, "usage: plan_check rows FILE | plan_check sweep SCENE_LIMIT BLOCK_BUDGET\n");
+    std::fprintf(stderr, "usage: plan_check rows FILE | plan_check ring FILE | plan_check sweep SCENE_LIMIT BLOCK_BUDGET\n");
     return 2;
 }

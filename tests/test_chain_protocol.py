@@ -1,7 +1,9 @@
 """The chained-batch protocol (hippt_trace.h "chained batches", hippt_api.cpp chain_batch)
 as a host-compiled model: tests/native/chain_model.cpp drives the product's own integer rules
-(qt-raytracer_amd/csrc/hippt_chain_logic.h, the header the gfx950 kernels include) through seeded
-adversarial interleavings of host calls and device micro-steps, and checks the reference's contract
+(qt-raytracer_amd/csrc/hippt_chain_logic.h, the header the gfx950 kernels and hippt_api.cpp include:
+the device's rules, and the host's run state machine host_continues / host_open / host_add /
+host_launch_held / host_close that chain_batch, launch_held and flush_chain call; the ring's slots
+from hippt_plan.h ring_slots) through seeded adversarial interleavings of host calls and device micro-steps, and checks the reference's contract
 for every batch of every run: each work unit traced exactly once with its batch's frames, each batch
 combined exactly once, in order, after it is fully traced, from an intact ring slot
 (CudaPathTracerKernel.cu:157-178: one sample per frame, blended in frame order).
@@ -9,7 +11,9 @@ combined exactly once, in order, after it is fully traced, from an intact ring s
 The round-5 rules are restated in the model (`legacy`): the model reproduces the recorded GPU failure
 (GPUTEST_r05: a batch's items traced with another batch's frames), and the fixed rules never fail.
 Mutants of the fixed rules (a ring under 2 x cap slots, a launch counting its own waves' batches as
-finished) must be caught, so that a green run means the checks can see a broken protocol.  No GPU.
+finished, a host that closes a run without launching its held group) must be caught, so that a green
+run means the checks can see a broken protocol.  `fixed-early` adds the host operation the library
+performs before host-side waits: the held group launched while the run stays open.  No GPU.
 """
 import os
 import re
@@ -69,7 +73,16 @@ def test_fixed_rules_hold_over_many_schedules(model):
     assert counts["launches"] > 50000 and counts["batches"] > 100000, text
 
 
-@pytest.mark.parametrize("mutant,kind", [("small-ring", "slot"), ("own-markers", "untraced")])
+def test_fixed_rules_hold_with_held_groups_launched_early(model):
+    """The fixed rules with launch_held's operation in the schedules (chain::host_launch_held: the held
+    group launched before the run closes).  Seeds 1..6000: 15159 early group launches, no violation."""
+    counts, text = run(model, "fixed-early", 6000, 1)
+    assert counts["violations"] == 0, text
+    assert counts["early_launches"] > 0, text
+
+
+# (drop-held: the run reports `untraced` first — its flush combines the held batches nobody traced)
+@pytest.mark.parametrize("mutant,kind", [("small-ring", "slot"), ("own-markers", "untraced"), ("drop-held", "untraced")])
 def test_model_catches_broken_rules(model, mutant, kind):
     counts, text = run(model, mutant, 500, 1)
     assert counts.get(kind, 0) > 0, text

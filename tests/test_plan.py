@@ -2,8 +2,10 @@
 the product's own planner: tests/native/plan_check.cpp.  The yardstick is a recording of every scalar a
 launch received at the commit before the planner existed (tests/golden/traversal_plan_parent.json: the
 megakernel, wavefront, chained and query launch sites over a matrix of scenes and options on an MI355X):
-the planner, fed a row's facts, options and call, returns the row's values exactly.  No GPU.
+the planner, fed a row's facts, options and call, returns the row's values exactly.  The chained run's
+ring (chain_cap, ring_slots, ring_plan) has its own recording, tests/golden/ring_plan_parent.json.  No GPU.
 """
+import json
 import os
 import subprocess
 
@@ -137,6 +139,47 @@ def test_the_query_profile_is_the_wavefront_over_float_nodes_without_a_pool(plan
     for r, q, g in zip(rows, query, render):
         for key in layout:
             assert q[key] == g[key], (r["scene"], r["over"], r["site"], key)
+
+
+def ring_rows():
+    """tests/golden/ring_plan_parent.json: chain_cap / ring_plan as they stood in hippt_api.cpp at the commit
+    before they moved into hippt_plan.h, over total x HIPPT_OPT_CHAIN x ldsScene x scratch budget."""
+    with open(os.path.join(REPO, "tests", "golden", "ring_plan_parent.json")) as f:
+        doc = json.load(f)
+    return [dict(zip(doc["columns"], row)) for row in doc["rows"]]
+
+
+def test_the_ring_plan_returns_every_recorded_row(exe, tmp_path):
+    rows = ring_rows()
+    path = tmp_path / "ring.txt"
+    path.write_text("".join("%d %d %d %d\n" % (r["total"], r["option"], r["ldsScene"], r["budget"]) for r in rows))
+    out = subprocess.run([exe, "ring", str(path)], capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0, out.stderr
+    lines = out.stdout.splitlines()
+    assert len(lines) == len(rows)
+    for r, line in zip(rows, lines):
+        got = dict(zip(("cap", "slots", "shift", "bytes"), map(int, line.split())))
+        assert got == {k: r[k] for k in got}, r
+
+
+def test_the_ring_recording_covers_every_branch():
+    rows = ring_rows()
+    auto = [r for r in rows if r["option"] <= 0]
+    # both ceilings of the automatic cap: 8 for LDS-resident scenes, 16 for trees in global memory
+    assert any(r["ldsScene"] and r["cap"] == 8 and r["total"] < 4e8 / 8.5 for r in auto)
+    assert any(not r["ldsScene"] and r["cap"] == 16 and r["total"] < 4e8 / 16.5 for r in auto)
+    # batches of more than a whole image's items: cap 8 whatever the scene
+    assert any(not r["ldsScene"] and r["total"] > 1 << 26 and r["cap"] == 8 for r in auto)
+    # a cap shrunk to the budget: below what the same case gets with the largest budget
+    most = {(r["total"], r["option"], r["ldsScene"]): r["cap"] for r in rows if r["budget"] == 64 << 30}
+    assert any(0 < r["cap"] < most[r["total"], r["option"], r["ldsScene"]] for r in rows)
+    assert any(r["bytes"] == 0 and r["cap"] == 0 for r in rows), "unchained"
+    assert any(r["slots"] == 32 for r in rows), "the 32-slot ring"
+    # Recorded, not endorsed: 32 slots of 2^27 items use every bit of an item, so slot 31's last item
+    # encodes as kNone (ADVICE.md's open finding).  The row keeps the parent's answer; the fix changes
+    # behaviour and is its own change.
+    assert any(r["total"] == 1 << 27 and r["option"] == 16 and r["budget"] == 64 << 30 and r["slots"] == 32 and
+               r["shift"] == 27 for r in rows)
 
 
 def test_no_plan_is_one_the_launchers_would_refuse(exe):
