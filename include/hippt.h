@@ -163,7 +163,11 @@ bool hipptUpdateVertices(const float *verts, int numTris, int flags, const char 
  * that interior child codes are byte offsets, node * 128; primitive records of 12 words in BVH leaf
  * order, the primitive id in word 9, 1 in word 10 for a sphere; shading records of 4 words: normal and
  * material word) into dst after the queued work; dst null: returns the bytes needed.  -1 on error. */
-enum { HIPPT_SCENE_NODES2 = 0, HIPPT_SCENE_NODES4 = 1, HIPPT_SCENE_PRIMS = 2, HIPPT_SCENE_SHADE = 3 };
+enum { HIPPT_SCENE_NODES2 = 0, HIPPT_SCENE_NODES4 = 1, HIPPT_SCENE_PRIMS = 2, HIPPT_SCENE_SHADE = 3,
+       /* the light selection table (HIPPT_OPT_LIGHT_SELECT below), as the device built it: one record of 4
+          words per light in ascending primitive id: the primitive id as uploaded, q_j, c_j, the bits of
+          ip_j; 0 bytes for a scene without lights or with more than 2^20 - 1 */
+       HIPPT_SCENE_LIGHTS = 4 };
 long long hipptSceneDownload(int what, void *dst, long long bytes, const char **errorMessage);
 
 /* ---- devices and row bands ------------------------------------------------------- */
@@ -498,6 +502,14 @@ enum {
                                        said of HIPPT_OPT_LIGHT_SAMPLING 1 holds for 2: the render route, the
                                        next call without an upload, the option-off code for a scene without
                                        an emissive primitive */
+    , HIPPT_OPT_LIGHT_SELECT = 39   /* how a connection picks its light under HIPPT_OPT_LIGHT_SAMPLING_MODE 1 and 2:
+                                       0 (default) uniformly over the list, byte for byte as before the option
+                                       existed; HIPPT_LIGHT_SELECT_POWER (1): in proportion to area x emission, by
+                                       a table the device builds with the scene and rebuilds behind every
+                                       hipptUpdateVertices in stream order (the third rule below).  Other values
+                                       are rejected.  Takes effect at the next render or hipptTraceRadiance,
+                                       without an upload; ignored while the light-sampling mode is 0 or the
+                                       scene has no light, and uniform for more than 2^20 - 1 lights */
 };
 /* Light sampling (HIPPT_OPT_LIGHT_SAMPLING 1; this library's own, as the emissive rule is; tests/nee_ref.py
  * restates it in numpy float32 and the GPU matches that bit for bit).  A path carries
@@ -518,7 +530,8 @@ enum {
  *     g = (((cosS * cosL) * A) * float(nLights)) / (3.14159274f * d2); Ld.c = (thr'.c * Le.c) * g
  *     the shadow ray (p, om), tmin 0.001, no tmax, is a closest-hit query: if its hit is light k,
  *     Lacc.c += Ld.c.  The path goes on along the scattered ray.
- * No MIS under 1 (HIPPT_LIGHT_SAMPLING_MIS below adds it); one light per vertex, uniform over the list.  maxDepth means what it meant: the connection at
+ * No MIS under 1 (HIPPT_LIGHT_SAMPLING_MIS below adds it); one light per vertex, uniform over the list
+ * unless HIPPT_OPT_LIGHT_SELECT (the third rule below) says otherwise.  maxDepth means what it meant: the connection at
  * vertex d stands for the light hit of segment d + 1 and is made exactly when that segment would exist.
  * segments (hipptTraceRadiance, hipptGetStats) count every closest-hit query traced, shadow rays included. */
 enum { HIPPT_LIGHT_SAMPLING_MIS = 2 /* a value of HIPPT_OPT_LIGHT_SAMPLING_MODE */ };
@@ -550,7 +563,40 @@ enum { HIPPT_LIGHT_SAMPLING_MIS = 2 /* a value of HIPPT_OPT_LIGHT_SAMPLING_MODE 
  * brighter than the lights: every connection adds at most thr' * Le / 2. */
 enum { HIPPT_INFO_LIGHTS = 107          /* emissive primitives in the uploaded scene */,
        HIPPT_INFO_LIGHT_SAMPLING = 108  /* the value of HIPPT_OPT_LIGHT_SAMPLING_MODE (1 or 2) that the last render
-                                           applied if it took the light-sampling route, else 0 */ };
+                                           applied if it took the light-sampling route, else 0 */,
+       HIPPT_INFO_LIGHT_SELECT = 109    /* the value of HIPPT_OPT_LIGHT_SELECT that the last render applied if it
+                                           took the light-sampling route, else 0 (0 too above the light limit) */ };
+enum { HIPPT_LIGHT_SELECT_POWER = 1 /* a value of HIPPT_OPT_LIGHT_SELECT */ };
+/* Light selection by power (HIPPT_OPT_LIGHT_SELECT HIPPT_LIGHT_SELECT_POWER; tests/select_ref.py restates it in
+ * numpy integers and float32 and the GPU matches that bit for bit, the table word for word).  It
+ * replaces the selection draw and the factor float(nLights) of the two rules above; nothing else changes.
+ * The table, over the lights j = 0 .. n-1 (the emissive primitives in ascending id), is made of integers, so
+ * that no word depends on the order in which a parallel scan or reduction adds; each float operation is one
+ * float32 operation in the association written:
+ *   A_j    the light's area as the connection forms it (triangle: 0.5f * sqrtf(|cross(e1, e2)|^2) from the
+ *          primitive record's edges; sphere: (12.566371f * r) * r)
+ *   y_j    (Le.r + Le.g) + Le.b of its material
+ *   lit_j  A_j > 0 and y_j > 0 (false for NaN);   W_j = lit_j ? A_j * y_j : 0
+ *   Wmax   max_j W_j;   flat = not (Wmax > 0 and Wmax < +inf)
+ *   q_j    not lit_j: 0;   flat: 1;   else min(4096, max(1, int((W_j / Wmax) * 4096.0f)))     (uint32)
+ *   c_j    q_0 + ... + q_j (uint32, inclusive);   T = c_{n-1}
+ *   ip_j   q_j > 0 ? float(T) / float(q_j) : 0     (the inverse of the selection probability)
+ * n <= 2^20 - 1 keeps T below 2^32; above that there is no table and the choice stays uniform.
+ *   selection draw: rng = hash32(rng), one draw, the state advancing exactly as rand01 advances it;
+ *     x = (uint64(rng) * T) >> 32.  If T == 0 no light can add anything: no shadow ray is traced and no further
+ *     draw is consumed.  Otherwise k is the light with the smallest j such that c_j > x.
+ *   connection: the point draws, q, A, cosS, cosL, d2 and the skip conditions are unchanged;
+ *     g = (((cosS * cosL) * A) * ip_j) / (3.14159274f * d2); Ld, the MIS weight g / fmaf(g, g, 1) and the
+ *     g < +inf condition follow as written above.
+ *   MIS, light hit with cb >= 0: gh = (((cb * cosL) * A) * ip_j) / (3.14159274f * d2) with the hit light's ip_j;
+ *     a hit light with q_j == 0 gives wb = 1 (light sampling could not have produced that point).
+ * Consequences: with equal weights q_j = 4096 and ip_j = float(n) exactly; with one lit light among one the
+ * bytes are the uniform rule's (k = 0, ip = 1); a lit light always has q_j >= 1, so none has selection
+ * probability 0.  A light's true selection probability differs from q_j / T by a relative amount below
+ * T / (q_j * 2^32) (x takes 2^32 values over T cells); the uniform rule's int(u * n) has an error of the same
+ * kind.  The table is rebuilt on the device from the refitted primitive records after every hipptUpdateVertices,
+ * in stream order behind the refit: work enqueued earlier sees the old table, work enqueued later the new one.  A
+ * triangle that a device-memory update dropped for a non-finite coordinate has area 0, hence q_j = 0. */
 /* Records of the chained runs closed since the last call (HIPPT_OPT_CHAIN_AUDIT), as 32-bit words:
  * per run a 16-word header  [0] 0xC4A1D17 [1] run id [2] device [3] batch 0's first frame [4] frames
  * from one batch to the next (-1: one batch) [5] frames per batch [6] band pixels [7] items per batch

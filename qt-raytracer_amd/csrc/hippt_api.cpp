@@ -103,6 +103,7 @@ struct OccKey {
     unsigned topBytes = 0;
     bool ldsScene = false, full = false, spills = false;
     int variant = 0;  // ray-per-lane launches: the QueryMode, or a path kernel's route (kVariantPath ...)
+    bool select = false;  // a light-sampling route's kernel with the selection table (HIPPT_OPT_LIGHT_SELECT)
 };
 // The path kernel's routes as OccKey variants, after the QueryModes: plain paths, light-sampled path
 // queries, the light-sampling render route.
@@ -111,7 +112,7 @@ constexpr int kVariantPath = 8, kVariantLitPath = 9, kVariantLitRender = 10, kVa
 bool same_key(const OccKey &a, const OccKey &b) {
     return a.version == b.version && a.stackDepth == b.stackDepth && a.fmt == b.fmt && a.poolWords == b.poolWords &&
            a.topBytes == b.topBytes && a.ldsScene == b.ldsScene && a.full == b.full && a.spills == b.spills &&
-           a.variant == b.variant;
+           a.variant == b.variant && a.select == b.select;
 }
 
 // Run costs computed on a detached host thread (HIPPT_OPT_ITEM_ORDER automatic).  The thread owns a
@@ -270,6 +271,11 @@ struct Ctx {
     // be in flight when a query grows qLaunch.spill): claim counters, spill area, resident blocks per CU.
     int *lights = nullptr;
     RayLaunch litLaunch;
+    // Light selection (HIPPT_OPT_LIGHT_SELECT): the selection table of the scene's lights (hippt_refit.h
+    // light_table_buffers; a scene buffer), built on the device when the context gets its scene and again
+    // behind every vertex update's refit, so it is current in stream order whatever the option says.
+    // Null for a scene without lights or with more than the table's limit (light_table_fits).
+    unsigned *lightTable = nullptr;
     // Denoiser (hipptDenoise, hippt_denoise.h): one buffer of 80 bytes per pixel (the guide sample's hit
     // records, two colour buffers, the guide), allocated at first use, reused while large enough and
     // freed with the context; the stages' timing events (HIPPT_OPT_DENOISE_TIMING), created on use.
@@ -351,6 +357,8 @@ struct State {
     bool denoiseTiming = false;         // HIPPT_OPT_DENOISE_TIMING
     int lightSampling = 0;              // HIPPT_OPT_LIGHT_SAMPLING_MODE: 0, 1 or HIPPT_LIGHT_SAMPLING_MIS
     int activeLightSampling = 0;        // the mode of the light-sampling route if the last render took it (HIPPT_INFO_LIGHT_SAMPLING)
+    int lightSelect = 0;                // HIPPT_OPT_LIGHT_SELECT: 0 uniform, HIPPT_LIGHT_SELECT_POWER
+    int activeLightSelect = 0;          // as the last light-sampling render applied it (HIPPT_INFO_LIGHT_SELECT)
     long long denoiseNs[hippt::kDenoiseStages] = {};  // HIPPT_INFO_DENOISE_NS + k of the last timed hipptDenoise
     std::vector<unsigned> auditWords;   // closed runs' audit words not yet read (hipptChainAudit)
     std::vector<std::pair<int, uint32_t *>> rngTables;  // per device, built on first use
@@ -605,8 +613,10 @@ void free_scene_buffers(Ctx &c) {
     (void)hipFree(c.nodes4f);
     (void)hipFree(c.padDev);
     (void)hipFree(c.lights);
+    (void)hipFree(c.lightTable);
     c.padDev = nullptr;
     c.lights = nullptr;
+    c.lightTable = nullptr;
     c.nodes = c.tris = c.shade = c.mats = c.nodes4 = c.nodes4q = c.nodes4h = c.nodes4f = nullptr;
     (void)hipFree(c.rfVerts);
     (void)hipFree(c.rfBoxes);
@@ -917,6 +927,19 @@ bool harvest_locked(Ctx &c, const char **err) {
     return true;
 }
 
+// Enqueues a build of c's light selection table from its scene buffers as they are at that point of the stream.
+bool enqueue_light_table(Ctx &c, const char **err) {
+    const SceneHost &sc = S().scene;
+    if (!c.lightTable) return true;
+    hippt::LightTableBuffers t = hippt::light_table_buffers(c.lightTable, int(sc.lights.size()), sc.numTris);
+    t.tris = c.tris;
+    t.shade = c.shade;
+    t.mats = c.mats;
+    t.lights = c.lights;
+    HIP_TRY(hippt::launch_light_table(t, c.stream));
+    return true;
+}
+
 bool ensure_scene(Ctx &c, const char **err) {
     State &s = S();
     if (s.scene.kind != HIPPT_SCENE_MESH || c.sceneVersion == s.scene.version) return true;
@@ -938,6 +961,13 @@ bool ensure_scene(Ctx &c, const char **err) {
     if (!s.scene.lights.empty()) {
         HIP_TRY(hipMalloc(&c.lights, s.scene.lights.size() * sizeof(int)));
         HIP_TRY(hipMemcpy(c.lights, s.scene.lights.data(), s.scene.lights.size() * sizeof(int), hipMemcpyHostToDevice));
+        if (hippt::light_table_fits(s.scene.lights.size())) {
+            const size_t bytes = hippt::light_table_words(s.scene.lights.size(), size_t(s.scene.numTris)) * sizeof(unsigned);
+            HIP_TRY(hipMalloc(&c.lightTable, bytes));
+            // (ip of the primitives that are no lights: 0 for good; on the stream, ahead of the build)
+            HIP_TRY(hipMemsetAsync(c.lightTable, 0, bytes, c.stream));
+            if (!enqueue_light_table(c, err)) return false;
+        }
     }
     c.sceneVersion = s.scene.version;
     return true;
@@ -1770,6 +1800,22 @@ int light_sampling_applies() {
     return s.scene.kind == HIPPT_SCENE_MESH && !s.scene.lights.empty() ? s.lightSampling : 0;
 }
 
+// HIPPT_OPT_LIGHT_SELECT as applied: its value where light sampling applies and the scene's lights have a
+// selection table (hippt_refit.h light_table_fits), else 0 (uniform).
+int light_select_applies() {
+    const State &s = S();
+    return light_sampling_applies() && hippt::light_table_fits(s.scene.lights.size()) ? s.lightSelect : 0;
+}
+
+// The table's pointers for a launch of c under the option as applied (nulls: the uniform choice).
+void set_light_select(const Ctx &c, hippt::PathParams &p) {
+    if (!light_select_applies() || !c.lightTable) return;
+    const hippt::LightTableBuffers t =
+        hippt::light_table_buffers(c.lightTable, int(S().scene.lights.size()), S().scene.numTris);
+    p.lightCdf = t.cdf;
+    p.lightIp = t.ipPrim;
+}
+
 // A mesh call's batches on a context: as many frames per batch as the sample scratch budget
 // (HIPPT_OPT_SCRATCH_MB) and the 2^31 work items of a launch hold.
 struct BatchSize {
@@ -1909,6 +1955,7 @@ bool enqueue_mesh(Ctx &c, const CameraF &cam, int firstFrame, int count, int max
     State &s = S();
     if (!ensure_scene(c, err)) return false;
     s.activeLightSampling = 0;
+    s.activeLightSelect = 0;
     if (const int mode = light_sampling_applies(); maxDepth > 0 && mode)
         return enqueue_mesh_lights(c, cam, firstFrame, count, maxDepth, mode, err);
     const unsigned bandPixels = unsigned(c.rows) * unsigned(s.width);
@@ -2190,16 +2237,19 @@ hippt::QueryCam query_cam(const CameraF &cam, int y0, int rowStride, unsigned ba
 // scene's parameters under layout L (query_scene_params): the kernel's resident blocks per CU, the claim
 // counters and, a 4-wide tree, a spill area for every resident lane, set in q.
 bool ensure_ray_launch(Ctx &c, RayLaunch &r, const plan::Layout &L, int variant, hippt::QueryParams &q, const char **err) {
+    const bool select = variant >= kVariantLitPath && light_select_applies() && c.lightTable;
     OccKey occKey;
     occKey.version = S().scene.version, occKey.stackDepth = L.stackDepth, occKey.fmt = L.fmt, occKey.topBytes = L.topBytes;
     occKey.ldsScene = L.ldsScene, occKey.full = q.full != 0;
     occKey.variant = variant;
+    occKey.select = select;
     if (!same_key(r.occKey, occKey)) {
         // (the pointers select the kernel: any non-null scratch the render route's)
         const bool render = variant == kVariantLitRender || variant == kVariantMisRender;
-        const hippt::PathParams pp{q, c.mats, nullptr, nullptr, nullptr, 1, variant >= kVariantLitPath ? c.lights : nullptr, 1,
-                                   variant >= kVariantMisPath ? 2 : 1, render ? reinterpret_cast<float *>(c.stats) : nullptr,
-                                   nullptr};
+        hippt::PathParams pp{q, c.mats, nullptr, nullptr, nullptr, 1, variant >= kVariantLitPath ? c.lights : nullptr, 1,
+                             variant >= kVariantMisPath ? 2 : 1, render ? reinterpret_cast<float *>(c.stats) : nullptr,
+                             nullptr};
+        if (select) set_light_select(c, pp);
         r.blocksPerCu = variant >= kVariantPath ? hippt::path_blocks_per_cu(pp)
                                                 : hippt::query_blocks_per_cu(q, hippt::QueryMode(variant));
         r.occKey = occKey;
@@ -2244,6 +2294,8 @@ bool enqueue_mesh_lights(Ctx &c, const CameraF &cam, int firstFrame, int count, 
     if (!ensure_ray_launch(c, R, L, mode == 2 ? kVariantMisRender : kVariantLitRender, q, err)) return false;
     hippt::PathParams np{q,    c.mats,  nullptr, nullptr, nullptr, maxDepth, c.lights, int(s.scene.lights.size()),
                          mode, nullptr, c.stats};
+    set_light_select(c, np);
+    s.activeLightSelect = np.lightCdf ? light_select_applies() : 0;
     s.activeWidth = L.wide ? 4 : 2;
     s.activeTopBytes = L.topBytes;
     s.activeBlocksPerCu = R.blocksPerCu;
@@ -2288,10 +2340,11 @@ bool query_enqueue(Ctx &c, hippt::QueryParams q, unsigned first, unsigned m, con
     HIP_TRY(hipMemsetAsync(c.qLaunch.ctr, 0, hippt::kQueryCtrBytes, c.stream));
     if (call.path) {
         const int lit = light_sampling_applies();
-        HIP_TRY(hippt::launch_path(hippt::PathParams{q, c.mats, pp.seeds, pp.radiance, pp.segments, call.maxDepth,
-                                                     lit ? c.lights : nullptr, lit ? int(S().scene.lights.size()) : 0, lit,
-                                                     nullptr, nullptr},
-                                   int(blocks), c.stream));
+        hippt::PathParams np{q, c.mats, pp.seeds, pp.radiance, pp.segments, call.maxDepth,
+                             lit ? c.lights : nullptr, lit ? int(S().scene.lights.size()) : 0, lit,
+                             nullptr, nullptr};
+        set_light_select(c, np);
+        HIP_TRY(hippt::launch_path(np, int(blocks), c.stream));
     } else {
         HIP_TRY(hippt::launch_query(q, int(blocks), call.mode, c.stream));
     }
@@ -2910,6 +2963,8 @@ bool update_vertices_locked(const float *verts, int numTris, int flags, const ch
         r.numNodes2 = sc.numNodes;
         r.numNodes4 = sc.numNodes4;
         HIP_TRY(hippt::launch_refit(r, sc.plan.level2, sc.plan.level4, seedBits, c.stream));
+        // the light selection table follows the new areas, behind the refit on the same stream
+        if (!enqueue_light_table(c, err)) return false;
         c.rfUpdated = true;
     }
     return true;
@@ -2937,6 +2992,10 @@ extern "C" long long hipptSceneDownload(int what, void *dst, long long bytes, co
             case HIPPT_SCENE_NODES4: need = sc.nodes4.size(); break;
             case HIPPT_SCENE_PRIMS: need = sc.tris.size(); break;
             case HIPPT_SCENE_SHADE: need = sc.shade.size(); break;
+            case HIPPT_SCENE_LIGHTS:  // one record of 4 words per light; none without a table
+                need = hippt::light_table_fits(sc.lights.size()) ? sc.lights.size() : 0;
+                if (!need) return 0;
+                break;
             default: return bad("scene download: unknown buffer");
             }
             need *= sizeof(float4);
@@ -2949,7 +3008,13 @@ extern "C" long long hipptSceneDownload(int what, void *dst, long long bytes, co
             const float4 *src = what == HIPPT_SCENE_NODES2   ? c.nodes
                                 : what == HIPPT_SCENE_NODES4 ? c.nodes4
                                 : what == HIPPT_SCENE_PRIMS  ? c.tris
-                                                             : c.shade;
+                                : what == HIPPT_SCENE_SHADE  ? c.shade
+                                                             : nullptr;
+            if (what == HIPPT_SCENE_LIGHTS) {  // (built with the scene and behind every update: current here)
+                if (!c.lightTable) return bad("scene download: no light table");
+                src = reinterpret_cast<const float4 *>(
+                    hippt::light_table_buffers(c.lightTable, int(sc.lights.size()), sc.numTris).records);
+            }
             if (hipSetDevice(c.device) != hipSuccess ||
                 hipMemcpyAsync(dst, src, need, hipMemcpyDeviceToHost, c.stream) != hipSuccess ||
                 hipStreamSynchronize(c.stream) != hipSuccess) {
@@ -3445,6 +3510,10 @@ bool set_option_locked(int key, long long value) {
         if (value != 0 && value != 1 && value != HIPPT_LIGHT_SAMPLING_MIS) return false;
         s.lightSampling = int(value);
         return true;
+    case HIPPT_OPT_LIGHT_SELECT:
+        if (value != 0 && value != HIPPT_LIGHT_SELECT_POWER) return false;
+        s.lightSelect = int(value);
+        return true;
     default: return false;
     }
 }
@@ -3508,6 +3577,8 @@ long long get_option_locked(int key) {
     case HIPPT_OPT_LIGHT_SAMPLING_MODE: return s.lightSampling;
     case HIPPT_INFO_LIGHTS: return s.scene.kind == HIPPT_SCENE_MESH ? (long long)s.scene.lights.size() : 0;
     case HIPPT_INFO_LIGHT_SAMPLING: return s.activeLightSampling;
+    case HIPPT_OPT_LIGHT_SELECT: return s.lightSelect;
+    case HIPPT_INFO_LIGHT_SELECT: return s.activeLightSelect;
     case HIPPT_INFO_SKY_RECT_PIXELS: return s.activeSkyPixels;
     case HIPPT_INFO_UPDATE_DROPPED:
         // the last update's count, from the first context that ran it (every context counts the same)

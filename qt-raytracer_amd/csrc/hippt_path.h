@@ -20,6 +20,10 @@ namespace hippt {
 // scratch[3 i .. 3 i + 2] (the combine's layout) and the segments and samples are added to `stats`
 // (hippt_device.h kStatWords).  lightMode 2 (HIPPT_LIGHT_SAMPLING_MIS) weights the connection
 // and the light met after a Lambertian scatter by the power heuristic; the routes are the same.
+// Light selection (HIPPT_OPT_LIGHT_SELECT): with `lightCdf` (light sampling only) the connection
+// picks its light by the device-built table (hippt_refit.h LightTableBuffers: cdf and ipPrim) in place of the
+// uniform choice, and ip of the light replaces float(numLights); null: uniform, the bytes of before, from the
+// kernels of before (the choice is a compile-time flag of the kernel, as MIS is).
 struct PathParams {
     QueryParams q;
     const float4 *mats;     // MeshParams::mats
@@ -32,6 +36,8 @@ struct PathParams {
     int lightMode;  // with `lights`: 1 plain, 2 with MIS (HIPPT_LIGHT_SAMPLING_MIS)
     float *scratch;
     unsigned long long *stats;
+    const unsigned *lightCdf = nullptr;  // c_j of the numLights lights, or null (uniform)
+    const float *lightIp = nullptr;      // with lightCdf: ip by primitive in leaf order
 };
 
 hipError_t launch_path(const PathParams &p, int blocks, hipStream_t s);

@@ -65,17 +65,36 @@ __device__ __forceinline__ float light_area(const float4 *prims, int k, bool sph
 }
 
 // One connection from the Lambertian vertex p (faced normal n, throughput t* after the scatter): picks a
-// light and a point on it from `rng`, and returns whether a shadow ray is to be traced; then (wx, wy, wz)
+// light (uniformly over the list, or under SELECT, HIPPT_LIGHT_SELECT_POWER, by the selection table `cdf`: one
+// draw either way) and a point on it from `rng`, and returns whether a shadow ray is to be traced; then (wx, wy, wz)
 // is its unit direction, (l0, l1, l2) what the light adds if the ray's closest hit is primitive `lk`
 // (leaf order).  The draws are consumed either way.  MIS: the power heuristic's weight against the scatter
 // sample, 1 / (1 + g^2), is in (l0, l1, l2), and a g that is not below +inf makes no shadow ray.
-template <bool MIS>
-__device__ __forceinline__ bool light_connect(const int *lights, int numLights, const float4 *shade, const float4 *prims,
-                                              const float4 *mats, float px, float py, float pz, float nx, float ny,
+template <bool MIS, bool SELECT>
+__device__ __forceinline__ bool light_connect(const int *lights, int numLights, const unsigned *cdf, const float *ipPrim,
+                                              const float4 *shade, const float4 *prims, const float4 *mats, float px,
+                                              float py, float pz, float nx, float ny,
                                               float nz, float tr, float tg, float tb, uint32_t &rng, unsigned *pc,
                                               float &wx, float &wy, float &wz, float &l0, float &l1, float &l2, int &lk) {
-    const float nl = float(numLights);
-    lk = lights[min(int(rand01(rng) * nl), numLights - 1)];
+    float nl = float(numLights);
+    if (SELECT) {  // by the selection table: the smallest j with c_j > x, x uniform below T
+        rng = hash32(rng);
+        const unsigned total = cdf[numLights - 1];
+        if (total == 0u) return false;  // no light can add anything: no further draw
+        const unsigned x = __umulhi(rng, total);
+        int lo = 0, hi = numLights - 1;  // c_hi = T > x
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (cdf[mid] > x)
+                hi = mid;
+            else
+                lo = mid + 1;
+        }
+        lk = lights[lo];
+        nl = ipPrim[lk];
+    } else {
+        lk = lights[min(int(rand01(rng) * nl), numLights - 1)];
+    }
     const float4 sh = shade[lk];
     const float4 A = prims[3 * lk], B = prims[3 * lk + 1];
     const int mw = __float_as_int(sh.w);
@@ -125,8 +144,9 @@ __device__ __forceinline__ bool light_connect(const int *lights, int numLights, 
 // MIS: the weight wb of the emission of light `prim`, met at t on the segment r that a Lambertian scatter
 // with cosine cb to its normal started: the scatter's density against light sampling's at that point,
 // squared (the power heuristic); 1 where light sampling could not have produced the point.
+template <bool SELECT>
 __device__ __forceinline__ float light_hit_weight(const Ray &r, float t, int prim, const float4 *shade, const float4 *prims,
-                                                  float cb, int numLights) {
+                                                  float cb, int numLights, const float *ipPrim) {
     const float4 sh = shade[prim];
     const bool sphere = (__float_as_int(sh.w) & kShadeSphere) != 0;
     const float dd = fdot(r.dx, r.dy, r.dz, r.dx, r.dy, r.dz);
@@ -142,9 +162,11 @@ __device__ __forceinline__ float light_hit_weight(const Ray &r, float t, int pri
     }
     const float cosL = fabsf(fdot(nx, ny, nz, r.dx * inv, r.dy * inv, r.dz * inv));
     const float area = light_area(prims, prim, sphere);
+    // the inverse of the light's selection probability: the count, or the table's ip (0: never selected)
+    const float nl = SELECT ? ipPrim[prim] : float(numLights);
     float wb = 1.0f;
-    if (cb > 0.0f && cosL > 0.0f && d2 > 0.0f && area > 0.0f) {
-        const float gh = (((cb * cosL) * area) * float(numLights)) / (3.14159274f * d2);
+    if (cb > 0.0f && cosL > 0.0f && d2 > 0.0f && area > 0.0f && (!SELECT || nl > 0.0f)) {
+        const float gh = (((cb * cosL) * area) * nl) / (3.14159274f * d2);
         const float s = gh * gh;
         if (s < INFINITY) wb = s / fmaf(gh, gh, 1.0f);
     }
@@ -163,11 +185,16 @@ __device__ __forceinline__ float light_hit_weight(const Ray &r, float t, int pri
 // MIS (with NEE): HIPPT_LIGHT_SAMPLING_MIS (tests/mis_ref.py is the statement of record).  In
 // place of `spec` the path carries cb, the cosine of the last scatter if it was Lambertian, else -1; the
 // connection and a light met after a Lambertian scatter are each weighted against the other technique.
-template <bool LDS_SCENE, bool FULL, bool WIDE, bool NEE, bool CAMERA, bool MIS>
+// SELECT (with NEE): HIPPT_LIGHT_SELECT_POWER (tests/select_ref.py is the statement of record): the
+// connection's light comes from the selection table (PathParams::lightCdf) and the table's ip stands where
+// float(numLights) stood.  A flag and not a branch on the pointer: the branch cost every NEE kernel 1 to 4 VGPRs,
+// and three of the 2-wide query kernels an occupancy step, with the option off.
+template <bool LDS_SCENE, bool FULL, bool WIDE, bool NEE, bool CAMERA, bool MIS, bool SELECT>
 __global__ __launch_bounds__(kMeshBlock) void path_kernel(PathParams P) {
     static_assert(FULL || !NEE, "light sampling has general kernels only");
     static_assert(NEE || !CAMERA, "the camera start belongs to the light-sampling render route");
     static_assert(NEE || !MIS, "the weights belong to light sampling");
+    static_assert(NEE || !SELECT, "the light choice belongs to light sampling");
     const QueryParams &Q = P.q;
     const Staged sc = stage_scene<LDS_SCENE, WIDE>(Q.nodes, Q.tris, Q.numNodes, Q.numTris, Q.stackDepth, Q.topBytes);
     const SpillArea S = lane_spill(Q.spill, Q.spillCap, Q.stackCap);
@@ -232,7 +259,7 @@ __global__ __launch_bounds__(kMeshBlock) void path_kernel(PathParams P) {
                     shadow = false;
                 }
                 // begin_query_ray, with the mark of hipptTraceRays' invalid rays (no segment, (0, 0, 0, 0))
-                // in its branch: set after it, the mark costs path_kernel<false, false, false, false, false, false>
+                // in its branch: set after it, the mark costs path_kernel<false, false, false, false, false, false, false>
                 // 2 VGPRs
                 begin(T);
                 T.bestO = -1;  // a hit at exactly t == tmax loses the tie on the id: tmax is exclusive
@@ -292,7 +319,8 @@ __global__ __launch_bounds__(kMeshBlock) void path_kernel(PathParams P) {
                     // scatter sample's weight
                     if (MIS) {
                         if (!(cb < 0.0f)) {
-                            const float wb = light_hit_weight(r, T.bestT, T.bestI, Q.shade, sc.tris, cb, P.numLights);
+                            const float wb = light_hit_weight<SELECT>(r, T.bestT, T.bestI, Q.shade, sc.tris, cb,
+                                                                      P.numLights, P.lightIp);
                             L0 *= wb;
                             L1 *= wb;
                             L2 *= wb;
@@ -313,8 +341,10 @@ __global__ __launch_bounds__(kMeshBlock) void path_kernel(PathParams P) {
                                           : fdot(nx, ny, nz, r.dx, r.dy, r.dz) *
                                                 rsqrt_rn(fdot(r.dx, r.dy, r.dz, r.dx, r.dy, r.dz));
                             float wx, wy, wz;
-                            if (!spec && light_connect<MIS>(P.lights, P.numLights, Q.shade, sc.tris, P.mats, r.ox, r.oy, r.oz,
-                                                            nx, ny, nz, tr, tg, tb, rng, pc, wx, wy, wz, ld0, ld1, ld2, lk)) {
+                            if (!spec &&
+                                light_connect<MIS, SELECT>(P.lights, P.numLights, P.lightCdf, P.lightIp, Q.shade, sc.tris,
+                                                           P.mats, r.ox, r.oy, r.oz, nx, ny, nz, tr, tg, tb, rng, pc, wx, wy,
+                                                           wz, ld0, ld1, ld2, lk)) {
                                 shadow = true;
                                 sdx = r.dx, sdy = r.dy, sdz = r.dz;
                                 r.dx = wx, r.dy = wy, r.dz = wz;
@@ -368,12 +398,21 @@ PathFn path_fn(const PathParams &p) {
     return for_scene_layout(q, [&p](auto lds, auto full, auto wide) -> PathFn {
         constexpr bool L = decltype(lds)::value, F = decltype(full)::value, W = decltype(wide)::value;
         if constexpr (F) {
+            if (p.lights && p.lightCdf) {
+                if (p.lightMode == 2)
+                    return p.scratch ? path_kernel<L, F, W, true, true, true, true>
+                                     : path_kernel<L, F, W, true, false, true, true>;
+                return p.scratch ? path_kernel<L, F, W, true, true, false, true>
+                                 : path_kernel<L, F, W, true, false, false, true>;
+            }
             if (p.lights && p.lightMode == 2)
-                return p.scratch ? path_kernel<L, F, W, true, true, true> : path_kernel<L, F, W, true, false, true>;
+                return p.scratch ? path_kernel<L, F, W, true, true, true, false>
+                                 : path_kernel<L, F, W, true, false, true, false>;
             if (p.lights)
-                return p.scratch ? path_kernel<L, F, W, true, true, false> : path_kernel<L, F, W, true, false, false>;
+                return p.scratch ? path_kernel<L, F, W, true, true, false, false>
+                                 : path_kernel<L, F, W, true, false, false, false>;
         }
-        return path_kernel<L, F, W, false, false, false>;
+        return path_kernel<L, F, W, false, false, false, false>;
     });
 }
 
@@ -399,6 +438,7 @@ hipError_t launch_path(const PathParams &p, int blocks, hipStream_t s) {
     if (!q.shade || !p.mats || p.maxDepth < 1) return hipErrorInvalidValue;
     if (p.lights ? (!q.full || p.numLights < 1 || p.lightMode < 1 || p.lightMode > 2) : p.scratch != nullptr)
         return hipErrorInvalidValue;
+    if (p.lightCdf ? (!p.lights || !p.lightIp) : p.lightIp != nullptr) return hipErrorInvalidValue;
     // a render batch's counters; a query's own pointers: rays and records are read and stored whole
     if (p.scratch ? !p.stats
                   : (!q.rays || !p.seeds || !p.radiance || reinterpret_cast<uintptr_t>(q.rays) % 16 ||

@@ -38,4 +38,40 @@ struct RefitBuffers {
 hipError_t launch_refit(const RefitBuffers &b, const std::vector<int> &level2, const std::vector<int> &level4,
                         unsigned seedBits, hipStream_t s);
 
+// ---- the light selection table (include/hippt.h HIPPT_OPT_LIGHT_SELECT) ----------------
+// Most lights a table is built for: q_j <= 4096 = 2^12, so the total T of 2^20 - 1 lights stays below 2^32.
+// Above it there is no table and the light choice stays uniform.
+constexpr int kLightSelectMax = (1 << 20) - 1;
+// Whether a scene with n lights has a table: the one place that applies the limit.
+constexpr bool light_table_fits(size_t n) { return n >= 1 && n <= size_t(kLightSelectMax); }
+
+// The table's words for n lights and p primitives, as launch_light_table lays them out in one allocation.
+constexpr size_t light_table_words(size_t n, size_t p) {
+    return n + 4 * n + p + n + (n + kRefitBlock - 1) / kRefitBlock + 2;
+}
+
+// Every pointer is memory of the launch's device.  The scene buffers are a context's; the rest is the
+// table's own (one allocation of light_table_words words, see light_table_buffers).
+struct LightTableBuffers {
+    const float4 *tris;   // primitive records in leaf order (RefitBuffers::tris)
+    const float4 *shade;  // normal + material word per primitive
+    const float4 *mats;   // MeshParams::mats: the emission in [2 m].xyz
+    const int *lights;    // leaf-order indices of the emissive primitives by ascending id
+    unsigned *cdf;        // numLights: c_j, dense for the search (T = cdf[numLights - 1])
+    unsigned *records;    // numLights * 4: primitive id, q_j, c_j, bits of ip_j (hipptSceneDownload)
+    float *ipPrim;        // numPrims: ip by primitive in leaf order; the build writes the lights' entries,
+                          // the others are zeroed once by the owner
+    float *weights;       // numLights: W_j (between the passes)
+    unsigned *blockSums;  // one per block of kRefitBlock lights: the block's sum of q, then its offset
+    unsigned *words;      // [0] bits of Wmax, [1] T
+    int numLights, numPrims;
+};
+
+// The pointers of a table in `base` (light_table_words(n, p) words).
+LightTableBuffers light_table_buffers(unsigned *base, int numLights, int numPrims);
+
+// Enqueues one build on `s`: Wmax zeroed, then four launches (weights and Wmax, q and the blocks' scans,
+// one block over the blocks' sums, offsets + ip + scatter).  light_table_fits(numLights).
+hipError_t launch_light_table(const LightTableBuffers &b, hipStream_t s);
+
 }  // namespace hippt

@@ -11,9 +11,12 @@
 //                 of its leaf's primitive boxes or of its child node's unpadded slot boxes (written
 //                 by the previous launch), kept on the side, and the node's box = that moved out once
 //                 by the pad of the update's largest |coordinate| (bvh_builder.h refit_bvh)
+// and, behind them for a scene with lights, the four launches that rebuild the light selection table
+// from the refitted primitive records (HIPPT_OPT_LIGHT_SELECT; below).
 #include "hippt_refit.h"
 
 #include "bvh_builder.h"
+#include "hippt_device.h"
 
 namespace hippt {
 namespace {
@@ -164,7 +167,148 @@ void launch_levels(uint32_t *nodes, const int *list, const std::vector<int> &lev
     }
 }
 
+// ---- the light selection table (hippt_refit.h; the rule: include/hippt.h, tests/select_ref.py) ----
+// Four launches in stream order over the light list, a lane per light; the hand-off between them is the
+// kernel boundary (no block waits for another).  Everything summed is an integer, and the one maximum is
+// an integer maximum of non-negative floats' bits, so no word depends on the order of arrival.
+
+// Inclusive scan of v over the block's kRefitBlock threads, all of which call it; `total`: the block's sum.
+__device__ inline unsigned block_scan(unsigned v, unsigned *waveSums, unsigned &total) {
+    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    for (unsigned d = 1; d < 64; d <<= 1) {
+        const unsigned o = unsigned(__shfl_up(int(v), d));
+        if (lane >= d) v += o;
+    }
+    if (lane == 63u) waveSums[wave] = v;
+    __syncthreads();
+    total = 0;
+    for (unsigned w = 0; w < unsigned(kRefitBlock) / 64u; ++w) {
+        const unsigned s = waveSums[w];
+        if (w < wave) v += s;
+        total += s;
+    }
+    __syncthreads();  // (the sums may be written again)
+    return v;
+}
+
+// W_j = A_j * y_j of a lit light (A_j > 0 and y_j > 0), -1 for an unlit one, and Wmax.
+__global__ __launch_bounds__(kRefitBlock) void light_weights(LightTableBuffers B) {
+    const int j = int(blockIdx.x) * kRefitBlock + int(threadIdx.x);
+    unsigned maxBits = 0u;
+    if (j < B.numLights) {
+        const int k = B.lights[j];
+        float W = -1.0f;
+        if (unsigned(k) < unsigned(B.numPrims)) {
+            const float4 A = B.tris[3 * size_t(k)];
+            const int mw = i_of(B.shade[k].w);
+            float area;
+            if (mw & kShadeSphere) {
+                area = (12.566371f * A.w) * A.w;
+            } else {  // the path kernel's light_area
+                const float4 E = B.tris[3 * size_t(k) + 1];
+                const float e1x = A.w, e1y = E.x, e1z = E.y;
+                const float e2x = E.z, e2y = E.w, e2z = B.tris[3 * size_t(k) + 2].x;
+                const float cx = fmaf(e1y, e2z, -(e1z * e2y)), cy = fmaf(e1z, e2x, -(e1x * e2z)),
+                            cz = fmaf(e1x, e2y, -(e1y * e2x));
+                area = 0.5f * sqrtf(fmaf(cx, cx, fmaf(cy, cy, cz * cz)));
+            }
+            const float4 le = B.mats[2 * size_t(mw & ~kShadeSphere)];
+            const float y = (le.x + le.y) + le.z;
+            if (area > 0.0f && y > 0.0f) {
+                W = area * y;
+                maxBits = __float_as_uint(W);
+            }
+        }
+        B.weights[j] = W;
+    }
+    // one atomic per wave
+    for (int d = 32; d > 0; d >>= 1) maxBits = max(maxBits, unsigned(__shfl_xor(int(maxBits), d)));
+    if ((threadIdx.x & 63u) == 0u && maxBits) atomicMax(&B.words[0], maxBits);
+}
+
+// q_j, its inclusive sum within the block, and the block's sum.
+__global__ __launch_bounds__(kRefitBlock) void light_scan_blocks(LightTableBuffers B) {
+    __shared__ unsigned waveSums[kRefitBlock / 64];
+    const int j = int(blockIdx.x) * kRefitBlock + int(threadIdx.x);
+    unsigned q = 0u;
+    if (j < B.numLights) {
+        const float W = B.weights[j], Wmax = f_of(B.words[0]);
+        if (W >= 0.0f) {
+            const bool flat = !(Wmax > 0.0f && Wmax < INFINITY);
+            q = flat ? 1u : unsigned(min(4096, max(1, int((W / Wmax) * 4096.0f))));
+        }
+    }
+    unsigned total;
+    const unsigned c = block_scan(q, waveSums, total);
+    if (j < B.numLights) {
+        B.cdf[j] = c;
+        B.records[4 * size_t(j) + 1] = q;
+    }
+    if (threadIdx.x == 0u) B.blockSums[blockIdx.x] = total;
+}
+
+// One block: the blocks' sums become the blocks' offsets (their exclusive sums), and T.
+__global__ __launch_bounds__(kRefitBlock) void light_scan_sums(LightTableBuffers B) {
+    __shared__ unsigned waveSums[kRefitBlock / 64];
+    const int blocks = (B.numLights + kRefitBlock - 1) / kRefitBlock;
+    const int per = (blocks + kRefitBlock - 1) / kRefitBlock;
+    const int first = min(int(threadIdx.x) * per, blocks), last = min(first + per, blocks);
+    unsigned sum = 0u;
+    for (int i = first; i < last; ++i) sum += B.blockSums[i];
+    unsigned total;
+    unsigned at = block_scan(sum, waveSums, total) - sum;
+    for (int i = first; i < last; ++i) {
+        const unsigned s = B.blockSums[i];
+        B.blockSums[i] = at;
+        at += s;
+    }
+    if (threadIdx.x == 0u) B.words[1] = total;
+}
+
+// c_j with its block's offset, ip_j, the record, and ip by primitive.
+__global__ __launch_bounds__(kRefitBlock) void light_finish(LightTableBuffers B) {
+    const int j = int(blockIdx.x) * kRefitBlock + int(threadIdx.x);
+    if (j >= B.numLights) return;
+    const unsigned q = B.records[4 * size_t(j) + 1];
+    const unsigned c = B.cdf[j] + B.blockSums[blockIdx.x];
+    const float ip = q > 0u ? float(B.words[1]) / float(q) : 0.0f;
+    const int k = B.lights[j];
+    const bool have = unsigned(k) < unsigned(B.numPrims);
+    B.cdf[j] = c;
+    B.records[4 * size_t(j)] = have ? unsigned(i_of(B.tris[3 * size_t(k) + 2].y)) : ~0u;
+    B.records[4 * size_t(j) + 2] = c;
+    B.records[4 * size_t(j) + 3] = __float_as_uint(ip);
+    if (have) B.ipPrim[k] = ip;
+}
+
 }  // namespace
+
+LightTableBuffers light_table_buffers(unsigned *base, int numLights, int numPrims) {
+    const size_t n = size_t(numLights), p = size_t(numPrims);
+    LightTableBuffers b{};
+    b.cdf = base;
+    b.records = b.cdf + n;
+    b.ipPrim = reinterpret_cast<float *>(b.records + 4 * n);
+    b.weights = b.ipPrim + p;
+    b.blockSums = reinterpret_cast<unsigned *>(b.weights + n);
+    b.words = b.blockSums + (n + kRefitBlock - 1) / kRefitBlock;
+    b.numLights = numLights;
+    b.numPrims = numPrims;
+    return b;
+}
+
+hipError_t launch_light_table(const LightTableBuffers &b, hipStream_t s) {
+    if (b.numLights <= 0 || !light_table_fits(size_t(b.numLights)) || b.numPrims <= 0) return hipErrorInvalidValue;
+    if (!b.tris || !b.shade || !b.mats || !b.lights || !b.cdf) return hipErrorInvalidValue;
+    const hipError_t e = hipMemsetAsync(b.words, 0, 2 * sizeof(unsigned), s);
+    if (e != hipSuccess) return e;
+    const dim3 grid((b.numLights + kRefitBlock - 1) / kRefitBlock), block(kRefitBlock);
+    hipLaunchKernelGGL(light_weights, grid, block, 0, s, b);
+    hipLaunchKernelGGL(light_scan_blocks, grid, block, 0, s, b);
+    hipLaunchKernelGGL(light_scan_sums, dim3(1), block, 0, s, b);
+    hipLaunchKernelGGL(light_finish, grid, block, 0, s, b);
+    return hipGetLastError();
+}
 
 hipError_t launch_refit(const RefitBuffers &b, const std::vector<int> &level2, const std::vector<int> &level4,
                         unsigned seedBits, hipStream_t s) {

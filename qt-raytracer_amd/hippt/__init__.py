@@ -66,6 +66,8 @@ OPT_DENOISE_TIMING = 36
 OPT_LIGHT_SAMPLING = 37  # next-event estimation at Lambertian vertices (include/hippt.h; 0 default)
 OPT_LIGHT_SAMPLING_MODE = 38  # the same word with all its values: 0, 1 and LIGHT_SAMPLING_MIS (37 takes 0 and 1 only)
 LIGHT_SAMPLING_MIS = 2  # light sampling with MIS (the power heuristic with the scatter sample)
+OPT_LIGHT_SELECT = 39  # how a connection picks its light: 0 (default) uniformly, LIGHT_SELECT_POWER by area x emission
+LIGHT_SELECT_POWER = 1
 OPT_PIXEL_FORMAT = 25
 PIXEL_ARGB = 0
 PIXEL_RGBA8 = 1
@@ -78,6 +80,7 @@ INFO_RENDER_PAD = 105
 INFO_SKY_RECT_PIXELS = 106
 INFO_LIGHTS = 107  # emissive primitives in the uploaded scene
 INFO_LIGHT_SAMPLING = 108  # OPT_LIGHT_SAMPLING_MODE's value (1 or 2) if the last render took the light-sampling route
+INFO_LIGHT_SELECT = 109  # OPT_LIGHT_SELECT's value if the last render took the light-sampling route and applied it
 INFO_DENOISE_NS = 200
 RAYS_DEVICE = 1
 HIT_SPHERE = 1 << 30
@@ -91,6 +94,7 @@ SCENE_NODES2 = 0
 SCENE_NODES4 = 1
 SCENE_PRIMS = 2
 SCENE_SHADE = 3
+SCENE_LIGHTS = 4  # the light selection table: (prim, q, c, bits of ip) per light
 
 # Every symbol include/hippt.h declares (checked by tests/test_abi_cpu.py).
 EXPORTS = (
@@ -377,13 +381,15 @@ def _update_verts(verts):
     return verts, False
 
 
-_SCENE_WORDS = {SCENE_NODES2: 16, SCENE_NODES4: 32, SCENE_PRIMS: 12, SCENE_SHADE: 4}
+_SCENE_WORDS = {SCENE_NODES2: 16, SCENE_NODES4: 32, SCENE_PRIMS: 12, SCENE_SHADE: 4, SCENE_LIGHTS: 4}
+LIGHT_TABLE_DTYPE = np.dtype([("prim", "<i4"), ("q", "<u4"), ("c", "<u4"), ("ip", "<f4")])
 
 
 def scene_download(what: int) -> np.ndarray:
     """hipptSceneDownload: context 0's device copy of the 2-wide nodes (N, 16), the 4-wide float nodes
     (M, 32; interior child codes are byte offsets), the primitive records (P, 12; leaf order, id in
-    word 9) or the shading records (P, 4), as uint32, after the queued work."""
+    word 9), the shading records (P, 4) or the light selection table (L, 4; PathTracer.lightTable names its
+    words), as uint32, after the queued work."""
     if what not in _SCENE_WORDS:
         raise HipptError(f"unknown scene buffer {what}")
     lib = load_library()
@@ -651,6 +657,13 @@ class PathTracer:
             ok = self._lib.hipptUpdateVertices(v.ctypes.data, int(v.shape[0]), 0, ctypes.byref(e))
         if not ok:
             raise HipptError(_err(e, "vertex update failed"))
+
+    def lightTable(self) -> np.ndarray:  # noqa: N802
+        """The light selection table as the device built it (include/hippt.h HIPPT_OPT_LIGHT_SELECT), after the
+        queued work: a structured array with one entry per light in ascending primitive id: `prim` the id as
+        uploaded, `q` the light's integer weight, `c` the inclusive sum of q, `ip` the inverse of its selection
+        probability (float32; 0 for a light that is never selected).  Empty for a scene without lights."""
+        return scene_download(SCENE_LIGHTS).reshape(-1).view(LIGHT_TABLE_DTYPE)
 
     def updateDropped(self) -> int:  # noqa: N802
         """Triangles the last device-memory update dropped for a non-finite coordinate (synchronises)."""

@@ -305,6 +305,47 @@ def cornell_lit(base: str = "cornell_mixed", sphere: bool = True) -> Scene:
     return sc
 
 
+def cornell_lamps(base: str = "cornell34", small: int = 240, sphere: bool = True, seed: int = 3) -> Scene:
+    """`cornell_lit(base, sphere=False)`, lamp unchanged, plus `small` small dim emissive triangles (legs of 4 to
+    20 units, three dim emissions in turn) one unit inside the floor, the back wall and the side walls and,
+    with `sphere`, one small dim emissive sphere on the floor: the scene on which the light choice matters
+    (include/hippt.h HIPPT_OPT_LIGHT_SELECT).  Uniformly chosen, the lamp gets two connections in `small` + 3;
+    chosen by power, nearly all of them.  Not in SCENES, as cornell_lit."""
+    sc = cornell_lit(base, sphere=False)
+    rng = np.random.default_rng(seed)
+    mats = sc.materials()
+    k = len(mats)
+    dim = [(0.5, 0.4, 0.3), (0.2, 0.5, 0.3), (0.3, 0.3, 0.6)]
+    walls = ((1, 1.0), (2, 554.0), (0, 1.0), (0, 554.0))  # (fixed axis, its coordinate)
+    tris = []
+    for i in range(small):
+        axis, at = walls[i % len(walls)]
+        u, v = [a for a in range(3) if a != axis]
+        p = np.zeros(3)
+        p[axis] = at
+        p[u], p[v] = rng.uniform(20.0, 515.0, 2)
+        side = rng.uniform(4.0, 20.0)
+        a, b = p.copy(), p.copy()
+        a[u] += side
+        b[v] += side
+        tris.append(tuple(p) + tuple(a) + tuple(b))
+    sc.name = f"{base}_lamps"
+    sc.verts = np.ascontiguousarray(
+        np.concatenate([sc.verts, np.asarray(tris, dtype=np.float64).reshape(-1, 9).astype(np.float32)], axis=0))
+    sc.tri_mat = np.concatenate([sc.tri_mat, k + np.arange(small, dtype=np.int32) % len(dim)]).astype(np.int32)
+    new = list(dim)
+    if sphere:
+        sc.spheres = np.concatenate([np.asarray(sc.spheres, np.float32).reshape(-1, 4),
+                                     np.asarray([(470.0, 12.0, 90.0, 12.0)], np.float32)], axis=0)
+        sc.sph_mat = np.concatenate([np.asarray(sc.sph_mat, np.int32), np.asarray([k + len(dim)], np.int32)])
+        new.append((1.0, 0.8, 0.6))
+    sc.albedo = np.concatenate([mats["albedo"], np.asarray(new, np.float32)], axis=0)
+    sc.mat_kind = np.concatenate([mats["kind"], np.full(len(new), MAT_EMISSIVE, np.int32)])
+    sc.fuzz = np.concatenate([mats["fuzz"], np.zeros(len(new), np.float32)])
+    sc.ir = np.concatenate([mats["ir"], np.ones(len(new), np.float32)])
+    return sc
+
+
 SCENES = {"cornell34": cornell34, "blob70k": blob70k, "random_scene": random_scene, "cornell_mixed": cornell_mixed}
 
 

@@ -6,6 +6,7 @@
 //                [--emit NAME=r,g,b[;NAME=r,g,b...]] [--width W] [--height H] [--spp N] [--depth D] [--per-frame] [--present]
 //                [--out FILE] [--ppm FILE.ppm] [--pick X,Y] [--denoise PASSES]
 //                [--radiance-in FILE|camera --radiance-out FILE] [--light-sampling] [--mis]
+//                [--light-select power|uniform]
 //
 // --backend cuda (default): HipPathTracer, the CudaPathTracer interface.  Without --mesh: the
 // reference kernel's built-in 4-sphere scene, one renderFrame per frame (the CUDA backend's
@@ -16,6 +17,8 @@
 // --light-sampling: HIPPT_OPT_LIGHT_SAMPLING 1 (next-event estimation towards those lights) for the render
 // and --radiance-out.  --mis: HIPPT_OPT_LIGHT_SAMPLING_MODE HIPPT_LIGHT_SAMPLING_MIS (light sampling with the scatter sample weighed in by
 // the power heuristic); it implies --light-sampling.
+// --light-select power: HIPPT_OPT_LIGHT_SELECT HIPPT_LIGHT_SELECT_POWER (a connection picks its light in proportion
+// to area x emission); uniform (default): over the list.  Meaningful with --light-sampling or --mis; it implies neither.
 // --backend vulkan: HipVulkanPathTracer, one renderFrame(depth) per frame (the app's "vulkan"
 // branch, RayTracerFboItem.cpp:576-600).  --backend gl: HipGpuPathTracer, initialize + resize,
 // then renderFrame(N, depth) once (or per frame with --per-frame), as the GL branch calls it.
@@ -51,7 +54,8 @@ int usage() {
                  "                    [--emit NAME=r,g,b[;...]]\n"
                  "                    [--height H] [--spp N] [--depth D] [--per-frame] [--present] [--out FILE]\n"
                  "                    [--ppm FILE.ppm] [--pick X,Y] [--update-mesh FILE] [--denoise PASSES]\n"
-                 "                    [--radiance-in FILE|camera --radiance-out FILE] [--light-sampling] [--mis]\n");
+                 "                    [--radiance-in FILE|camera --radiance-out FILE] [--light-sampling] [--mis]\n"
+                 "                    [--light-select power|uniform]\n");
     return 2;
 }
 
@@ -73,6 +77,7 @@ std::vector<float> parse_floats(const std::string &s) {
 
 int main(int argc, char **argv) {
     std::string mesh, out, ppm, albedoArg, emitArg, pickArg, updateMesh, radianceIn, radianceOut, backend = "cuda";
+    std::string lightSelect = "uniform";
     int width = 320, height = 180, spp = 16, depth = 8, denoise = -1;
     bool perFrame = false, present = false, lightSampling = false, mis = false;
     for (int i = 1; i < argc; ++i) {
@@ -99,10 +104,13 @@ int main(int argc, char **argv) {
         else if (a == "--denoise") denoise = std::atoi(v);
         else if (a == "--radiance-in") radianceIn = v;
         else if (a == "--radiance-out") radianceOut = v;
+        else if (a == "--light-select") lightSelect = v;
         else return usage();
     }
     if (backend != "cuda" && backend != "vulkan" && backend != "gl") return usage();
+    if (lightSelect != "power" && lightSelect != "uniform") return usage();
     HipPathTracer tracer;
+    hipptSetOption(HIPPT_OPT_LIGHT_SELECT, lightSelect == "power" ? HIPPT_LIGHT_SELECT_POWER : 0);
     hipptSetOption(HIPPT_OPT_LIGHT_SAMPLING_MODE, mis ? HIPPT_LIGHT_SAMPLING_MIS : lightSampling ? 1 : 0);
     if (!mesh.empty()) {
         // the scene is the library's (shared by every interface)

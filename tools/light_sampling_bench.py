@@ -2,8 +2,9 @@
 """What light sampling (HIPPT_OPT_LIGHT_SAMPLING) costs per frame and buys per unit of time, on one device.  No
 oracle and no reference tree: it measures, it does not check.
 
-Per scene (hippt.scenes.cornell_lit of a base scene; a child process of its own, ended after --limit seconds;
-the tool stops at the first child that fails), at 1920x1080 and depth 8:
+Per scene (hippt.scenes.cornell_lit of a base scene, or for a name BASE_lamps hippt.scenes.cornell_lamps of BASE; a
+child process of its own, ended after --limit seconds; the tool stops at the first child that fails), at 1920x1080
+and depth 8:
   frame time    hipptRenderFrames(f, 1) with no host copy, the option off (the render megakernel), on (the
                 light-sampling route) and, with --modes 0,1,2 (the default), with MIS (HIPPT_LIGHT_SAMPLING_MIS, the
                 same route), alternating call by call after --warmup untimed rounds, each timed by a host clock
@@ -15,6 +16,10 @@ the tool stops at the first child that fails), at 1920x1080 and depth 8:
                 the accumulated rgb against the reference, the same without the 0.1 % of pixels that err most, and
                 the largest absolute error of a channel.  The reference holds the option-off render's own
                 samples (frames 0..): a share of n / ref-spp of it.
+  light choice  with --select 0,1: under MIS, HIPPT_OPT_LIGHT_SELECT 0 (uniform) against 1 (by power): the frame time
+                of each, alternating call by call as above, and per entry n of --spp the errors above of n frames
+                with the first value against as many frames with each other value as take the same time, all
+                against the same option-off reference image ("select" in the result).
 
 Writes <out>/<base>.json and prints one summary line per scene."""
 import argparse
@@ -36,7 +41,8 @@ def child(args):
     import hippt
     from hippt import scenes
 
-    sc = scenes.cornell_lit(args.scene)
+    lamps = args.scene.endswith("_lamps")
+    sc = scenes.cornell_lamps(args.scene[:-len("_lamps")]) if lamps else scenes.cornell_lit(args.scene)
     pt = hippt.PathTracer()
     pt.setDevices([args.device])
     pt.uploadMesh(sc)
@@ -88,6 +94,42 @@ def child(args):
                                           "mse_without_worst_permille": float(err[:len(err) - len(err) // 1000].mean()),
                                           "max_abs_error": float(np.abs(img - ref).max())}
         equal.append(row)
+    select = None
+    if args.select:
+        vals = tuple(int(x) for x in args.select.split(","))
+
+        def render_select(sel, frames):
+            pt.setOption(hippt.OPT_LIGHT_SELECT, sel)
+            got = render(2, frames)
+            if int(lib.hipptGetOption(hippt.INFO_LIGHT_SELECT)) != sel:
+                raise SystemExit(f"{args.scene}: the render did not apply light selection {sel}")
+            return got
+
+        for _ in range(args.warmup):
+            for sel in vals:
+                render_select(sel, 1)
+        sms = {sel: [] for sel in vals}
+        for _ in range(args.runs):
+            for sel in vals:
+                sms[sel].append(render_select(sel, 1)[0] * 1e3)
+        smed = {sel: statistics.median(v) for sel, v in sms.items()}
+        rows = []
+        for n0 in [int(x) for x in args.spp.split(",")]:
+            row = {}
+            for sel in vals:
+                n = max(1, int(round(n0 * smed[vals[0]] / smed[sel])))
+                dt, s, sh = render_select(sel, n)
+                img = pt.readback()[1][..., :3].astype(np.float64)
+                err = np.sort(((img - ref) ** 2).mean(axis=-1).ravel())
+                row[str(sel)] = {"frames": n, "ms": round(dt * 1e3, 3), "segments": s, "shadow_rays": sh,
+                                 "mse": float(err.mean()),
+                                 "mse_without_worst_permille": float(err[:len(err) - len(err) // 1000].mean()),
+                                 "max_abs_error": float(np.abs(img - ref).max())}
+            rows.append(row)
+        pt.setOption(hippt.OPT_LIGHT_SELECT, 0)
+        select = {"mode": 2, "order": ", ".join(str(v) for v in vals) + " alternating per call",
+                  "ms": {str(sel): [round(x, 4) for x in sms[sel]] for sel in vals},
+                  "median_ms": {str(sel): round(smed[sel], 4) for sel in vals}, "equal_time": rows}
     pt.setOption(hippt.OPT_LIGHT_SAMPLING, 0)
     out = {"scene": sc.name, "primitives": sc.num_tris + sc.num_spheres, "lights": int(lib.hipptGetOption(hippt.INFO_LIGHTS)),
            "width": W, "height": H, "max_depth": DEPTH, "warmup": args.warmup, "runs": args.runs,
@@ -100,6 +142,8 @@ def child(args):
            "gsegments_per_s": {key[on]: round(segs[on] / med[on] / 1e6, 3) for on in modes},
            "reference": {"spp": args.ref_spp, "option": 0, "seconds": round(t_ref, 3)},
            "equal_time": equal}
+    if select:
+        out["select"] = select
     lib.cudaPathTracerShutdown()
     print(json.dumps(out))
 
@@ -113,6 +157,7 @@ def main():
     ap.add_argument("--ref-spp", type=int, default=16384)
     ap.add_argument("--spp", default="1,4,16,64", help="frames with the option on of the equal-time comparisons")
     ap.add_argument("--modes", default="0,1,2", help="values of the option to time: 0,1 or 0,1,2")
+    ap.add_argument("--select", default="", help="values of HIPPT_OPT_LIGHT_SELECT to compare under MIS: 0,1 (default: none)")
     ap.add_argument("--limit", type=float, default=500.0, help="seconds a scene's child process may take")
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "light_sampling"))
     ap.add_argument("--scene", help=argparse.SUPPRESS)  # the child's
@@ -123,7 +168,7 @@ def main():
     for name in args.scenes.split(","):
         cmd = [sys.executable, os.path.abspath(__file__), "--scene", name, "--device", str(args.device), "--warmup",
                str(args.warmup), "--runs", str(args.runs), "--ref-spp", str(args.ref_spp), "--spp", args.spp, "--modes",
-               args.modes]
+               args.modes] + (["--select", args.select] if args.select else [])
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.limit)
         except subprocess.TimeoutExpired:
@@ -131,7 +176,7 @@ def main():
         if r.returncode != 0:
             raise SystemExit(f"{name}: exit status {r.returncode}; stopping\n{r.stderr[-2000:]}")
         res = json.loads(r.stdout.strip().splitlines()[-1])
-        with open(os.path.join(args.out, f"{name}_lit.json"), "w") as fo:
+        with open(os.path.join(args.out, f"{name}.json" if name.endswith("_lamps") else f"{name}_lit.json"), "w") as fo:
             json.dump(res, fo, indent=1)
             fo.write("\n")
         m = res["median_ms"]
@@ -142,6 +187,12 @@ def main():
         print(f"{res['scene']:18s} " + "  ".join(f"{k} {v:7.3f} ms" for k, v in m.items()) +
               f"  shadow share {res['shadow_share']:.3f}  mse {'/'.join(cols)} at equal time, frames on v off (without the "
               f"worst 0.1 % of pixels) and the largest error: {eq}", flush=True)
+        if "select" in res:
+            sel = res["select"]
+            print(f"{res['scene']:18s} light choice under MIS: " + "  ".join(f"{k} {v:7.3f} ms" for k, v in sel["median_ms"].items()) +
+                  "  mse at equal time: " + "  ".join("v".join(str(r["frames"]) for r in e.values()) + ": " +
+                                                      "/".join(f"{r['mse']:.4g}" for r in e.values()) for e in sel["equal_time"]),
+                  flush=True)
 
 
 if __name__ == "__main__":

@@ -14,6 +14,11 @@ path there was before it, hipptUploadScene (host SAH rebuild, stream drain, real
 (b) decay: the render rate (ms per 8-spp depth-8 batch) after 1, 10 and 100 cumulative wobble steps
     applied by refit, against a fresh hipptUploadScene of the same vertices.
 --kernels N runs N update+render iterations and nothing else (for a kernel trace of the passes).
+--lights N runs measurement (c) and nothing else: the scene with every Nth triangle emissive (6, 4, 2), under
+    HIPPT_LIGHT_SAMPLING_MIS: hipptUpdateVertices (host memory) plus a 1-spp frame to idle with
+    HIPPT_OPT_LIGHT_SELECT 0 and 1 alternating, and the update alone to idle on that scene against the same
+    triangles without a light (no selection table to rebuild): the difference is the table's share of an update.
+    Written to <out>/<scene>_lights.json.
 
 Writes one JSON file per scene into --out and prints one line per figure."""
 import argparse
@@ -41,6 +46,85 @@ def with_verts(sc, v):
     return out
 
 
+def lights(args, lib, dev):
+    """Measurement (c): the selection table's rebuild behind the refit."""
+    for name in args.scenes.split(","):
+        plain = scenes.get_scene(name)
+        v0 = np.ascontiguousarray(plain.verts, np.float32).reshape(-1, 9)
+        p = v0.reshape(-1, 3)
+        ext = float((p.max(axis=0) - p.min(axis=0)).max())
+        phase = 0.7 * (np.arange(9) % 3)
+        moved = [v0 + np.float32(0.02 * ext) * np.sin(7.0 / ext * v0.astype(np.float64) + phase + 0.37 * i).astype(np.float32)
+                 for i in range(8)]
+        lit = copy.copy(plain)
+        m = plain.materials()
+        k = len(m)
+        tm = np.array(plain.tri_mat, np.int32)
+        tm[np.arange(args.lights // 2, len(tm), args.lights)] = k
+        lit.tri_mat = tm
+        lit.albedo = np.concatenate([m["albedo"], [(6.0, 4.0, 2.0)]]).astype(np.float32)
+        lit.mat_kind = np.concatenate([m["kind"], [scenes.MAT_EMISSIVE]]).astype(np.int32)
+        lit.fuzz = np.concatenate([m["fuzz"], [0.0]]).astype(np.float32)
+        lit.ir = np.concatenate([m["ir"], [1.0]]).astype(np.float32)
+        pt = hippt.PathTracer()
+        pt.setDevices([args.device])
+        pt.setOption(hippt.OPT_LIGHT_SAMPLING_MODE, hippt.LIGHT_SAMPLING_MIS)
+
+        def loop(frame):
+            t0 = time.perf_counter()
+            for i in range(args.iters):
+                pt.updateVertices(moved[i % 8])
+                if frame:
+                    assert pt.renderFramesAsync(1, args.depth), pt.lastError()
+                assert pt.synchronize(), pt.lastError()
+            return (time.perf_counter() - t0) * 1e3 / args.iters
+
+        out = {"scene": name, "triangles": len(v0), "every": args.lights, "width": args.width, "height": args.height,
+               "depth": args.depth, "iters": args.iters, "warmup": args.warmup, "runs": args.runs,
+               "device": torch.cuda.get_device_name(dev), "unit": "ms per iteration to idle (host clock)"}
+        # the update alone: with lights (the table is rebuilt behind the refit) against without (no table)
+        alone = {}
+        for what, sc in (("with_lights", lit), ("without_lights", plain)):
+            pt.uploadScene(sc)
+            if not pt.initialize(args.width, args.height):
+                raise SystemExit(pt.lastError())
+            if what == "with_lights":
+                out["lights"] = int(lib.hipptGetOption(hippt.INFO_LIGHTS))
+            for _ in range(args.warmup):
+                loop(False)
+            alone[what] = [round(loop(False), 4) for _ in range(args.runs)]
+        out["update_alone_ms"] = alone
+        # update + one frame, the light choice off and on, alternating
+        pt.uploadScene(lit)
+        if not pt.initialize(args.width, args.height):
+            raise SystemExit(pt.lastError())
+        frame = {"0": [], "1": []}
+        for r in range(args.warmup + args.runs):
+            for sel in (0, 1):
+                pt.setOption(hippt.OPT_LIGHT_SELECT, sel)
+                ms = loop(True)
+                if int(lib.hipptGetOption(hippt.INFO_LIGHT_SELECT)) != sel:
+                    raise SystemExit("the render did not apply the light choice asked for")
+                if r >= args.warmup:
+                    frame[str(sel)].append(round(ms, 4))
+        pt.setOption(hippt.OPT_LIGHT_SELECT, 0)
+        out["update_plus_frame_ms"] = frame
+        med = {w: statistics.median(v) for w, v in alone.items()}
+        fmed = {w: statistics.median(v) for w, v in frame.items()}
+        out["median_ms"] = {"update_with_lights": med["with_lights"], "update_without_lights": med["without_lights"],
+                            "table": round(med["with_lights"] - med["without_lights"], 4),
+                            "update_plus_frame_select_0": fmed["0"], "update_plus_frame_select_1": fmed["1"],
+                            "table_share_of_update_plus_frame": round((med["with_lights"] - med["without_lights"]) / fmed["1"], 4)}
+        with open(os.path.join(args.out, f"{name}_lights.json"), "w") as fo:
+            json.dump(out, fo, indent=1)
+            fo.write("\n")
+        print(f"{name}: {out['lights']} lights; update alone {med['with_lights']:.3f} ms with lights, "
+              f"{med['without_lights']:.3f} ms without (table {out['median_ms']['table']:.3f} ms); update + frame "
+              f"{fmed['0']:.3f} ms uniform, {fmed['1']:.3f} ms by power", flush=True)
+    pt.setOption(hippt.OPT_LIGHT_SAMPLING_MODE, 0)
+    lib.cudaPathTracerShutdown()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--scenes", default="blob70k,cornell34")
@@ -53,6 +137,7 @@ def main():
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--decay", default="blob70k", help="scenes of measurement (b)")
     ap.add_argument("--kernels", type=int, default=0)
+    ap.add_argument("--lights", type=int, default=0, help="measurement (c): every Nth triangle emissive")
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "refit"))
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -66,6 +151,8 @@ def main():
         if not ok:
             raise SystemExit(e.value.decode() if e.value else "call failed")
 
+    if args.lights:
+        return lights(args, lib, dev)
     for name in args.scenes.split(","):
         sc = scenes.get_scene(name)
         v0 = np.ascontiguousarray(sc.verts, np.float32).reshape(-1, 9)
