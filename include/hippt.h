@@ -167,8 +167,73 @@ enum { HIPPT_SCENE_NODES2 = 0, HIPPT_SCENE_NODES4 = 1, HIPPT_SCENE_PRIMS = 2, HI
        /* the light selection table (HIPPT_OPT_LIGHT_SELECT below), as the device built it: one record of 4
           words per light in ascending primitive id: the primitive id as uploaded, q_j, c_j, the bits of
           ip_j; 0 bytes for a scene without lights or with more than 2^20 - 1 */
-       HIPPT_SCENE_LIGHTS = 4 };
+       HIPPT_SCENE_LIGHTS = 4,
+       /* the environment (hipptSetEnvironment below) as context 0 holds it, whatever scene is current: one
+          record of 16 bytes per texel, row-major, row y indexing w: r, g, b as float32 and a zero word; 0
+          bytes without one */
+       HIPPT_SCENE_ENVIRONMENT = 5 };
 long long hipptSceneDownload(int what, void *dst, long long bytes, const char **errorMessage);
+
+/* ---- environment: a settable sky (tests/env_ref.py is the statement of record) ----
+ * In place of the sky gradient, an uploaded scene's paths take a miss's radiance from an HDR environment
+ * map: wherever a path rule above or below says "miss: thr x sky", thr.c * e.c stands instead, e = env(d):
+ *   plain paths:                 L.c = thr.c * e.c               (one multiply)
+ *   light sampling modes 1, 2:   L.c = Lacc.c + thr.c * e.c
+ * d is the direction of the segment that missed, exactly as the path holds it, at any length: the caller's
+ * own for segment 0 of hipptTraceRadiance, the camera's or the scatter's otherwise.  Nothing else changes:
+ * the segments, the RNG chain, a, the depth rule, emissive hits and their MIS weights.  Only the scatter
+ * sample finds the environment; no connection samples it.
+ *
+ * The map is a square octahedral image of S x S texels E[y][x] (rgb, float32, finite, >= 0, may exceed 1),
+ * 1 <= S <= 4096 (at 4096 the device's 16-byte texels are 256 MiB per context).  +y is up and the upper
+ * hemisphere is the inner diamond.  The centre of texel (x, y) is u = (2x + 1)/S - 1, w = (2y + 1)/S - 1; its
+ * direction has dy = 1 - |u| - |w| and (dx, dz) = (u, w) if dy >= 0, else ((1 - |w|) sg(u), (1 - |u|) sg(w)),
+ * then normalised.  env(d) has no transcendental and no square, so a length from 2^-100 to 2^80 gives the
+ * words of a unit direction; each line is one IEEE float32 operation in the association written:
+ *   s  = (|dx| + |dy|) + |dz|
+ *   u  = dx / s;   w = dz / s
+ *   if dy < 0:  (u, w) = ((1 - |w|) * sg(u), (1 - |u|) * sg(w))   sg(x) = x < 0 ? -1 : 1, both from the old u, w
+ *   h  = 0.5f * float(S)
+ *   fx = fminf(fmaxf(fmaf(u, h, h) - 0.5f, 0.0f), float(S - 1))   fy the same from w (minNum/maxNum: NaN gives 0)
+ *   x0 = int(fx); x1 = min(x0 + 1, S - 1); a = fx - float(x0)     y0, y1, b the same from fy
+ *   per channel: top = fmaf(a, E[y0][x1] - E[y0][x0], E[y0][x0]); bot the same on row y1;
+ *                e = fmaf(b, bot - top, top)
+ * S = 1 is a constant background colour; equal neighbouring texels give that value exactly.  The filter is
+ * bilinear with clamp to edge: across the lower hemisphere's fold lines (the square's border, where the
+ * -y hemisphere's directions meet) it is not continuous within half a texel.
+ *
+ * hipptSetEnvironment: texels = size*size*3 floats, row-major, row y indexing w.  texels NULL with size 0
+ * removes the environment: the gradient is back.  Host memory is validated and copied before the call
+ * returns: a negative or non-finite texel, a size outside 1..4096 or unknown flags is rejected before any
+ * device call, and a rejected call leaves the old environment in place.  With HIPPT_ENV_DEVICE the pointer
+ * is memory of one of the contexts' devices (after an Init); it is fetched into the library's host copy and
+ * not inspected.  Stream order, as hipptUpdateVertices: work enqueued earlier sees the old environment, work
+ * enqueued later the new one.  A call of the size already set waits for nothing queued and reallocates no
+ * device memory; a change of size may wait for the queued work of every context (the old buffer is freed),
+ * and a device-memory call waits for its fetch.  The environment belongs to the library, not to a scene: it
+ * stays across hipptUploadScene, a re-Init and hipptSetDevices until it is removed, and reaches every
+ * context.  Before an Init the call sets the host copy only.  The built-in 4-sphere scene ignores it.
+ *
+ * A mesh render with an environment takes the ray-per-lane route of the light-sampling renders (a path
+ * kernel launch per batch over the camera's own samples), whatever HIPPT_OPT_LIGHT_SAMPLING_MODE and
+ * HIPPT_OPT_PATH_MODE say, under that route's conditions: no chaining, sky rectangle, render pad or item
+ * order (their HIPPT_INFO_* read 0) and no traversal counts.  hipptGetOption(HIPPT_INFO_ENVIRONMENT): the
+ * size the last render applied, 0 for the gradient or the built-in scene. */
+enum { HIPPT_ENV_DEVICE = 1 };   /* flags: texels is device memory of one of the contexts' devices */
+enum { HIPPT_INFO_ENVIRONMENT = 110 };
+bool hipptSetEnvironment(const float *texels, int size, int flags, const char **errorMessage);
+/* Host only: rgb[3 i ..] = env(dirs[3 i ..]) of the library's host copy, i < n, by the very text the kernels
+ * compile (the hook by which a CPU test pins their arithmetic).  Fails without an environment. */
+bool hipptEnvLookup(const float *dirs, long long n, float *rgb, const char **errorMessage);
+/* dirs[3 (y size + x) ..]: the unit direction of texel (x, y)'s centre (computed in double, rounded once).
+ * Nothing is written for a size outside 1..4096. */
+void hipptEnvDirections(int size, float *dirs);
+/* Host only, double precision: texels (size*size*3 floats) from a lat-long image rgb (width*height*3 floats,
+ * row 0 at +y), sampled bilinearly at the texel-centre directions.  Pixel (c, r)'s centre is at
+ * theta = pi (r + 1/2) / height from +y and phi = 2 pi (c + 1/2) / width - pi, direction
+ * (sin theta cos phi, cos theta, sin theta sin phi); wraps in phi, clamps in theta.  No prefilter: an image
+ * much larger than the map aliases. */
+bool hipptEnvFromEquirect(const float *rgb, int width, int height, int size, float *texels, const char **errorMessage);
 
 /* ---- devices and row bands ------------------------------------------------------- */
 int hipptDeviceCount(void);

@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "bvh_builder.h"
+#include "env_io.h"
 #include "mesh_io.h"
 #include "hippt_chain_logic.h"
 #include "hippt_denoise.h"
@@ -104,15 +105,17 @@ struct OccKey {
     bool ldsScene = false, full = false, spills = false;
     int variant = 0;  // ray-per-lane launches: the QueryMode, or a path kernel's route (kVariantPath ...)
     bool select = false;  // a light-sampling route's kernel with the selection table (HIPPT_OPT_LIGHT_SELECT)
+    bool env = false;     // a path kernel's ENV variant (hipptSetEnvironment)
 };
 // The path kernel's routes as OccKey variants, after the QueryModes: plain paths, light-sampled path
 // queries, the light-sampling render route.
 constexpr int kVariantPath = 8, kVariantLitPath = 9, kVariantLitRender = 10, kVariantMisPath = 11, kVariantMisRender = 12;
+constexpr int kVariantEnvRender = 13;  // plain paths from the camera start: the render route under an environment
 
 bool same_key(const OccKey &a, const OccKey &b) {
     return a.version == b.version && a.stackDepth == b.stackDepth && a.fmt == b.fmt && a.poolWords == b.poolWords &&
            a.topBytes == b.topBytes && a.ldsScene == b.ldsScene && a.full == b.full && a.spills == b.spills &&
-           a.variant == b.variant && a.select == b.select;
+           a.variant == b.variant && a.select == b.select && a.env == b.env;
 }
 
 // Run costs computed on a detached host thread (HIPPT_OPT_ITEM_ORDER automatic).  The thread owns a
@@ -276,6 +279,12 @@ struct Ctx {
     // behind every vertex update's refit, so it is current in stream order whatever the option says.
     // Null for a scene without lights or with more than the table's limit (light_table_fits).
     unsigned *lightTable = nullptr;
+    // Environment (hipptSetEnvironment): the context's copy of State::env, envSize x envSize texels, written
+    // on the stream (upload_env); envRev: the State::envRev it holds or has queued.  Not a scene buffer: it
+    // outlives the scene, and goes with the context.
+    hippt::env::Texel *env = nullptr;
+    int envSize = 0;
+    unsigned envRev = 0;
     // Denoiser (hipptDenoise, hippt_denoise.h): one buffer of 80 bytes per pixel (the guide sample's hit
     // records, two colour buffers, the guide), allocated at first use, reused while large enough and
     // freed with the context; the stages' timing events (HIPPT_OPT_DENOISE_TIMING), created on use.
@@ -359,6 +368,21 @@ struct State {
     int activeLightSampling = 0;        // the mode of the light-sampling route if the last render took it (HIPPT_INFO_LIGHT_SAMPLING)
     int lightSelect = 0;                // HIPPT_OPT_LIGHT_SELECT: 0 uniform, HIPPT_LIGHT_SELECT_POWER
     int activeLightSelect = 0;          // as the last light-sampling render applied it (HIPPT_INFO_LIGHT_SELECT)
+    // hipptSetEnvironment: the host copy (envSize x envSize texels in the device layout; empty: the sky
+    // gradient), its revision (a context whose envRev differs has yet to receive it), the size the last
+    // render applied (HIPPT_INFO_ENVIRONMENT), and the pinned staging buffers of uploads that may still be
+    // queued on a stream: a call fills a free one (every event passed) and leaves it to its copies.
+    std::vector<hippt::env::Texel> env;
+    int envSize = 0;
+    unsigned envRev = 0;
+    int activeEnv = 0;
+    struct EnvStage {
+        hippt::env::Texel *ptr = nullptr;
+        size_t bytes = 0;
+        unsigned rev = 0;                              // the State::envRev it holds
+        std::vector<std::pair<int, hipEvent_t>> busy;  // (device, event)
+    };
+    std::vector<EnvStage> envStages;
     long long denoiseNs[hippt::kDenoiseStages] = {};  // HIPPT_INFO_DENOISE_NS + k of the last timed hipptDenoise
     std::vector<unsigned> auditWords;   // closed runs' audit words not yet read (hipptChainAudit)
     std::vector<std::pair<int, uint32_t *>> rngTables;  // per device, built on first use
@@ -633,6 +657,7 @@ void free_scene_buffers(Ctx &c) {
 }
 
 void harvest_audit(Ctx &c);
+void env_stages_release();
 
 // Waits for the copies that still read or write staging array b (State::Update) and forgets them.
 void stage_wait(int b) {
@@ -815,6 +840,7 @@ void destroy_ctx(Ctx &c, bool keep) {
     (void)hipFree(c.qStage);
     if (c.qDone) (void)hipEventDestroy(c.qDone);
     (void)hipFree(c.dnBuf);
+    (void)hipFree(c.env);
     for (hipEvent_t e : c.dnEv) (void)hipEventDestroy(e);
     (void)hipHostFree(c.wfHost);
     for (hipEvent_t e : c.wfPoll)
@@ -844,6 +870,7 @@ void destroy_all(bool keep = false) {
     s.rngTables.clear();
     stage_wait(0);  // (the contexts' streams are finished: these return at once)
     stage_wait(1);
+    env_stages_release();
     if (!keep) {
         settle_scene();
         for (float *&p : s.upd.stage) {
@@ -1781,6 +1808,7 @@ bool enqueue_sphere4(Ctx &c, int firstFrame, int count, int maxDepth, bool copy,
     State &s = S();
     // the legacy kernel writes accum/out itself: a mesh batch's pending combine goes first
     if (!flush_deferred(c, err)) return false;
+    s.activeEnv = 0;  // (the built-in scene keeps its gradient)
     hippt::Sphere4Params p{c.accum, c.out, c.stats, s.width, s.height, c.y0, c.rows, c.stride, firstFrame, count,
                            maxDepth, s.pixelFormat, nullptr};
     // A blocking frame (the app's cudaPathTracerRender): the kernel writes the words into
@@ -1814,6 +1842,107 @@ void set_light_select(const Ctx &c, hippt::PathParams &p) {
         hippt::light_table_buffers(c.lightTable, int(S().scene.lights.size()), S().scene.numTris);
     p.lightCdf = t.cdf;
     p.lightIp = t.ipPrim;
+}
+
+// ---- environment (hipptSetEnvironment; hippt_env.h) ----
+// The environment as applied: its size for an uploaded scene, else 0 (the built-in scene keeps its gradient).
+int env_applies() {
+    const State &s = S();
+    return s.scene.kind == HIPPT_SCENE_MESH ? s.envSize : 0;
+}
+
+// Forgets the copies of a staging buffer that have finished; true if none is left.
+bool env_stage_free(State::EnvStage &st) {
+    size_t kept = 0;
+    for (auto &de : st.busy) {
+        (void)hipSetDevice(de.first);
+        if (hipEventQuery(de.second) == hipSuccess) (void)hipEventDestroy(de.second);
+        else st.busy[kept++] = de;
+    }
+    (void)hipGetLastError();  // (hipErrorNotReady is no error of ours)
+    st.busy.resize(kept);
+    return st.busy.empty();
+}
+
+// Waits for every queued upload and frees the staging buffers (the contexts go away).
+void env_stages_release() {
+    for (auto &st : S().envStages) {
+        for (auto &de : st.busy) {
+            (void)hipSetDevice(de.first);
+            (void)hipEventSynchronize(de.second);
+            (void)hipEventDestroy(de.second);
+        }
+        if (st.ptr) (void)hipHostFree(st.ptr);
+    }
+    S().envStages.clear();
+}
+
+// Brings context c's copy of the environment up to the host copy's revision, in stream order: launches
+// queued before see the old texels, later ones the new.  A copy of the same size is one hipMemcpyAsync from
+// a pinned staging buffer that no earlier upload still reads; another size waits for the stream (queued
+// launches read the buffer that is freed).
+bool upload_env(Ctx &c, const char **err) {
+    State &s = S();
+    if (c.envRev == s.envRev) return true;
+    if (s.envSize == 0) {  // removed: the buffer stays for the launches that may still read it
+        c.envRev = s.envRev;
+        return true;
+    }
+    HIP_TRY(hipSetDevice(c.device));
+    const size_t bytes = s.env.size() * sizeof(hippt::env::Texel);
+    if (c.envSize != s.envSize) {
+        HIP_TRY(hipStreamSynchronize(c.stream));
+        (void)hipFree(c.env);
+        c.env = nullptr;
+        c.envSize = 0;
+        HIP_TRY(hipMalloc(&c.env, bytes));
+        c.envSize = s.envSize;
+    }
+    // the staging buffer of this revision, or a free one filled now; other free ones beyond one go
+    State::EnvStage *st = nullptr;
+    for (auto &e : s.envStages)
+        if (e.rev == s.envRev) st = &e;
+    if (!st) {
+        std::vector<State::EnvStage> keep;
+        bool taken = false, spare = false;
+        for (auto &e : s.envStages) {
+            const bool free = env_stage_free(e);
+            if (free && !taken && e.bytes >= bytes) {
+                taken = true;
+                keep.insert(keep.begin(), e);  // (first: found again below)
+            } else if (!free || !spare) {
+                spare = spare || free;
+                keep.push_back(e);
+            } else {
+                (void)hipHostFree(e.ptr);
+            }
+        }
+        s.envStages.swap(keep);
+        if (taken) st = &s.envStages.front();
+        if (!st) {
+            State::EnvStage e;
+            HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&e.ptr), bytes, hipHostMallocDefault));
+            e.bytes = bytes;
+            s.envStages.push_back(e);
+            st = &s.envStages.back();
+        }
+        std::memcpy(st->ptr, s.env.data(), bytes);
+        st->rev = s.envRev;
+    }
+    HIP_TRY(hipMemcpyAsync(c.env, st->ptr, bytes, hipMemcpyHostToDevice, c.stream));
+    hipEvent_t ev = nullptr;
+    HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    st->busy.push_back({c.device, ev});
+    HIP_TRY(hipEventRecord(ev, c.stream));
+    c.envRev = s.envRev;
+    return true;
+}
+
+// The environment's pointers for a launch of c (upload_env has run), or nulls without one.
+void set_env(const Ctx &c, hippt::PathParams &p) {
+    if (!env_applies()) return;
+    p.env = c.env;
+    p.envSize = c.envSize;
 }
 
 // A mesh call's batches on a context: as many frames per batch as the sample scratch budget
@@ -1956,7 +2085,8 @@ bool enqueue_mesh(Ctx &c, const CameraF &cam, int firstFrame, int count, int max
     if (!ensure_scene(c, err)) return false;
     s.activeLightSampling = 0;
     s.activeLightSelect = 0;
-    if (const int mode = light_sampling_applies(); maxDepth > 0 && mode)
+    s.activeEnv = 0;
+    if (const int mode = light_sampling_applies(); maxDepth > 0 && (mode || env_applies()))
         return enqueue_mesh_lights(c, cam, firstFrame, count, maxDepth, mode, err);
     const unsigned bandPixels = unsigned(c.rows) * unsigned(s.width);
     const BatchSize size = frames_per_batch(bandPixels, count);
@@ -2237,19 +2367,28 @@ hippt::QueryCam query_cam(const CameraF &cam, int y0, int rowStride, unsigned ba
 // scene's parameters under layout L (query_scene_params): the kernel's resident blocks per CU, the claim
 // counters and, a 4-wide tree, a spill area for every resident lane, set in q.
 bool ensure_ray_launch(Ctx &c, RayLaunch &r, const plan::Layout &L, int variant, hippt::QueryParams &q, const char **err) {
-    const bool select = variant >= kVariantLitPath && light_select_applies() && c.lightTable;
+    const bool lit = variant >= kVariantLitPath && variant <= kVariantMisRender;
+    const bool select = lit && light_select_applies() && c.lightTable;
+    // the environment (a path kernel's launches only): the context's copy first, in stream order; the general kernels
+    const bool envOn = variant >= kVariantPath && env_applies();
+    if (envOn) {
+        if (!upload_env(c, err)) return false;
+        q.full = 1;
+    }
     OccKey occKey;
     occKey.version = S().scene.version, occKey.stackDepth = L.stackDepth, occKey.fmt = L.fmt, occKey.topBytes = L.topBytes;
     occKey.ldsScene = L.ldsScene, occKey.full = q.full != 0;
     occKey.variant = variant;
     occKey.select = select;
+    occKey.env = envOn;
     if (!same_key(r.occKey, occKey)) {
         // (the pointers select the kernel: any non-null scratch the render route's)
-        const bool render = variant == kVariantLitRender || variant == kVariantMisRender;
-        hippt::PathParams pp{q, c.mats, nullptr, nullptr, nullptr, 1, variant >= kVariantLitPath ? c.lights : nullptr, 1,
-                             variant >= kVariantMisPath ? 2 : 1, render ? reinterpret_cast<float *>(c.stats) : nullptr,
-                             nullptr};
+        const bool render = variant == kVariantLitRender || variant == kVariantMisRender || variant == kVariantEnvRender;
+        hippt::PathParams pp{q, c.mats, nullptr, nullptr, nullptr, 1, lit ? c.lights : nullptr, 1,
+                             variant == kVariantMisPath || variant == kVariantMisRender ? 2 : 1,
+                             render ? reinterpret_cast<float *>(c.stats) : nullptr, nullptr};
         if (select) set_light_select(c, pp);
+        if (envOn) set_env(c, pp);
         r.blocksPerCu = variant >= kVariantPath ? hippt::path_blocks_per_cu(pp)
                                                 : hippt::query_blocks_per_cu(q, hippt::QueryMode(variant));
         r.occKey = occKey;
@@ -2278,8 +2417,9 @@ bool query_setup(Ctx &c, const QueryCall &call, hippt::QueryParams &q, const cha
     return ensure_ray_launch(c, c.qLaunch, L, variant, q, err);
 }
 
-// The light-sampling render route (HIPPT_OPT_LIGHT_SAMPLING on a scene with a light): each
-// batch is one launch of the path queries' light-sampling kernel over the renderer's own camera samples
+// The ray-per-lane render route: light sampling (HIPPT_OPT_LIGHT_SAMPLING on a scene with a light; DESIGN.md §16;
+// mode 1 or 2) and, with or without it (mode 0: plain paths), an environment (hipptSetEnvironment; §19).  Each
+// batch is one launch of the path queries' kernel of that mode over the renderer's own camera samples
 // (QueryCam: the context's rows of the image, frame-major items as the combine reads them), into the batch
 // scratch, combined by the deferred combine.  No chaining, sky rectangle, render pad or item order.  Its
 // counters and spill area are the route's own: a batch may still be in flight when a query is made.
@@ -2291,10 +2431,13 @@ bool enqueue_mesh_lights(Ctx &c, const CameraF &cam, int firstFrame, int count, 
     const plan::Layout L = query_scene_params(c, q);
     q.cam = query_cam(cam, c.y0, c.stride, bandPixels, firstFrame);
     RayLaunch &R = c.litLaunch;
-    if (!ensure_ray_launch(c, R, L, mode == 2 ? kVariantMisRender : kVariantLitRender, q, err)) return false;
-    hippt::PathParams np{q,    c.mats,  nullptr, nullptr, nullptr, maxDepth, c.lights, int(s.scene.lights.size()),
-                         mode, nullptr, c.stats};
+    const int variant = mode == 2 ? kVariantMisRender : mode ? kVariantLitRender : kVariantEnvRender;
+    if (!ensure_ray_launch(c, R, L, variant, q, err)) return false;
+    hippt::PathParams np{q,    c.mats,  nullptr, nullptr, nullptr, maxDepth, mode ? c.lights : nullptr,
+                         mode ? int(s.scene.lights.size()) : 0, mode, nullptr, c.stats};
     set_light_select(c, np);
+    set_env(c, np);
+    s.activeEnv = np.envSize;
     s.activeLightSelect = np.lightCdf ? light_select_applies() : 0;
     s.activeWidth = L.wide ? 4 : 2;
     s.activeTopBytes = L.topBytes;
@@ -2344,6 +2487,7 @@ bool query_enqueue(Ctx &c, hippt::QueryParams q, unsigned first, unsigned m, con
                              lit ? c.lights : nullptr, lit ? int(S().scene.lights.size()) : 0, lit,
                              nullptr, nullptr};
         set_light_select(c, np);
+        set_env(c, np);
         HIP_TRY(hippt::launch_path(np, int(blocks), c.stream));
     } else {
         HIP_TRY(hippt::launch_query(q, int(blocks), call.mode, c.stream));
@@ -2984,6 +3128,21 @@ extern "C" long long hipptSceneDownload(int what, void *dst, long long bytes, co
         [&]() -> long long {
             State &s = S();
             auto bad = [&](const char *m) -> long long { return (fail(err, m), -1); };
+            if (what == HIPPT_SCENE_ENVIRONMENT) {  // (not the scene's: whatever scene is current)
+                const size_t envBytes = s.env.size() * sizeof(hippt::env::Texel);
+                if (!envBytes || !dst) return (long long)envBytes;
+                if (bytes < (long long)envBytes) return bad("scene download: destination too small");
+                if (!s.ready || s.ctxs.empty()) return bad("scene download: HIP path tracer not initialized");
+                Ctx &c = s.ctxs[0];
+                if (!upload_env(c, err)) return -1;
+                if (hipSetDevice(c.device) != hipSuccess ||
+                    hipMemcpyAsync(dst, c.env, envBytes, hipMemcpyDeviceToHost, c.stream) != hipSuccess ||
+                    hipStreamSynchronize(c.stream) != hipSuccess) {
+                    (void)hipGetLastError();
+                    return bad("scene download: copy failed");
+                }
+                return (long long)envBytes;
+            }
             if (s.scene.kind != HIPPT_SCENE_MESH) return bad("scene download: no mesh scene");
             const SceneHost &sc = s.scene;
             size_t need = 0;
@@ -3024,6 +3183,87 @@ extern "C" long long hipptSceneDownload(int what, void *dst, long long bytes, co
             return (long long)need;
         },
         [err](const char *what) { return (fail_free(err, what), -1LL); });
+}
+
+// ---- environment ---------------------------------------------------------------------------------
+namespace {
+bool set_environment_locked(const float *texels, int size, int flags, const char **err) {
+    State &s = S();
+    const std::string who = "environment";
+    // argument checks first: none of them touches the GPU, and a rejected call changes nothing
+    if (flags & ~HIPPT_ENV_DEVICE) return fail(err, who + ": unknown flags");
+    if (!texels && size == 0) {  // remove: the sky gradient again
+        s.env.clear();
+        s.env.shrink_to_fit();
+        s.envSize = 0;
+        ++s.envRev;
+        return true;
+    }
+    if (size < 1 || size > hippt::env::kMaxSize)
+        return fail(err, who + ": size must be in 1.." + std::to_string(hippt::env::kMaxSize));
+    if (!texels) return fail(err, who + ": null texels");
+    const size_t count = size_t(size) * size_t(size);
+    std::vector<float> fetched;
+    if (flags & HIPPT_ENV_DEVICE) {
+        if (!s.ready || s.ctxs.empty()) return fail(err, who + ": HIPPT_ENV_DEVICE needs an initialized path tracer");
+        const void *ptr = texels;
+        const size_t align = sizeof(float);
+        int dev = -1;
+        if (!device_pointers_ok(who, "HIPPT_ENV_DEVICE", -1, &ptr, &align, 1, &dev, err)) return false;
+        bool ours = false;
+        for (const Ctx &c : s.ctxs) ours = ours || c.device == dev;
+        if (!ours) return fail(err, who + ": the pointer is on a device that is none of hipptSetDevices'");
+        // the host copy fetches it (not inspected: what the device holds is what the paths see)
+        fetched.resize(count * 3);
+        HIP_TRY(hipSetDevice(dev));
+        HIP_TRY(hipMemcpy(fetched.data(), texels, fetched.size() * sizeof(float), hipMemcpyDeviceToHost));
+        texels = fetched.data();
+    } else {
+        for (size_t k = 0; k < count * 3; ++k)
+            if (!(texels[k] >= 0.0f) || !std::isfinite(texels[k]))
+                return fail(err, who + ": texel " + std::to_string(k / 3) + " is negative or not finite");
+    }
+    std::vector<hippt::env::Texel> next(count);
+    for (size_t k = 0; k < count; ++k) next[k] = hippt::env::Texel{texels[3 * k], texels[3 * k + 1], texels[3 * k + 2], 0.0f};
+    s.env.swap(next);
+    s.envSize = size;
+    ++s.envRev;
+    // every context takes it now, in its stream's order (one that does not exist yet: at its first use)
+    if (s.ready)
+        for (Ctx &c : s.ctxs)
+            if (!upload_env(c, err)) return false;
+    return true;
+}
+}  // namespace
+
+extern "C" bool hipptSetEnvironment(const float *texels, int size, int flags, const char **err) {
+    return abi_bool(kLocked, err, [&]() -> bool { return set_environment_locked(texels, size, flags, err); });
+}
+
+extern "C" bool hipptEnvLookup(const float *dirs, long long n, float *rgb, const char **err) {
+    return abi_bool(kLocked, err, [&]() -> bool {
+        const State &s = S();
+        if (n < 0) return fail(err, "environment lookup: negative count");
+        if (n > 0 && (!dirs || !rgb)) return fail(err, "environment lookup: null pointer");
+        if (!s.envSize) return fail(err, "environment lookup: no environment set");
+        for (long long i = 0; i < n; ++i)
+            hippt::env::lookup(s.env.data(), s.envSize, dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2], rgb[3 * i],
+                               rgb[3 * i + 1], rgb[3 * i + 2]);
+        return true;
+    });
+}
+
+extern "C" void hipptEnvDirections(int size, float *dirs) {
+    abi_void(kUnlocked, [&] { hippt::envio::directions(size, dirs); });
+}
+
+extern "C" bool hipptEnvFromEquirect(const float *rgb, int width, int height, int size, float *texels, const char **err) {
+    return abi_bool(kUnlocked, err, [&]() -> bool {
+        std::string msg;
+        if (hippt::envio::from_equirect(rgb, width, height, size, texels, &msg)) return true;
+        std::lock_guard<std::mutex> g(S().mu);
+        return fail(err, msg);
+    });
 }
 
 // ---- ray queries ---------------------------------------------------------------------------------
@@ -3579,6 +3819,7 @@ long long get_option_locked(int key) {
     case HIPPT_INFO_LIGHT_SAMPLING: return s.activeLightSampling;
     case HIPPT_OPT_LIGHT_SELECT: return s.lightSelect;
     case HIPPT_INFO_LIGHT_SELECT: return s.activeLightSelect;
+    case HIPPT_INFO_ENVIRONMENT: return s.activeEnv;
     case HIPPT_INFO_SKY_RECT_PIXELS: return s.activeSkyPixels;
     case HIPPT_INFO_UPDATE_DROPPED:
         // the last update's count, from the first context that ran it (every context counts the same)

@@ -2,6 +2,7 @@
 // rays and the camera's own rays (include/hippt.h hipptTraceRadiance, hipptCameraRays).
 #pragma once
 
+#include "hippt_env.h"
 #include "hippt_query.h"
 
 namespace hippt {
@@ -24,6 +25,10 @@ namespace hippt {
 // picks its light by the device-built table (hippt_refit.h LightTableBuffers: cdf and ipPrim) in place of the
 // uniform choice, and ip of the light replaces float(numLights); null: uniform, the bytes of before, from the
 // kernels of before (the choice is a compile-time flag of the kernel, as MIS is).
+// Environment (hipptSetEnvironment): with `env` a miss takes throughput x env(d) of the map
+// (hippt_env.h) in place of the sky gradient, from the general kernels (as with `lights`, whatever q.full
+// says), and `scratch` may be set without `lights`: a render batch of plain paths.  Null: the bytes of before,
+// from the kernels of before (a compile-time flag again).
 struct PathParams {
     QueryParams q;
     const float4 *mats;     // MeshParams::mats
@@ -38,6 +43,8 @@ struct PathParams {
     unsigned long long *stats;
     const unsigned *lightCdf = nullptr;  // c_j of the numLights lights, or null (uniform)
     const float *lightIp = nullptr;      // with lightCdf: ip by primitive in leaf order
+    const env::Texel *env = nullptr;     // the environment's size x size texels, or null (the sky gradient)
+    int envSize = 0;
 };
 
 hipError_t launch_path(const PathParams &p, int blocks, hipStream_t s);

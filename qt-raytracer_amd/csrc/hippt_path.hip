@@ -23,6 +23,7 @@
 // light-sampling render route.
 #include "hippt_path.h"
 
+#include "hippt_env.h"
 #include "hippt_ray_loop.h"
 
 namespace hippt {
@@ -189,10 +190,16 @@ __device__ __forceinline__ float light_hit_weight(const Ray &r, float t, int pri
 // connection's light comes from the selection table (PathParams::lightCdf) and the table's ip stands where
 // float(numLights) stood.  A flag and not a branch on the pointer: the branch cost every NEE kernel 1 to 4 VGPRs,
 // and three of the 2-wide query kernels an occupancy step, with the option off.
-template <bool LDS_SCENE, bool FULL, bool WIDE, bool NEE, bool CAMERA, bool MIS, bool SELECT>
+// ENV (general kernels only: FULL): hipptSetEnvironment (tests/env_ref.py is the statement of
+// record).  A miss takes throughput x env(d) of the map (PathParams::env, hippt_env.h) in place of the sky
+// gradient, d the missed segment's direction as the path holds it; nothing else changes.  A flag for the
+// reason SELECT is one.  With ENV the camera start serves plain paths too: an environment sends every mesh
+// render down the ray-per-lane route.
+template <bool LDS_SCENE, bool FULL, bool WIDE, bool NEE, bool CAMERA, bool MIS, bool SELECT, bool ENV>
 __global__ __launch_bounds__(kMeshBlock) void path_kernel(PathParams P) {
     static_assert(FULL || !NEE, "light sampling has general kernels only");
-    static_assert(NEE || !CAMERA, "the camera start belongs to the light-sampling render route");
+    static_assert(FULL || !ENV, "the environment has general kernels only");
+    static_assert(NEE || ENV || !CAMERA, "the camera start belongs to the ray-per-lane render route");
     static_assert(NEE || !MIS, "the weights belong to light sampling");
     static_assert(NEE || !SELECT, "the light choice belongs to light sampling");
     const QueryParams &Q = P.q;
@@ -259,7 +266,7 @@ __global__ __launch_bounds__(kMeshBlock) void path_kernel(PathParams P) {
                     shadow = false;
                 }
                 // begin_query_ray, with the mark of hipptTraceRays' invalid rays (no segment, (0, 0, 0, 0))
-                // in its branch: set after it, the mark costs path_kernel<false, false, false, false, false, false, false>
+                // in its branch: set after it, the mark costs path_kernel<false, false, false, false, false, false, false, false>
                 // 2 VGPRs
                 begin(T);
                 T.bestO = -1;  // a hit at exactly t == tmax loses the tie on the id: tmax is exclusive
@@ -305,8 +312,16 @@ __global__ __launch_bounds__(kMeshBlock) void path_kernel(PathParams P) {
                 begin(T);
             } else if (depth < 0) {
                 // invalid ray
-            } else if (T.bestI < 0) {  // miss: the sky of the segment's direction
-                sky(r, tr, tg, tb, L0, L1, L2);
+            } else if (T.bestI < 0) {  // miss: the sky, or the environment, of the segment's direction
+                if (ENV) {
+                    float e0, e1, e2;
+                    env::lookup(P.env, P.envSize, r.dx, r.dy, r.dz, e0, e1, e2);
+                    L0 = tr * e0;
+                    L1 = tg * e1;
+                    L2 = tb * e2;
+                } else {
+                    sky(r, tr, tg, tb, L0, L1, L2);
+                }
                 segs = depth + 1;
                 if (NEE) ++nseg;
             } else {
@@ -390,29 +405,34 @@ __global__ __launch_bounds__(kMeshBlock) void path_kernel(PathParams P) {
 }
 
 // The kernel of p's scene layout and route: plain paths in all eight layouts, light sampling (plain or with
-// MIS: p.lightMode) in the four general ones (whatever p.q.full says), for a query or a render batch.
+// MIS: p.lightMode) and the environment in the four general ones (whatever p.q.full says), for a query or a
+// render batch.
 using PathFn = void (*)(PathParams);
+template <bool L, bool W, bool E>
+PathFn general_path_fn(const PathParams &p) {
+    const bool cam = p.scratch != nullptr;
+    if (p.lights && p.lightCdf) {
+        if (p.lightMode == 2)
+            return cam ? path_kernel<L, true, W, true, true, true, true, E> : path_kernel<L, true, W, true, false, true, true, E>;
+        return cam ? path_kernel<L, true, W, true, true, false, true, E> : path_kernel<L, true, W, true, false, false, true, E>;
+    }
+    if (p.lights && p.lightMode == 2)
+        return cam ? path_kernel<L, true, W, true, true, true, false, E> : path_kernel<L, true, W, true, false, true, false, E>;
+    if (p.lights)
+        return cam ? path_kernel<L, true, W, true, true, false, false, E> : path_kernel<L, true, W, true, false, false, false, E>;
+    if constexpr (E) {
+        if (cam) return path_kernel<L, true, W, false, true, false, false, true>;
+    }
+    return path_kernel<L, true, W, false, false, false, false, E>;
+}
+
 PathFn path_fn(const PathParams &p) {
     QueryParams q = p.q;
-    if (p.lights) q.full = 1;
+    if (p.lights || p.env) q.full = 1;
     return for_scene_layout(q, [&p](auto lds, auto full, auto wide) -> PathFn {
         constexpr bool L = decltype(lds)::value, F = decltype(full)::value, W = decltype(wide)::value;
-        if constexpr (F) {
-            if (p.lights && p.lightCdf) {
-                if (p.lightMode == 2)
-                    return p.scratch ? path_kernel<L, F, W, true, true, true, true>
-                                     : path_kernel<L, F, W, true, false, true, true>;
-                return p.scratch ? path_kernel<L, F, W, true, true, false, true>
-                                 : path_kernel<L, F, W, true, false, false, true>;
-            }
-            if (p.lights && p.lightMode == 2)
-                return p.scratch ? path_kernel<L, F, W, true, true, true, false>
-                                 : path_kernel<L, F, W, true, false, true, false>;
-            if (p.lights)
-                return p.scratch ? path_kernel<L, F, W, true, true, false, false>
-                                 : path_kernel<L, F, W, true, false, false, false>;
-        }
-        return path_kernel<L, F, W, false, false, false, false>;
+        if constexpr (F) return p.env ? general_path_fn<L, W, true>(p) : general_path_fn<L, W, false>(p);
+        return path_kernel<L, F, W, false, false, false, false, false>;
     });
 }
 
@@ -436,7 +456,9 @@ hipError_t launch_path(const PathParams &p, int blocks, hipStream_t s) {
     const QueryParams &q = p.q;
     if (!query_params_ok(q, blocks)) return hipErrorInvalidValue;
     if (!q.shade || !p.mats || p.maxDepth < 1) return hipErrorInvalidValue;
-    if (p.lights ? (!q.full || p.numLights < 1 || p.lightMode < 1 || p.lightMode > 2) : p.scratch != nullptr)
+    if (p.lights ? (!q.full || p.numLights < 1 || p.lightMode < 1 || p.lightMode > 2) : (p.scratch != nullptr && !p.env))
+        return hipErrorInvalidValue;
+    if (p.env ? (p.envSize < 1 || p.envSize > env::kMaxSize || reinterpret_cast<uintptr_t>(p.env) % 16) : p.envSize != 0)
         return hipErrorInvalidValue;
     if (p.lightCdf ? (!p.lights || !p.lightIp) : p.lightIp != nullptr) return hipErrorInvalidValue;
     // a render batch's counters; a query's own pointers: rays and records are read and stored whole

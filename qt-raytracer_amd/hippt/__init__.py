@@ -81,6 +81,7 @@ INFO_SKY_RECT_PIXELS = 106
 INFO_LIGHTS = 107  # emissive primitives in the uploaded scene
 INFO_LIGHT_SAMPLING = 108  # OPT_LIGHT_SAMPLING_MODE's value (1 or 2) if the last render took the light-sampling route
 INFO_LIGHT_SELECT = 109  # OPT_LIGHT_SELECT's value if the last render took the light-sampling route and applied it
+INFO_ENVIRONMENT = 110  # the environment's size as the last render applied it (0: the gradient, or the built-in scene)
 INFO_DENOISE_NS = 200
 RAYS_DEVICE = 1
 HIT_SPHERE = 1 << 30
@@ -90,11 +91,14 @@ DENOISE_NO_DEMODULATE = 1
 DENOISE_DEVICE = 2
 DENOISE_STAGES = ("guides", "prepare", "pass0", "pass1", "pass2", "pass3", "pass4", "pass5", "pass6", "pass7", "finish")
 VERTS_DEVICE = 1
+ENV_DEVICE = 1
+ENV_MAX_SIZE = 4096
 SCENE_NODES2 = 0
 SCENE_NODES4 = 1
 SCENE_PRIMS = 2
 SCENE_SHADE = 3
 SCENE_LIGHTS = 4  # the light selection table: (prim, q, c, bits of ip) per light
+SCENE_ENVIRONMENT = 5  # the environment's texels: (r, g, b, 0) float32 per texel
 
 # Every symbol include/hippt.h declares (checked by tests/test_abi_cpu.py).
 EXPORTS = (
@@ -114,6 +118,7 @@ EXPORTS = (
     "hipptUpdateVertices", "hipptSceneDownload", "hipptBvhRefit",
     "hipptDenoiseDefaults", "hipptDenoise",
     "hipptTraceRadiance", "hipptCameraRays",
+    "hipptSetEnvironment", "hipptEnvLookup", "hipptEnvDirections", "hipptEnvFromEquirect",
 )
 
 
@@ -266,6 +271,10 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     sig("hipptBvhRefit", c_bool, c_void_p, p_float, c_int, c_float, pp_char)
     sig("hipptDenoiseDefaults", None, ctypes.POINTER(DenoiseParams))
     sig("hipptDenoise", c_bool, ctypes.POINTER(DenoiseParams), c_void_p, c_void_p, pp_char)
+    sig("hipptSetEnvironment", c_bool, c_void_p, c_int, c_int, pp_char)
+    sig("hipptEnvLookup", c_bool, c_void_p, ctypes.c_longlong, c_void_p, pp_char)
+    sig("hipptEnvDirections", None, c_int, c_void_p)
+    sig("hipptEnvFromEquirect", c_bool, c_void_p, c_int, c_int, c_int, c_void_p, pp_char)
     _lib = lib
     return lib
 
@@ -381,7 +390,8 @@ def _update_verts(verts):
     return verts, False
 
 
-_SCENE_WORDS = {SCENE_NODES2: 16, SCENE_NODES4: 32, SCENE_PRIMS: 12, SCENE_SHADE: 4, SCENE_LIGHTS: 4}
+_SCENE_WORDS = {SCENE_NODES2: 16, SCENE_NODES4: 32, SCENE_PRIMS: 12, SCENE_SHADE: 4, SCENE_LIGHTS: 4,
+                SCENE_ENVIRONMENT: 4}
 LIGHT_TABLE_DTYPE = np.dtype([("prim", "<i4"), ("q", "<u4"), ("c", "<u4"), ("ip", "<f4")])
 
 
@@ -389,7 +399,8 @@ def scene_download(what: int) -> np.ndarray:
     """hipptSceneDownload: context 0's device copy of the 2-wide nodes (N, 16), the 4-wide float nodes
     (M, 32; interior child codes are byte offsets), the primitive records (P, 12; leaf order, id in
     word 9), the shading records (P, 4) or the light selection table (L, 4; PathTracer.lightTable names its
-    words), as uint32, after the queued work."""
+    words) or the environment's texels (S*S, 4: the bits of r, g, b and a zero word), as uint32, after the queued
+    work."""
     if what not in _SCENE_WORDS:
         raise HipptError(f"unknown scene buffer {what}")
     lib = load_library()
@@ -401,6 +412,50 @@ def scene_download(what: int) -> np.ndarray:
     if lib.hipptSceneDownload(int(what), out.ctypes.data, need, ctypes.byref(e)) < 0:
         raise HipptError(_err(e, "scene download failed"))
     return out.reshape(-1, _SCENE_WORDS[what])
+
+
+def _env_size(size) -> int:
+    size = int(size)
+    if not 1 <= size <= ENV_MAX_SIZE:
+        raise HipptError(f"environment size must be in 1..{ENV_MAX_SIZE}, not {size}")
+    return size
+
+
+def env_directions(size: int) -> np.ndarray:
+    """hipptEnvDirections: the unit directions (S, S, 3) float32 of the texel centres of an S x S environment
+    map, [y, x] as the texels are indexed (+y up; the upper hemisphere is the inner diamond)."""
+    size = _env_size(size)
+    out = np.zeros((size, size, 3), np.float32)
+    load_library().hipptEnvDirections(size, out.ctypes.data)
+    return out
+
+
+def env_from_equirect(img, size: int) -> np.ndarray:
+    """hipptEnvFromEquirect: the (S, S, 3) float32 environment map of a lat-long image (H, W, 3) float32 (row 0
+    at +y), sampled bilinearly, in double, at the texel-centre directions; no prefilter."""
+    size = _env_size(size)
+    img = np.ascontiguousarray(img, np.float32)
+    if img.ndim != 3 or img.shape[2] != 3 or img.shape[0] < 1 or img.shape[1] < 1:
+        raise HipptError(f"the image must have shape (H, W, 3), not {img.shape}")
+    out = np.zeros((size, size, 3), np.float32)
+    e = ctypes.c_char_p()
+    if not load_library().hipptEnvFromEquirect(img.ctypes.data, int(img.shape[1]), int(img.shape[0]), size,
+                                               out.ctypes.data, ctypes.byref(e)):
+        raise HipptError(_err(e, "environment resampling failed"))
+    return out
+
+
+def env_lookup(dirs) -> np.ndarray:
+    """hipptEnvLookup: env(d) of the library's host copy of the environment for directions (..., 3) float32 of any
+    length, by the text the kernels compile; float32, the shape of `dirs`.  Raises without an environment."""
+    d = np.ascontiguousarray(dirs, np.float32)
+    if d.ndim < 1 or d.shape[-1] != 3:
+        raise HipptError(f"directions must have shape (..., 3), not {d.shape}")
+    out = np.zeros(d.shape, np.float32)
+    e = ctypes.c_char_p()
+    if not load_library().hipptEnvLookup(d.ctypes.data, d.size // 3, out.ctypes.data, ctypes.byref(e)):
+        raise HipptError(_err(e, "environment lookup failed"))
+    return out
 
 
 def read_mesh(path: str):
@@ -657,6 +712,52 @@ class PathTracer:
             ok = self._lib.hipptUpdateVertices(v.ctypes.data, int(v.shape[0]), 0, ctypes.byref(e))
         if not ok:
             raise HipptError(_err(e, "vertex update failed"))
+
+    def setEnvironment(self, texels) -> None:  # noqa: N802
+        """hipptSetEnvironment: an (S, S, 3) float32 octahedral environment map (texels[y, x]; finite, >= 0, may
+        exceed 1; env_directions(S) gives the texels' directions, env_from_equirect a map from a lat-long image)
+        in place of the sky gradient for every uploaded scene, in stream order: renders and path queries
+        enqueued later see it.  None removes it.  It stays across uploads and initialize() until removed.  A
+        numpy array is validated and copied before the call returns; a tensor on the ROCm device is fetched
+        from where it is, uninspected, after torch's current stream is synchronised."""
+        e = ctypes.c_char_p()
+        if texels is None:
+            ok = self._lib.hipptSetEnvironment(None, 0, 0, ctypes.byref(e))
+        else:
+            dev = _is_tensor(texels) and texels.device.type != "cpu"
+            if _is_tensor(texels):
+                import torch
+                if texels.dtype != torch.float32:
+                    raise HipptError(f"texels must be float32, not {texels.dtype}")
+                if not texels.is_contiguous():
+                    raise HipptError("texels must be contiguous")
+                if not dev:
+                    texels = texels.numpy()
+            elif not isinstance(texels, np.ndarray):
+                raise HipptError("texels must be a numpy array or a torch tensor")
+            elif texels.dtype != np.float32:
+                raise HipptError(f"texels must be float32, not {texels.dtype}")
+            elif not texels.flags["C_CONTIGUOUS"]:
+                raise HipptError("texels must be contiguous")
+            shape = tuple(texels.shape)
+            if len(shape) != 3 or shape[0] != shape[1] or shape[2] != 3:
+                raise HipptError(f"texels must have shape (S, S, 3), not {shape}")
+            if dev:
+                import torch
+                torch.cuda.current_stream(texels.device).synchronize()
+                ok = self._lib.hipptSetEnvironment(texels.data_ptr(), int(shape[0]), ENV_DEVICE, ctypes.byref(e))
+            else:
+                ok = self._lib.hipptSetEnvironment(texels.ctypes.data, int(shape[0]), 0, ctypes.byref(e))
+        if not ok:
+            raise HipptError(_err(e, "setting the environment failed"))
+
+    def environment(self) -> Optional[np.ndarray]:
+        """The environment as context 0 holds it after the queued work, (S, S, 3) float32; None without one."""
+        t = scene_download(SCENE_ENVIRONMENT)
+        if t.size == 0:
+            return None
+        size = int(round(t.shape[0] ** 0.5))
+        return np.ascontiguousarray(t.view(np.float32).reshape(size, size, 4)[:, :, :3])
 
     def lightTable(self) -> np.ndarray:  # noqa: N802
         """The light selection table as the device built it (include/hippt.h HIPPT_OPT_LIGHT_SELECT), after the

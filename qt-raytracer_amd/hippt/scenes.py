@@ -346,6 +346,33 @@ def cornell_lamps(base: str = "cornell34", small: int = 240, sphere: bool = True
     return sc
 
 
+def env_texel_directions(size: int) -> np.ndarray:
+    """The unit directions (S, S, 3) float64 of the texel centres of an S x S octahedral environment map
+    (include/hippt.h hipptSetEnvironment), [y, x]; hippt.env_directions is the library's own, in float32."""
+    c = (2.0 * np.arange(size, dtype=np.float64) + 1.0) / size - 1.0
+    u, w = np.meshgrid(c, c)  # u along x, w along y
+    dy = 1.0 - np.abs(u) - np.abs(w)
+    low = dy < 0
+    dx = np.where(low, (1.0 - np.abs(w)) * np.where(u < 0, -1.0, 1.0), u)
+    dz = np.where(low, (1.0 - np.abs(u)) * np.where(w < 0, -1.0, 1.0), w)
+    d = np.stack([dx, dy, dz], axis=-1)
+    return d / np.linalg.norm(d, axis=-1, keepdims=True)
+
+
+def sun_sky(size: int = 256, sun_dir=(0.35, 0.8, 0.45), sun_radiance: float = 60.0, sun_cos: float = 0.995,
+            zenith=(0.25, 0.45, 1.0), horizon=(0.9, 0.9, 0.95), ground=(0.18, 0.16, 0.14)) -> np.ndarray:
+    """A procedural environment (S, S, 3) float32 for PathTracer.setEnvironment: a zenith-to-horizon gradient
+    over a dim ground, plus a disc of `sun_radiance` (white) within acos(sun_cos) of `sun_dir`."""
+    d = env_texel_directions(size)
+    up = np.clip(d[..., 1], 0.0, 1.0)[..., None]
+    sky = (1.0 - up) * np.asarray(horizon, np.float64) + up * np.asarray(zenith, np.float64)
+    e = np.where(d[..., 1:2] >= 0.0, sky, np.asarray(ground, np.float64))
+    s = np.asarray(sun_dir, np.float64)
+    s = s / np.linalg.norm(s)
+    e = e + np.where((d @ s)[..., None] >= sun_cos, float(sun_radiance), 0.0)
+    return np.ascontiguousarray(e, np.float32)
+
+
 SCENES = {"cornell34": cornell34, "blob70k": blob70k, "random_scene": random_scene, "cornell_mixed": cornell_mixed}
 
 

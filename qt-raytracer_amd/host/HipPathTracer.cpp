@@ -103,6 +103,16 @@ bool HipPathTracer::updateVertices(const std::vector<float> &verts) {
     return true;
 }
 
+bool HipPathTracer::setEnvironment(const std::vector<float> &texels, int size) {
+    if (size < 0 || texels.size() != size_t(size) * size_t(size) * 3) {
+        m_lastError = "an environment needs size*size*3 floats";
+        return false;
+    }
+    const char *err = nullptr;
+    if (!hipptSetEnvironment(size ? texels.data() : nullptr, size, 0, &err)) return fail(err, "setting the environment failed");
+    return true;
+}
+
 bool HipPathTracer::renderFrames(int samplesPerFrame, int maxDepth) {
     const char *err = nullptr;
     const unsigned int *pixels = nullptr;

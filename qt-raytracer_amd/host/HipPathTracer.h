@@ -45,6 +45,9 @@ public:
     // scene, in place and in stream order: the frames rendered next show them; nothing queued is
     // drained.  The BVH is refitted, not rebuilt (hipptUpdateVertices): uploadScene is the rebuild.
     bool updateVertices(const std::vector<float> &verts);
+    // hipptSetEnvironment: an octahedral environment map of size x size rgb texels (size*size*3 floats) in place
+    // of the sky gradient for every uploaded scene, in stream order; an empty vector with size 0 removes it.
+    bool setEnvironment(const std::vector<float> &texels, int size);
     // samplesPerFrame frames in one call (GpuPathTracer::renderFrame(spp, depth) shape).
     bool renderFrames(int samplesPerFrame, int maxDepth);
     // Enqueue frames + copy to a hand-off frame; latestFrame() never blocks.

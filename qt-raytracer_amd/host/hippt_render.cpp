@@ -6,7 +6,7 @@
 //                [--emit NAME=r,g,b[;NAME=r,g,b...]] [--width W] [--height H] [--spp N] [--depth D] [--per-frame] [--present]
 //                [--out FILE] [--ppm FILE.ppm] [--pick X,Y] [--denoise PASSES]
 //                [--radiance-in FILE|camera --radiance-out FILE] [--light-sampling] [--mis]
-//                [--light-select power|uniform]
+//                [--light-select power|uniform] [--background r,g,b | --env FILE.pfm [--env-size N]]
 //
 // --backend cuda (default): HipPathTracer, the CudaPathTracer interface.  Without --mesh: the
 // reference kernel's built-in 4-sphere scene, one renderFrame per frame (the CUDA backend's
@@ -19,6 +19,9 @@
 // the power heuristic); it implies --light-sampling.
 // --light-select power: HIPPT_OPT_LIGHT_SELECT HIPPT_LIGHT_SELECT_POWER (a connection picks its light in proportion
 // to area x emission); uniform (default): over the list.  Meaningful with --light-sampling or --mis; it implies neither.
+// --background r,g,b (with --mesh): a constant environment of that radiance (hipptSetEnvironment, size 1) in place
+// of the sky gradient.  --env FILE.pfm (with --mesh): a lat-long colour PFM (little-endian, rows bottom to top)
+// resampled by hipptEnvFromEquirect to an octahedral map of --env-size texels a side (default 256).
 // --backend vulkan: HipVulkanPathTracer, one renderFrame(depth) per frame (the app's "vulkan"
 // branch, RayTracerFboItem.cpp:576-600).  --backend gl: HipGpuPathTracer, initialize + resize,
 // then renderFrame(N, depth) once (or per frame with --per-frame), as the GL branch calls it.
@@ -45,6 +48,7 @@
 
 #include "HipComputeTracers.h"
 #include "HipPathTracer.h"
+#include "env_io.h"
 
 namespace {
 
@@ -55,7 +59,7 @@ int usage() {
                  "                    [--height H] [--spp N] [--depth D] [--per-frame] [--present] [--out FILE]\n"
                  "                    [--ppm FILE.ppm] [--pick X,Y] [--update-mesh FILE] [--denoise PASSES]\n"
                  "                    [--radiance-in FILE|camera --radiance-out FILE] [--light-sampling] [--mis]\n"
-                 "                    [--light-select power|uniform]\n");
+                 "                    [--light-select power|uniform] [--background r,g,b | --env FILE.pfm [--env-size N]]\n");
     return 2;
 }
 
@@ -77,7 +81,8 @@ std::vector<float> parse_floats(const std::string &s) {
 
 int main(int argc, char **argv) {
     std::string mesh, out, ppm, albedoArg, emitArg, pickArg, updateMesh, radianceIn, radianceOut, backend = "cuda";
-    std::string lightSelect = "uniform";
+    std::string lightSelect = "uniform", background, envFile;
+    int envSize = 256;
     int width = 320, height = 180, spp = 16, depth = 8, denoise = -1;
     bool perFrame = false, present = false, lightSampling = false, mis = false;
     for (int i = 1; i < argc; ++i) {
@@ -105,11 +110,37 @@ int main(int argc, char **argv) {
         else if (a == "--radiance-in") radianceIn = v;
         else if (a == "--radiance-out") radianceOut = v;
         else if (a == "--light-select") lightSelect = v;
+        else if (a == "--background") background = v;
+        else if (a == "--env") envFile = v;
+        else if (a == "--env-size") envSize = std::atoi(v);
         else return usage();
     }
     if (backend != "cuda" && backend != "vulkan" && backend != "gl") return usage();
     if (lightSelect != "power" && lightSelect != "uniform") return usage();
+    if (!background.empty() && !envFile.empty()) return usage();
     HipPathTracer tracer;
+    if (!background.empty()) {
+        const std::vector<float> c = parse_floats(background);
+        if (c.size() != 3 || !tracer.setEnvironment(c, 1)) {
+            std::fprintf(stderr, "hippt_render: --background: %s\n", c.size() != 3 ? "needs r,g,b" : tracer.lastError().c_str());
+            return 1;
+        }
+    }
+    if (!envFile.empty()) {
+        std::vector<float> img;
+        int w = 0, h = 0;
+        std::string msg;
+        if (!hippt::envio::read_pfm(envFile, img, w, h, &msg)) {
+            std::fprintf(stderr, "hippt_render: --env: %s\n", msg.c_str());
+            return 1;
+        }
+        const char *err = nullptr;
+        std::vector<float> texels(envSize > 0 && envSize <= 4096 ? size_t(envSize) * size_t(envSize) * 3 : 0);
+        if (!hipptEnvFromEquirect(img.data(), w, h, envSize, texels.data(), &err) || !tracer.setEnvironment(texels, envSize)) {
+            std::fprintf(stderr, "hippt_render: --env: %s\n", err ? err : tracer.lastError().c_str());
+            return 1;
+        }
+    }
     hipptSetOption(HIPPT_OPT_LIGHT_SELECT, lightSelect == "power" ? HIPPT_LIGHT_SELECT_POWER : 0);
     hipptSetOption(HIPPT_OPT_LIGHT_SAMPLING_MODE, mis ? HIPPT_LIGHT_SAMPLING_MIS : lightSampling ? 1 : 0);
     if (!mesh.empty()) {
