@@ -171,7 +171,11 @@ enum { HIPPT_SCENE_NODES2 = 0, HIPPT_SCENE_NODES4 = 1, HIPPT_SCENE_PRIMS = 2, HI
        /* the environment (hipptSetEnvironment below) as context 0 holds it, whatever scene is current: one
           record of 16 bytes per texel, row-major, row y indexing w: r, g, b as float32 and a zero word; 0
           bytes without one */
-       HIPPT_SCENE_ENVIRONMENT = 5 };
+       HIPPT_SCENE_ENVIRONMENT = 5,
+       /* the environment's selection table (HIPPT_OPT_ENV_SAMPLING below) as context 0's device built it, for
+          a map of S x S texels: S row records of 2 words (m_y, C_y), then S x S texel records of 3 words,
+          row-major (q, c, the bits of k): (2 S + 3 S S) 32-bit words; 0 bytes without an environment */
+       HIPPT_SCENE_ENV_TABLE = 6 };
 long long hipptSceneDownload(int what, void *dst, long long bytes, const char **errorMessage);
 
 /* ---- environment: a settable sky (tests/env_ref.py is the statement of record) ----
@@ -182,7 +186,8 @@ long long hipptSceneDownload(int what, void *dst, long long bytes, const char **
  * d is the direction of the segment that missed, exactly as the path holds it, at any length: the caller's
  * own for segment 0 of hipptTraceRadiance, the camera's or the scatter's otherwise.  Nothing else changes:
  * the segments, the RNG chain, a, the depth rule, emissive hits and their MIS weights.  Only the scatter
- * sample finds the environment; no connection samples it.
+ * sample finds the environment; no connection samples it unless HIPPT_OPT_ENV_SAMPLING (below, beside the
+ * light-sampling rules) is set.
  *
  * The map is a square octahedral image of S x S texels E[y][x] (rgb, float32, finite, >= 0, may exceed 1),
  * 1 <= S <= 4096 (at 4096 the device's 16-byte texels are 256 MiB per context).  +y is up and the upper
@@ -575,6 +580,15 @@ enum {
                                        are rejected.  Takes effect at the next render or hipptTraceRadiance,
                                        without an upload; ignored while the light-sampling mode is 0 or the
                                        scene has no light, and uniform for more than 2^20 - 1 lights */
+    , HIPPT_OPT_ENV_SAMPLING = 40   /* 0 (default): only the scatter sample finds the environment, byte for byte
+                                       and kernel for kernel as before the option existed; 1: every Lambertian
+                                       vertex connects to the map by a table over its texels that the device
+                                       builds behind every hipptSetEnvironment in stream order (the fourth rule
+                                       below).  Other values are rejected.  Takes effect at the next render or
+                                       hipptTraceRadiance, without an upload or a new hipptSetEnvironment.  It
+                                       applies only with an environment set and HIPPT_OPT_LIGHT_SAMPLING_MODE 1
+                                       or 2, and then whether or not the scene holds a light: a scene without
+                                       lights runs the light-sampling route with an empty light list */
 };
 /* Light sampling (HIPPT_OPT_LIGHT_SAMPLING 1; this library's own, as the emissive rule is; tests/nee_ref.py
  * restates it in numpy float32 and the GPU matches that bit for bit).  A path carries
@@ -662,6 +676,56 @@ enum { HIPPT_LIGHT_SELECT_POWER = 1 /* a value of HIPPT_OPT_LIGHT_SELECT */ };
  * kind.  The table is rebuilt on the device from the refitted primitive records after every hipptUpdateVertices,
  * in stream order behind the refit: work enqueued earlier sees the old table, work enqueued later the new one.  A
  * triangle that a device-memory update dropped for a non-finite coordinate has area 0, hence q_j = 0. */
+enum { HIPPT_INFO_ENV_SAMPLING = 111 /* 1 if the last render applied HIPPT_OPT_ENV_SAMPLING, else 0 */ };
+/* Environment sampling (HIPPT_OPT_ENV_SAMPLING 1; tests/envs_ref.py restates it in numpy integers and float32 and
+ * the GPU matches that bit for bit, the table word for word).  It adds a connection to the map to
+ * the three rules above and replaces what a miss after a Lambertian scatter adds.  `fdot`, `rand01`, `hash32`,
+ * `sg` and env(d) are the ones above; each float operation is one float32 operation in the association written.
+ * The table over the map's texels E[y][x], S x S, is made of integers and of maxima, so that no word depends on
+ * the order in which a parallel reduction or scan combines; it has two levels (texels within a row, 12 bits
+ * against the row's heaviest; rows against each other, 16 bits), so that T and every R_y stay within 32 bits at
+ * S = 4096 and a few sun texels are not buried under 2^24 sky texels at the floor of 1:
+ *   uc = float(2x + 1) / float(S) - 1.0f;  wc the same from y                      (the texel's centre)
+ *   dy = (1 - |uc|) - |wc|;  (dx, dz) = dy >= 0 ? (uc, wc) : ((1 - |wc|) * sg(uc), (1 - |uc|) * sg(wc))
+ *   n2 = fdot(d, d);  J = 1.0f / (n2 * sqrtf(n2))        (solid angle per unit of (u, w) area: 1 / |p|^3)
+ *   lum = (E.r + E.g) + E.b;  W = lum * J;  W = (W > 0 and W < +inf) ? W : 0     (NaN, negative, infinite: 0)
+ *   per row y:  Wmax_y = max_x W;  q(x,y) = Wmax_y > 0 ? min(4096, max(1, int((W / Wmax_y) * 4096.0f))) : 1
+ *               c(x,y) = q(0,y) + ... + q(x,y) (uint32, inclusive);  R_y = c(S-1, y)        (S <= R_y <= 2^24)
+ *               V_y = (float(R_y) * 0.000244140625f) * Wmax_y
+ *   over rows:  Vmax = max_y V_y;  flat = not (Vmax > 0 and Vmax < +inf)
+ *               m_y = flat ? 1 : min(65536, max(1, int((V_y / Vmax) * 65536.0f)))
+ *               C_y = m_0 + ... + m_y (uint32, inclusive);  T = C_{S-1}                     (S <= T <= 2^28)
+ *   per texel:  k(x,y) = ((float(m_y) / float(T)) * (float(q) / float(R_y))) * (0.25f * (float(S) * float(S)))
+ * Every texel and every row has at least 1, black ones included (the bilinear lookup lets a black texel's cell
+ * read its lit neighbours), so an all-black map gives a uniform table and there is no T == 0 case.  The
+ * solid-angle density of a direction d drawn this way is k(x,y) * |p|^3, p = d / (|dx| + |dy| + |dz|).
+ *   connection, at a Lambertian vertex after the scatter (thr', faced normal n; nL emissive primitives):
+ *     sel = 1
+ *     if nL > 0:  c0 = rand01(rng); sel = 0.5f; if not c0 < 0.5f: the light connection of the mode and of
+ *       HIPPT_OPT_LIGHT_SELECT as above, with (nl * 2.0f) where nl (float(nLights) or ip_k) stands; done
+ *     rng = hash32(rng);  xr = (uint64(rng) * T) >> 32;    y = the smallest row with C_y > xr
+ *     rng = hash32(rng);  xc = (uint64(rng) * R_y) >> 32;  x = the smallest column with c(x,y) > xc
+ *     a = rand01(rng);  b = rand01(rng);  g2 = 2.0f / float(S)
+ *     u = fmaf(float(x) + a, g2, -1.0f);  w = fmaf(float(y) + b, g2, -1.0f)
+ *     dy = (1 - |u|) - |w|;  (dx, dz) as above from (u, w);  n2 = fdot(d, d);  om = d * (1.0f / sqrtf(n2))
+ *     cosS = fdot(n, om);  pl = (k(x,y) * (n2 * sqrtf(n2))) * sel
+ *     no shadow ray unless cosS > 0 and pl > 0     (the draws are consumed either way)
+ *     g = cosS / (3.14159274f * pl)
+ *     mode 1: Ld = (thr' * env(om)) * g
+ *     mode 2: no shadow ray unless g < +inf;  Ld = (thr' * env(om)) * (g / fmaf(g, g, 1.0f))
+ *     the shadow ray (p, om), tmin 0.001, no tmax: Lacc += Ld iff it has no hit at all; it counts as a segment
+ *     and as a shadow ray.
+ *   The coin is drawn whenever the scene holds a light; the * 2.0f also enters the MIS weight of a light hit.
+ *   a segment of direction d, as the path holds it, that misses:
+ *     no Lambertian scatter before it (mode 1: spec; mode 2: cb < 0):  L = Lacc + thr * env(d)
+ *     mode 1, after a Lambertian scatter:  L = Lacc                     (the connection counted it)
+ *     mode 2, after a Lambertian scatter:  L = Lacc + (thr * env(d)) * wb, wb = 1 unless
+ *       s1 = (|dx| + |dy|) + |dz|;  r = sqrtf(fdot(d, d)) / s1;  r3 = (r * r) * r
+ *       (u, w) = env(d)'s own octahedral coordinates (fold included);  h = 0.5f * float(S)
+ *       x = int(fminf(fmaxf(fmaf(u, h, h), 0.0f), float(S - 1)));  y the same from w
+ *       pl = (k(x,y) * r3) * sel;  cb > 0 and pl > 0: gh = cb / (3.14159274f * pl); s = gh * gh;
+ *       s < +inf: wb = s / fmaf(gh, gh, 1.0f)
+ * Depth, absorption, a, emissive hits and the segment counts are the rules' above. */
 /* Records of the chained runs closed since the last call (HIPPT_OPT_CHAIN_AUDIT), as 32-bit words:
  * per run a 16-word header  [0] 0xC4A1D17 [1] run id [2] device [3] batch 0's first frame [4] frames
  * from one batch to the next (-1: one batch) [5] frames per batch [6] band pixels [7] items per batch

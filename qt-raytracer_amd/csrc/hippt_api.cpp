@@ -106,6 +106,7 @@ struct OccKey {
     int variant = 0;  // ray-per-lane launches: the QueryMode, or a path kernel's route (kVariantPath ...)
     bool select = false;  // a light-sampling route's kernel with the selection table (HIPPT_OPT_LIGHT_SELECT)
     bool env = false;     // a path kernel's ENV variant (hipptSetEnvironment)
+    bool envs = false;    // its ENVS variant (HIPPT_OPT_ENV_SAMPLING)
 };
 // The path kernel's routes as OccKey variants, after the QueryModes: plain paths, light-sampled path
 // queries, the light-sampling render route.
@@ -115,7 +116,7 @@ constexpr int kVariantEnvRender = 13;  // plain paths from the camera start: the
 bool same_key(const OccKey &a, const OccKey &b) {
     return a.version == b.version && a.stackDepth == b.stackDepth && a.fmt == b.fmt && a.poolWords == b.poolWords &&
            a.topBytes == b.topBytes && a.ldsScene == b.ldsScene && a.full == b.full && a.spills == b.spills &&
-           a.variant == b.variant && a.select == b.select && a.env == b.env;
+           a.variant == b.variant && a.select == b.select && a.env == b.env && a.envs == b.envs;
 }
 
 // Run costs computed on a detached host thread (HIPPT_OPT_ITEM_ORDER automatic).  The thread owns a
@@ -285,6 +286,9 @@ struct Ctx {
     hippt::env::Texel *env = nullptr;
     int envSize = 0;
     unsigned envRev = 0;
+    // Its selection table (HIPPT_OPT_ENV_SAMPLING; hippt_refit.h env_table_buffers), allocated and freed with
+    // `env` and built on the stream behind every copy into it, whatever the option says.
+    unsigned *envTable = nullptr;
     // Denoiser (hipptDenoise, hippt_denoise.h): one buffer of 80 bytes per pixel (the guide sample's hit
     // records, two colour buffers, the guide), allocated at first use, reused while large enough and
     // freed with the context; the stages' timing events (HIPPT_OPT_DENOISE_TIMING), created on use.
@@ -368,6 +372,8 @@ struct State {
     int activeLightSampling = 0;        // the mode of the light-sampling route if the last render took it (HIPPT_INFO_LIGHT_SAMPLING)
     int lightSelect = 0;                // HIPPT_OPT_LIGHT_SELECT: 0 uniform, HIPPT_LIGHT_SELECT_POWER
     int activeLightSelect = 0;          // as the last light-sampling render applied it (HIPPT_INFO_LIGHT_SELECT)
+    int envSampling = 0;                // HIPPT_OPT_ENV_SAMPLING
+    int activeEnvSampling = 0;          // whether the last render applied it (HIPPT_INFO_ENV_SAMPLING)
     // hipptSetEnvironment: the host copy (envSize x envSize texels in the device layout; empty: the sky
     // gradient), its revision (a context whose envRev differs has yet to receive it), the size the last
     // render applied (HIPPT_INFO_ENVIRONMENT), and the pinned staging buffers of uploads that may still be
@@ -841,6 +847,7 @@ void destroy_ctx(Ctx &c, bool keep) {
     if (c.qDone) (void)hipEventDestroy(c.qDone);
     (void)hipFree(c.dnBuf);
     (void)hipFree(c.env);
+    (void)hipFree(c.envTable);
     for (hipEvent_t e : c.dnEv) (void)hipEventDestroy(e);
     (void)hipHostFree(c.wfHost);
     for (hipEvent_t e : c.wfPoll)
@@ -1821,11 +1828,19 @@ bool enqueue_sphere4(Ctx &c, int firstFrame, int count, int maxDepth, bool copy,
     return TIMED_LAUNCH(c, 0, hippt::launch_sphere4(p, c.stream));
 }
 
-// HIPPT_OPT_LIGHT_SAMPLING_MODE as applied: its value (1, or 2 with MIS) if the scene holds an emissive primitive,
-// else 0 (the option-off code runs).
+// HIPPT_OPT_ENV_SAMPLING as applied: 1 for an uploaded scene under an environment with a light-sampling mode set,
+// whether or not the scene holds a light; else 0 (the option-off code runs).
+int env_sampling_applies() {
+    const State &s = S();
+    return s.scene.kind == HIPPT_SCENE_MESH && s.envSize && s.lightSampling ? s.envSampling : 0;
+}
+
+// HIPPT_OPT_LIGHT_SAMPLING_MODE as applied: its value (1, or 2 with MIS) if the scene holds an emissive primitive
+// or the environment is sampled (the light-sampling route with an empty light list), else 0 (the option-off
+// code runs).
 int light_sampling_applies() {
     const State &s = S();
-    return s.scene.kind == HIPPT_SCENE_MESH && !s.scene.lights.empty() ? s.lightSampling : 0;
+    return s.scene.kind == HIPPT_SCENE_MESH && (!s.scene.lights.empty() || env_sampling_applies()) ? s.lightSampling : 0;
 }
 
 // HIPPT_OPT_LIGHT_SELECT as applied: its value where light sampling applies and the scene's lights have a
@@ -1893,9 +1908,17 @@ bool upload_env(Ctx &c, const char **err) {
     if (c.envSize != s.envSize) {
         HIP_TRY(hipStreamSynchronize(c.stream));
         (void)hipFree(c.env);
+        (void)hipFree(c.envTable);
         c.env = nullptr;
+        c.envTable = nullptr;
         c.envSize = 0;
         HIP_TRY(hipMalloc(&c.env, bytes));
+        if (hipMalloc(&c.envTable, hippt::env_table_words(size_t(s.envSize)) * sizeof(unsigned)) != hipSuccess) {
+            (void)hipFree(c.env);
+            c.env = nullptr;
+            c.envTable = nullptr;
+            return fail(err, "hipMalloc(&c.envTable, ...) failed");
+        }
         c.envSize = s.envSize;
     }
     // the staging buffer of this revision, or a free one filled now; other free ones beyond one go
@@ -1934,6 +1957,8 @@ bool upload_env(Ctx &c, const char **err) {
     HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     st->busy.push_back({c.device, ev});
     HIP_TRY(hipEventRecord(ev, c.stream));
+    // the selection table follows the new texels, behind the copy on the same stream
+    HIP_TRY(hippt::launch_env_table(hippt::env_table_buffers(c.env, c.envTable, c.envSize), c.stream));
     c.envRev = s.envRev;
     return true;
 }
@@ -1943,6 +1968,10 @@ void set_env(const Ctx &c, hippt::PathParams &p) {
     if (!env_applies()) return;
     p.env = c.env;
     p.envSize = c.envSize;
+    if (!env_sampling_applies() || !p.lightMode) return;
+    const hippt::EnvTableBuffers t = hippt::env_table_buffers(c.env, c.envTable, c.envSize);
+    p.envRowC = t.rowC;
+    p.envTexels = t.texels;
 }
 
 // A mesh call's batches on a context: as many frames per batch as the sample scratch budget
@@ -2086,6 +2115,7 @@ bool enqueue_mesh(Ctx &c, const CameraF &cam, int firstFrame, int count, int max
     s.activeLightSampling = 0;
     s.activeLightSelect = 0;
     s.activeEnv = 0;
+    s.activeEnvSampling = 0;
     if (const int mode = light_sampling_applies(); maxDepth > 0 && (mode || env_applies()))
         return enqueue_mesh_lights(c, cam, firstFrame, count, maxDepth, mode, err);
     const unsigned bandPixels = unsigned(c.rows) * unsigned(s.width);
@@ -2381,10 +2411,11 @@ bool ensure_ray_launch(Ctx &c, RayLaunch &r, const plan::Layout &L, int variant,
     occKey.variant = variant;
     occKey.select = select;
     occKey.env = envOn;
+    occKey.envs = envOn && lit && env_sampling_applies();
     if (!same_key(r.occKey, occKey)) {
         // (the pointers select the kernel: any non-null scratch the render route's)
         const bool render = variant == kVariantLitRender || variant == kVariantMisRender || variant == kVariantEnvRender;
-        hippt::PathParams pp{q, c.mats, nullptr, nullptr, nullptr, 1, lit ? c.lights : nullptr, 1,
+        hippt::PathParams pp{q, c.mats, nullptr, nullptr, nullptr, 1, lit ? c.lights : nullptr, lit && c.lights ? 1 : 0,
                              variant == kVariantMisPath || variant == kVariantMisRender ? 2 : 1,
                              render ? reinterpret_cast<float *>(c.stats) : nullptr, nullptr};
         if (select) set_light_select(c, pp);
@@ -2438,6 +2469,7 @@ bool enqueue_mesh_lights(Ctx &c, const CameraF &cam, int firstFrame, int count, 
     set_light_select(c, np);
     set_env(c, np);
     s.activeEnv = np.envSize;
+    s.activeEnvSampling = np.envRowC ? 1 : 0;
     s.activeLightSelect = np.lightCdf ? light_select_applies() : 0;
     s.activeWidth = L.wide ? 4 : 2;
     s.activeTopBytes = L.topBytes;
@@ -3143,6 +3175,38 @@ extern "C" long long hipptSceneDownload(int what, void *dst, long long bytes, co
                 }
                 return (long long)envBytes;
             }
+            if (what == HIPPT_SCENE_ENV_TABLE) {  // rows (m, C), then texels (q, c, bits of k): include/hippt.h
+                const size_t n = size_t(s.envSize);
+                const size_t tabBytes = (2 * n + 3 * n * n) * sizeof(unsigned);
+                if (!tabBytes || !dst) return (long long)tabBytes;
+                if (bytes < (long long)tabBytes) return bad("scene download: destination too small");
+                if (!s.ready || s.ctxs.empty()) return bad("scene download: HIP path tracer not initialized");
+                Ctx &c = s.ctxs[0];
+                if (!upload_env(c, err)) return -1;
+                std::vector<unsigned> dev(hippt::env_table_words(n));
+                if (hipSetDevice(c.device) != hipSuccess ||
+                    hipMemcpyAsync(dev.data(), c.envTable, dev.size() * sizeof(unsigned), hipMemcpyDeviceToHost, c.stream) !=
+                        hipSuccess ||
+                    hipStreamSynchronize(c.stream) != hipSuccess) {
+                    (void)hipGetLastError();
+                    return bad("scene download: copy failed");
+                }
+                unsigned *out = static_cast<unsigned *>(dst);
+                const unsigned *tex = dev.data(), *rowC = tex + 2 * n * n, *rowM = rowC + n;
+                for (size_t y = 0; y < n; ++y) {
+                    out[2 * y] = rowM[y];
+                    out[2 * y + 1] = rowC[y];
+                }
+                out += 2 * n;
+                for (size_t y = 0; y < n; ++y)
+                    for (size_t x = 0; x < n; ++x) {
+                        const size_t i = y * n + x;
+                        out[3 * i] = tex[2 * i] - (x ? tex[2 * (i - 1)] : 0u);
+                        out[3 * i + 1] = tex[2 * i];
+                        out[3 * i + 2] = tex[2 * i + 1];
+                    }
+                return (long long)tabBytes;
+            }
             if (s.scene.kind != HIPPT_SCENE_MESH) return bad("scene download: no mesh scene");
             const SceneHost &sc = s.scene;
             size_t need = 0;
@@ -3754,6 +3818,10 @@ bool set_option_locked(int key, long long value) {
         if (value != 0 && value != HIPPT_LIGHT_SELECT_POWER) return false;
         s.lightSelect = int(value);
         return true;
+    case HIPPT_OPT_ENV_SAMPLING:
+        if (value != 0 && value != 1) return false;
+        s.envSampling = int(value);
+        return true;
     default: return false;
     }
 }
@@ -3820,6 +3888,8 @@ long long get_option_locked(int key) {
     case HIPPT_OPT_LIGHT_SELECT: return s.lightSelect;
     case HIPPT_INFO_LIGHT_SELECT: return s.activeLightSelect;
     case HIPPT_INFO_ENVIRONMENT: return s.activeEnv;
+    case HIPPT_OPT_ENV_SAMPLING: return s.envSampling;
+    case HIPPT_INFO_ENV_SAMPLING: return s.activeEnvSampling;
     case HIPPT_INFO_SKY_RECT_PIXELS: return s.activeSkyPixels;
     case HIPPT_INFO_UPDATE_DROPPED:
         // the last update's count, from the first context that ran it (every context counts the same)

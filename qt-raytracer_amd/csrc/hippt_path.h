@@ -29,6 +29,10 @@ namespace hippt {
 // (hippt_env.h) in place of the sky gradient, from the general kernels (as with `lights`, whatever q.full
 // says), and `scratch` may be set without `lights`: a render batch of plain paths.  Null: the bytes of before,
 // from the kernels of before (a compile-time flag again).
+// Environment sampling (HIPPT_OPT_ENV_SAMPLING): with `envRowC` (under `env` and lightMode 1 or 2)
+// every Lambertian vertex connects to the map by its selection table (hippt_refit.h EnvTableBuffers: rowC and
+// texels), or by a fair coin to the map or to a light where the scene has lights; `lights` may then be null with
+// numLights 0 (a scene without lights under a map).  Null: the bytes and the kernels of before (a flag again).
 struct PathParams {
     QueryParams q;
     const float4 *mats;     // MeshParams::mats
@@ -45,6 +49,8 @@ struct PathParams {
     const float *lightIp = nullptr;      // with lightCdf: ip by primitive in leaf order
     const env::Texel *env = nullptr;     // the environment's size x size texels, or null (the sky gradient)
     int envSize = 0;
+    const unsigned *envRowC = nullptr;         // with env and lightMode 1 or 2: C_y of the map's selection table, or null
+    const env::TexelSel *envTexels = nullptr;  // with envRowC: (c, k) per texel
 };
 
 hipError_t launch_path(const PathParams &p, int blocks, hipStream_t s);

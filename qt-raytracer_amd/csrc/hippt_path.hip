@@ -71,7 +71,9 @@ __device__ __forceinline__ float light_area(const float4 *prims, int k, bool sph
 // is its unit direction, (l0, l1, l2) what the light adds if the ray's closest hit is primitive `lk`
 // (leaf order).  The draws are consumed either way.  MIS: the power heuristic's weight against the scatter
 // sample, 1 / (1 + g^2), is in (l0, l1, l2), and a g that is not below +inf makes no shadow ray.
-template <bool MIS, bool SELECT>
+// ENVS (HIPPT_OPT_ENV_SAMPLING): the coin sent this connection to the lights with probability 1/2, so twice the inverse
+// selection probability stands where it stood (exact: a power of two).
+template <bool MIS, bool SELECT, bool ENVS>
 __device__ __forceinline__ bool light_connect(const int *lights, int numLights, const unsigned *cdf, const float *ipPrim,
                                               const float4 *shade, const float4 *prims, const float4 *mats, float px,
                                               float py, float pz, float nx, float ny,
@@ -130,6 +132,7 @@ __device__ __forceinline__ bool light_connect(const int *lights, int numLights, 
     const float cosS = fdot(nx, ny, nz, wx, wy, wz);
     const float sL = fdot(lx, ly, lz, wx, wy, wz);
     const float cosL = sphere ? (flip ? -sL : sL) : fabsf(sL);
+    if (ENVS) nl = nl * 2.0f;
     if (!(cosS > 0.0f) || !(cosL > 0.0f) || !(d2 > 0.0f) || !(area > 0.0f)) return false;
     float g = (((cosS * cosL) * area) * nl) / (3.14159274f * d2);
     if (MIS) {
@@ -145,7 +148,7 @@ __device__ __forceinline__ bool light_connect(const int *lights, int numLights, 
 // MIS: the weight wb of the emission of light `prim`, met at t on the segment r that a Lambertian scatter
 // with cosine cb to its normal started: the scatter's density against light sampling's at that point,
 // squared (the power heuristic); 1 where light sampling could not have produced the point.
-template <bool SELECT>
+template <bool SELECT, bool ENVS>
 __device__ __forceinline__ float light_hit_weight(const Ray &r, float t, int prim, const float4 *shade, const float4 *prims,
                                                   float cb, int numLights, const float *ipPrim) {
     const float4 sh = shade[prim];
@@ -164,7 +167,8 @@ __device__ __forceinline__ float light_hit_weight(const Ray &r, float t, int pri
     const float cosL = fabsf(fdot(nx, ny, nz, r.dx * inv, r.dy * inv, r.dz * inv));
     const float area = light_area(prims, prim, sphere);
     // the inverse of the light's selection probability: the count, or the table's ip (0: never selected)
-    const float nl = SELECT ? ipPrim[prim] : float(numLights);
+    float nl = SELECT ? ipPrim[prim] : float(numLights);
+    if (ENVS) nl = nl * 2.0f;  // (the coin's 1/2)
     float wb = 1.0f;
     if (cb > 0.0f && cosL > 0.0f && d2 > 0.0f && area > 0.0f && (!SELECT || nl > 0.0f)) {
         const float gh = (((cb * cosL) * area) * nl) / (3.14159274f * d2);
@@ -172,6 +176,45 @@ __device__ __forceinline__ float light_hit_weight(const Ray &r, float t, int pri
         if (s < INFINITY) wb = s / fmaf(gh, gh, 1.0f);
     }
     return wb;
+}
+
+// ---- environment sampling (HIPPT_OPT_ENV_SAMPLING; tests/envs_ref.py is the statement of record) ----
+// One connection from a Lambertian vertex (faced normal n, throughput t* after the scatter) to the map: a
+// direction from the selection table (hippt_env.h draw: four draws from `rng`, consumed either way), and whether
+// a shadow ray is to be traced; then (wx, wy, wz) is its unit direction and (l0, l1, l2) what the map adds if the
+// ray has no hit at all.  `sel`: the coin's probability of the map (1 without lights).  MIS as in light_connect.
+template <bool MIS>
+__device__ __forceinline__ bool env_connect(const PathParams &P, float sel, float nx, float ny, float nz, float tr,
+                                            float tg, float tb, uint32_t &rng, float &wx, float &wy, float &wz,
+                                            float &l0, float &l1, float &l2) {
+    const env::Draw d = env::draw(P.envRowC, P.envTexels, P.envSize, rng);
+    wx = d.ox, wy = d.oy, wz = d.oz;
+    float g;
+    if (!env::connect_factor(d, fdot(nx, ny, nz, d.ox, d.oy, d.oz), sel, MIS, g)) return false;
+    float e0, e1, e2;
+    env::lookup(P.env, P.envSize, d.ox, d.oy, d.oz, e0, e1, e2);
+    l0 = (tr * e0) * g;
+    l1 = (tg * e1) * g;
+    l2 = (tb * e2) * g;
+    return true;
+}
+
+// The connection of a Lambertian vertex under ENVS: to the map, or in a scene with lights (LIT; the coin is drawn
+// whenever the scene holds one) by a fair coin to the map or to a light.  lk = -1 marks the map.
+template <bool MIS, bool SELECT, bool LIT>
+__device__ __forceinline__ bool envs_connect(const PathParams &P, const float4 *shade, const float4 *prims, float px,
+                                             float py, float pz, float nx, float ny, float nz, float tr, float tg, float tb,
+                                             uint32_t &rng, unsigned *pc, float &wx, float &wy, float &wz, float &l0,
+                                             float &l1, float &l2, int &lk) {
+    float sel = 1.0f;
+    if (LIT) {
+        sel = 0.5f;
+        if (!(rand01(rng) < 0.5f))
+            return light_connect<MIS, SELECT, true>(P.lights, P.numLights, P.lightCdf, P.lightIp, shade, prims, P.mats, px,
+                                                    py, pz, nx, ny, nz, tr, tg, tb, rng, pc, wx, wy, wz, l0, l1, l2, lk);
+    }
+    lk = -1;
+    return env_connect<MIS>(P, sel, nx, ny, nz, tr, tg, tb, rng, wx, wy, wz, l0, l1, l2);
 }
 
 // LDS_SCENE: the scene copy in LDS (else the tree in global memory, the top of a 4-wide one in LDS);
@@ -195,13 +238,23 @@ __device__ __forceinline__ float light_hit_weight(const Ray &r, float t, int pri
 // gradient, d the missed segment's direction as the path holds it; nothing else changes.  A flag for the
 // reason SELECT is one.  With ENV the camera start serves plain paths too: an environment sends every mesh
 // render down the ray-per-lane route.
-template <bool LDS_SCENE, bool FULL, bool WIDE, bool NEE, bool CAMERA, bool MIS, bool SELECT, bool ENV>
+// ENVS (with NEE and ENV): HIPPT_OPT_ENV_SAMPLING.  A Lambertian vertex connects to the map (env_connect) or, in
+// a scene with lights (LIT, with ENVS: P.numLights > 0), by a fair coin to the map or to a light; lk = -1 marks a
+// connection to the map, visible iff the shadow ray has no hit.  A miss after a Lambertian scatter adds nothing
+// (the connection counted it) or, with MIS, env(d) by the scatter sample's weight.  NEE is then on whether or not
+// the scene holds a light.  LIT is a flag and not a branch on P.numLights: without the light connection the
+// sixteen kernels of a scene without lights, the common case under a sky, take 3 to 6 VGPRs fewer, and six of them
+// stand an occupancy step higher (profiles/env_sampling/regs.txt).
+template <bool LDS_SCENE, bool FULL, bool WIDE, bool NEE, bool CAMERA, bool MIS, bool SELECT, bool ENV, bool ENVS, bool LIT>
 __global__ __launch_bounds__(kMeshBlock) void path_kernel(PathParams P) {
     static_assert(FULL || !NEE, "light sampling has general kernels only");
     static_assert(FULL || !ENV, "the environment has general kernels only");
     static_assert(NEE || ENV || !CAMERA, "the camera start belongs to the ray-per-lane render route");
     static_assert(NEE || !MIS, "the weights belong to light sampling");
     static_assert(NEE || !SELECT, "the light choice belongs to light sampling");
+    static_assert((NEE && ENV) || !ENVS, "environment sampling belongs to light sampling under an environment");
+    static_assert(ENVS || !LIT, "the coin belongs to environment sampling");
+    static_assert(LIT || !ENVS || !SELECT, "the light choice needs lights");
     const QueryParams &Q = P.q;
     const Staged sc = stage_scene<LDS_SCENE, WIDE>(Q.nodes, Q.tris, Q.numNodes, Q.numTris, Q.stackDepth, Q.topBytes);
     const SpillArea S = lane_spill(Q.spill, Q.spillCap, Q.stackCap);
@@ -266,7 +319,7 @@ __global__ __launch_bounds__(kMeshBlock) void path_kernel(PathParams P) {
                     shadow = false;
                 }
                 // begin_query_ray, with the mark of hipptTraceRays' invalid rays (no segment, (0, 0, 0, 0))
-                // in its branch: set after it, the mark costs path_kernel<false, false, false, false, false, false, false, false>
+                // in its branch: set after it, the mark costs path_kernel<false, false, false, false, false, false, false, false, false, false>
                 // 2 VGPRs
                 begin(T);
                 T.bestO = -1;  // a hit at exactly t == tmax loses the tie on the id: tmax is exclusive
@@ -300,7 +353,7 @@ __global__ __launch_bounds__(kMeshBlock) void path_kernel(PathParams P) {
             if (NEE && shadow) {  // the shadow segment: visible iff its closest hit is the light itself
                 ++nseg;
                 if (CAMERA) ++shadowAll;
-                if (T.bestI == lk) {
+                if (ENVS && lk < 0 ? T.bestI < 0 : T.bestI == lk) {
                     la0 += ld0;
                     la1 += ld1;
                     la2 += ld2;
@@ -319,6 +372,19 @@ __global__ __launch_bounds__(kMeshBlock) void path_kernel(PathParams P) {
                     L0 = tr * e0;
                     L1 = tg * e1;
                     L2 = tb * e2;
+                    if (ENVS) {  // after a Lambertian scatter: counted by the connection, or weighted against it
+                        if (MIS) {
+                            if (!(cb < 0.0f)) {
+                                const float wb = env::miss_weight(P.envTexels, P.envSize, r.dx, r.dy, r.dz, cb,
+                                                                  LIT ? 0.5f : 1.0f);
+                                L0 *= wb;
+                                L1 *= wb;
+                                L2 *= wb;
+                            }
+                        } else if (!spec) {
+                            L0 = L1 = L2 = 0.0f;
+                        }
+                    }
                 } else {
                     sky(r, tr, tg, tb, L0, L1, L2);
                 }
@@ -334,7 +400,7 @@ __global__ __launch_bounds__(kMeshBlock) void path_kernel(PathParams P) {
                     // scatter sample's weight
                     if (MIS) {
                         if (!(cb < 0.0f)) {
-                            const float wb = light_hit_weight<SELECT>(r, T.bestT, T.bestI, Q.shade, sc.tris, cb,
+                            const float wb = light_hit_weight<SELECT, ENVS>(r, T.bestT, T.bestI, Q.shade, sc.tris, cb,
                                                                       P.numLights, P.lightIp);
                             L0 *= wb;
                             L1 *= wb;
@@ -357,9 +423,12 @@ __global__ __launch_bounds__(kMeshBlock) void path_kernel(PathParams P) {
                                                 rsqrt_rn(fdot(r.dx, r.dy, r.dz, r.dx, r.dy, r.dz));
                             float wx, wy, wz;
                             if (!spec &&
-                                light_connect<MIS, SELECT>(P.lights, P.numLights, P.lightCdf, P.lightIp, Q.shade, sc.tris,
-                                                           P.mats, r.ox, r.oy, r.oz, nx, ny, nz, tr, tg, tb, rng, pc, wx, wy,
-                                                           wz, ld0, ld1, ld2, lk)) {
+                                (ENVS ? envs_connect<MIS, SELECT, LIT>(P, Q.shade, sc.tris, r.ox, r.oy, r.oz, nx, ny, nz, tr, tg,
+                                                                  tb, rng, pc, wx, wy, wz, ld0, ld1, ld2, lk)
+                                      : light_connect<MIS, SELECT, false>(P.lights, P.numLights, P.lightCdf, P.lightIp,
+                                                                          Q.shade, sc.tris, P.mats, r.ox, r.oy, r.oz, nx, ny,
+                                                                          nz, tr, tg, tb, rng, pc, wx, wy, wz, ld0, ld1, ld2,
+                                                                          lk))) {
                                 shadow = true;
                                 sdx = r.dx, sdy = r.dy, sdz = r.dz;
                                 r.dx = wx, r.dy = wy, r.dz = wz;
@@ -411,19 +480,42 @@ using PathFn = void (*)(PathParams);
 template <bool L, bool W, bool E>
 PathFn general_path_fn(const PathParams &p) {
     const bool cam = p.scratch != nullptr;
+    if constexpr (E) {
+        if (p.envRowC) {  // environment sampling: the light-sampling kernels, with or without lights
+            if (p.numLights > 0 && p.lightCdf) {
+                if (p.lightMode == 2)
+                    return cam ? path_kernel<L, true, W, true, true, true, true, true, true, true>
+                               : path_kernel<L, true, W, true, false, true, true, true, true, true>;
+                return cam ? path_kernel<L, true, W, true, true, false, true, true, true, true>
+                           : path_kernel<L, true, W, true, false, false, true, true, true, true>;
+            }
+            if (p.numLights > 0) {
+                if (p.lightMode == 2)
+                    return cam ? path_kernel<L, true, W, true, true, true, false, true, true, true>
+                               : path_kernel<L, true, W, true, false, true, false, true, true, true>;
+                return cam ? path_kernel<L, true, W, true, true, false, false, true, true, true>
+                           : path_kernel<L, true, W, true, false, false, false, true, true, true>;
+            }
+            if (p.lightMode == 2)
+                return cam ? path_kernel<L, true, W, true, true, true, false, true, true, false>
+                           : path_kernel<L, true, W, true, false, true, false, true, true, false>;
+            return cam ? path_kernel<L, true, W, true, true, false, false, true, true, false>
+                       : path_kernel<L, true, W, true, false, false, false, true, true, false>;
+        }
+    }
     if (p.lights && p.lightCdf) {
         if (p.lightMode == 2)
-            return cam ? path_kernel<L, true, W, true, true, true, true, E> : path_kernel<L, true, W, true, false, true, true, E>;
-        return cam ? path_kernel<L, true, W, true, true, false, true, E> : path_kernel<L, true, W, true, false, false, true, E>;
+            return cam ? path_kernel<L, true, W, true, true, true, true, E, false, false> : path_kernel<L, true, W, true, false, true, true, E, false, false>;
+        return cam ? path_kernel<L, true, W, true, true, false, true, E, false, false> : path_kernel<L, true, W, true, false, false, true, E, false, false>;
     }
     if (p.lights && p.lightMode == 2)
-        return cam ? path_kernel<L, true, W, true, true, true, false, E> : path_kernel<L, true, W, true, false, true, false, E>;
+        return cam ? path_kernel<L, true, W, true, true, true, false, E, false, false> : path_kernel<L, true, W, true, false, true, false, E, false, false>;
     if (p.lights)
-        return cam ? path_kernel<L, true, W, true, true, false, false, E> : path_kernel<L, true, W, true, false, false, false, E>;
+        return cam ? path_kernel<L, true, W, true, true, false, false, E, false, false> : path_kernel<L, true, W, true, false, false, false, E, false, false>;
     if constexpr (E) {
-        if (cam) return path_kernel<L, true, W, false, true, false, false, true>;
+        if (cam) return path_kernel<L, true, W, false, true, false, false, true, false, false>;
     }
-    return path_kernel<L, true, W, false, false, false, false, E>;
+    return path_kernel<L, true, W, false, false, false, false, E, false, false>;
 }
 
 PathFn path_fn(const PathParams &p) {
@@ -432,7 +524,7 @@ PathFn path_fn(const PathParams &p) {
     return for_scene_layout(q, [&p](auto lds, auto full, auto wide) -> PathFn {
         constexpr bool L = decltype(lds)::value, F = decltype(full)::value, W = decltype(wide)::value;
         if constexpr (F) return p.env ? general_path_fn<L, W, true>(p) : general_path_fn<L, W, false>(p);
-        return path_kernel<L, F, W, false, false, false, false, false>;
+        return path_kernel<L, F, W, false, false, false, false, false, false, false>;
     });
 }
 
@@ -461,6 +553,10 @@ hipError_t launch_path(const PathParams &p, int blocks, hipStream_t s) {
     if (p.env ? (p.envSize < 1 || p.envSize > env::kMaxSize || reinterpret_cast<uintptr_t>(p.env) % 16) : p.envSize != 0)
         return hipErrorInvalidValue;
     if (p.lightCdf ? (!p.lights || !p.lightIp) : p.lightIp != nullptr) return hipErrorInvalidValue;
+    // environment sampling: the map, a light-sampling mode, and an empty light list where the scene has none
+    if (p.envRowC ? (!p.env || !p.envTexels || p.lightMode < 1 || p.lightMode > 2 || (p.lights ? p.numLights < 1 : p.numLights != 0))
+                  : p.envTexels != nullptr)
+        return hipErrorInvalidValue;
     // a render batch's counters; a query's own pointers: rays and records are read and stored whole
     if (p.scratch ? !p.stats
                   : (!q.rays || !p.seeds || !p.radiance || reinterpret_cast<uintptr_t>(q.rays) % 16 ||

@@ -9,6 +9,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "hippt_env.h"
+
 namespace hippt {
 
 constexpr int kRefitBlock = 256;
@@ -73,5 +75,27 @@ LightTableBuffers light_table_buffers(unsigned *base, int numLights, int numPrim
 // Enqueues one build on `s`: Wmax zeroed, then four launches (weights and Wmax, q and the blocks' scans,
 // one block over the blocks' sums, offsets + ip + scatter).  light_table_fits(numLights).
 hipError_t launch_light_table(const LightTableBuffers &b, hipStream_t s);
+
+// ---- the environment's selection table (include/hippt.h HIPPT_OPT_ENV_SAMPLING) ----------
+// The table's words for a map of size x size texels, as env_table_buffers lays them out in one allocation: 8
+// bytes per texel (c, k), then per row C, m and, between the passes, V.
+constexpr size_t env_table_words(size_t size) { return 2 * size * size + 3 * size; }
+
+// Every pointer is memory of the launch's device.
+struct EnvTableBuffers {
+    const env::Texel *env;  // the map, size x size
+    env::TexelSel *texels;  // size x size: c(x, y) and k(x, y)
+    unsigned *rowC;         // size: C_y, dense for the search (T = rowC[size - 1])
+    unsigned *rowM;         // size: m_y
+    float *rowV;            // size: V_y (between the passes)
+    int size;
+};
+
+// The pointers of a table in `base` (env_table_words(size) words, 8-byte aligned).
+EnvTableBuffers env_table_buffers(const env::Texel *env, unsigned *base, int size);
+
+// Enqueues one build on `s`: three launches (a block per row: W, Wmax, q, c, V; one block over the rows: Vmax,
+// m, C; k per texel).
+hipError_t launch_env_table(const EnvTableBuffers &b, hipStream_t s);
 
 }  // namespace hippt

@@ -12,8 +12,11 @@
 //                 by the previous launch), kept on the side, and the node's box = that moved out once
 //                 by the pad of the update's largest |coordinate| (bvh_builder.h refit_bvh)
 // and, behind them for a scene with lights, the four launches that rebuild the light selection table
-// from the refitted primitive records (HIPPT_OPT_LIGHT_SELECT; below).
+// from the refitted primitive records (HIPPT_OPT_LIGHT_SELECT; below).  The environment's selection table
+// (HIPPT_OPT_ENV_SAMPLING), built behind every hipptSetEnvironment, sits beside it: it shares the block scan.
 #include "hippt_refit.h"
+
+#include <algorithm>
 
 #include "bvh_builder.h"
 #include "hippt_device.h"
@@ -281,7 +284,111 @@ __global__ __launch_bounds__(kRefitBlock) void light_finish(LightTableBuffers B)
     if (have) B.ipPrim[k] = ip;
 }
 
+// ---- the environment's selection table (hippt_refit.h; the rule: include/hippt.h, tests/envs_ref.py) ----
+// Three launches in stream order; the hand-off between them is the kernel boundary.  The per-texel arithmetic
+// is hippt_env.h's.  Every reduction is a maximum of non-negative floats' bits or a sum of integers, so no word
+// depends on the order in which it combines.
+
+// The largest v over the block's kRefitBlock threads, all of which call it.
+__device__ inline unsigned block_max(unsigned v, unsigned *waveMax) {
+    for (int d = 32; d > 0; d >>= 1) v = max(v, unsigned(__shfl_xor(int(v), d)));
+    if ((threadIdx.x & 63u) == 0u) waveMax[threadIdx.x >> 6] = v;
+    __syncthreads();
+    unsigned m = 0u;
+    for (unsigned w = 0; w < unsigned(kRefitBlock) / 64u; ++w) m = max(m, waveMax[w]);
+    __syncthreads();  // (the words may be written again)
+    return m;
+}
+
+// A block per row y, a thread per run of at most 16 texels: Wmax_y, q and c along the row, V_y.
+__global__ __launch_bounds__(kRefitBlock) void env_table_rows(EnvTableBuffers B) {
+    __shared__ unsigned waveWords[kRefitBlock / 64];
+    const int size = B.size, y = int(blockIdx.x);
+    const int per = (size + kRefitBlock - 1) / kRefitBlock;
+    const int first = min(int(threadIdx.x) * per, size), last = min(first + per, size);
+    const env::Texel *in = B.env + size_t(y) * size_t(size);
+    env::TexelSel *out = B.texels + size_t(y) * size_t(size);
+    unsigned maxBits = 0u;
+#pragma unroll 1
+    for (int x = first; x < last; ++x) maxBits = max(maxBits, __float_as_uint(env::texel_weight(in[x], x, y, size)));
+    const float Wmax = f_of(block_max(maxBits, waveWords));
+    unsigned sum = 0u;
+#pragma unroll 1
+    for (int x = first; x < last; ++x) {
+        const unsigned q = env::texel_q(env::texel_weight(in[x], x, y, size), Wmax);
+        out[x].c = q;
+        sum += q;
+    }
+    unsigned total;
+    unsigned at = block_scan(sum, waveWords, total) - sum;
+#pragma unroll 1
+    for (int x = first; x < last; ++x) {
+        at += out[x].c;
+        out[x].c = at;
+    }
+    if (threadIdx.x == 0u) B.rowV[y] = env::row_value(total, Wmax);
+}
+
+// One block over the rows, a thread per run of at most 16: Vmax, m_y, C_y.
+__global__ __launch_bounds__(kRefitBlock) void env_table_scan_rows(EnvTableBuffers B) {
+    __shared__ unsigned waveWords[kRefitBlock / 64];
+    const int size = B.size;
+    const int per = (size + kRefitBlock - 1) / kRefitBlock;
+    const int first = min(int(threadIdx.x) * per, size), last = min(first + per, size);
+    unsigned maxBits = 0u;
+#pragma unroll 1
+    for (int y = first; y < last; ++y) maxBits = max(maxBits, __float_as_uint(B.rowV[y]));
+    const float Vmax = f_of(block_max(maxBits, waveWords));
+    unsigned sum = 0u;
+#pragma unroll 1
+    for (int y = first; y < last; ++y) {
+        const unsigned m = env::row_m(B.rowV[y], Vmax);
+        B.rowM[y] = m;
+        sum += m;
+    }
+    unsigned total;
+    unsigned at = block_scan(sum, waveWords, total) - sum;
+#pragma unroll 1
+    for (int y = first; y < last; ++y) {
+        at += B.rowM[y];
+        B.rowC[y] = at;
+    }
+}
+
+// k(x, y), a lane per texel, grid stride.
+__global__ __launch_bounds__(kRefitBlock) void env_table_finish(EnvTableBuffers B) {
+    const unsigned size = unsigned(B.size), count = size * size;  // (<= 2^24)
+    const unsigned T = B.rowC[size - 1u];
+    for (unsigned i = blockIdx.x * unsigned(kRefitBlock) + threadIdx.x; i < count; i += gridDim.x * unsigned(kRefitBlock)) {
+        const unsigned y = i / size, x = i - y * size;
+        const unsigned c = B.texels[i].c, q = x ? c - B.texels[i - 1u].c : c;
+        B.texels[i].k = env::texel_k(B.rowM[y], T, q, B.texels[size_t(y) * size + size - 1u].c, int(size));
+    }
+}
+
 }  // namespace
+
+EnvTableBuffers env_table_buffers(const env::Texel *env, unsigned *base, int size) {
+    const size_t n = size_t(size);
+    EnvTableBuffers b{};
+    b.env = env;
+    b.texels = reinterpret_cast<env::TexelSel *>(base);
+    b.rowC = base + 2 * n * n;
+    b.rowM = b.rowC + n;
+    b.rowV = reinterpret_cast<float *>(b.rowM + n);
+    b.size = size;
+    return b;
+}
+
+hipError_t launch_env_table(const EnvTableBuffers &b, hipStream_t s) {
+    if (b.size < 1 || b.size > env::kMaxSize || !b.env || !b.texels) return hipErrorInvalidValue;
+    const unsigned count = unsigned(b.size) * unsigned(b.size);
+    const unsigned blocks = std::min(4096u, (count + unsigned(kRefitBlock) - 1u) / unsigned(kRefitBlock));
+    hipLaunchKernelGGL(env_table_rows, dim3(b.size), dim3(kRefitBlock), 0, s, b);
+    hipLaunchKernelGGL(env_table_scan_rows, dim3(1), dim3(kRefitBlock), 0, s, b);
+    hipLaunchKernelGGL(env_table_finish, dim3(blocks), dim3(kRefitBlock), 0, s, b);
+    return hipGetLastError();
+}
 
 LightTableBuffers light_table_buffers(unsigned *base, int numLights, int numPrims) {
     const size_t n = size_t(numLights), p = size_t(numPrims);

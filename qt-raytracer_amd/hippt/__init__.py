@@ -68,6 +68,7 @@ OPT_LIGHT_SAMPLING_MODE = 38  # the same word with all its values: 0, 1 and LIGH
 LIGHT_SAMPLING_MIS = 2  # light sampling with MIS (the power heuristic with the scatter sample)
 OPT_LIGHT_SELECT = 39  # how a connection picks its light: 0 (default) uniformly, LIGHT_SELECT_POWER by area x emission
 LIGHT_SELECT_POWER = 1
+OPT_ENV_SAMPLING = 40  # connect every Lambertian vertex to the environment map by its selection table: 0 (default), 1
 OPT_PIXEL_FORMAT = 25
 PIXEL_ARGB = 0
 PIXEL_RGBA8 = 1
@@ -82,6 +83,7 @@ INFO_LIGHTS = 107  # emissive primitives in the uploaded scene
 INFO_LIGHT_SAMPLING = 108  # OPT_LIGHT_SAMPLING_MODE's value (1 or 2) if the last render took the light-sampling route
 INFO_LIGHT_SELECT = 109  # OPT_LIGHT_SELECT's value if the last render took the light-sampling route and applied it
 INFO_ENVIRONMENT = 110  # the environment's size as the last render applied it (0: the gradient, or the built-in scene)
+INFO_ENV_SAMPLING = 111  # 1 if the last render applied OPT_ENV_SAMPLING
 INFO_DENOISE_NS = 200
 RAYS_DEVICE = 1
 HIT_SPHERE = 1 << 30
@@ -99,6 +101,7 @@ SCENE_PRIMS = 2
 SCENE_SHADE = 3
 SCENE_LIGHTS = 4  # the light selection table: (prim, q, c, bits of ip) per light
 SCENE_ENVIRONMENT = 5  # the environment's texels: (r, g, b, 0) float32 per texel
+SCENE_ENV_TABLE = 6  # the environment's selection table: S rows (m, C), then S x S texels (q, c, bits of k)
 
 # Every symbol include/hippt.h declares (checked by tests/test_abi_cpu.py).
 EXPORTS = (
@@ -391,7 +394,9 @@ def _update_verts(verts):
 
 
 _SCENE_WORDS = {SCENE_NODES2: 16, SCENE_NODES4: 32, SCENE_PRIMS: 12, SCENE_SHADE: 4, SCENE_LIGHTS: 4,
-                SCENE_ENVIRONMENT: 4}
+                SCENE_ENVIRONMENT: 4, SCENE_ENV_TABLE: 1}
+ENV_ROW_DTYPE = np.dtype([("m", "<u4"), ("C", "<u4")])
+ENV_TEXEL_DTYPE = np.dtype([("q", "<u4"), ("c", "<u4"), ("k", "<f4")])
 LIGHT_TABLE_DTYPE = np.dtype([("prim", "<i4"), ("q", "<u4"), ("c", "<u4"), ("ip", "<f4")])
 
 
@@ -758,6 +763,18 @@ class PathTracer:
             return None
         size = int(round(t.shape[0] ** 0.5))
         return np.ascontiguousarray(t.view(np.float32).reshape(size, size, 4)[:, :, :3])
+
+    def envTable(self) -> Optional[dict]:  # noqa: N802
+        """The environment's selection table as the device built it (include/hippt.h HIPPT_OPT_ENV_SAMPLING), after
+        the queued work: {"rows": structured (S,) with m (the row's integer weight) and C (its inclusive sum),
+        "texels": structured (S, S) with q (the texel's integer weight within its row), c (its inclusive sum along
+        the row) and k (float32: the draw's density per unit of (u, w) area)}.  None without an environment."""
+        t = scene_download(SCENE_ENV_TABLE).reshape(-1)
+        if t.size == 0:
+            return None
+        size = int(round((-2 + (4 + 12 * t.size) ** 0.5) / 6))
+        assert 2 * size + 3 * size * size == t.size
+        return {"rows": t[:2 * size].view(ENV_ROW_DTYPE), "texels": t[2 * size:].view(ENV_TEXEL_DTYPE).reshape(size, size)}
 
     def lightTable(self) -> np.ndarray:  # noqa: N802
         """The light selection table as the device built it (include/hippt.h HIPPT_OPT_LIGHT_SELECT), after the

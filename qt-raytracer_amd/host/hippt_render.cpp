@@ -6,7 +6,7 @@
 //                [--emit NAME=r,g,b[;NAME=r,g,b...]] [--width W] [--height H] [--spp N] [--depth D] [--per-frame] [--present]
 //                [--out FILE] [--ppm FILE.ppm] [--pick X,Y] [--denoise PASSES]
 //                [--radiance-in FILE|camera --radiance-out FILE] [--light-sampling] [--mis]
-//                [--light-select power|uniform] [--background r,g,b | --env FILE.pfm [--env-size N]]
+//                [--light-select power|uniform] [--background r,g,b | --env FILE.pfm [--env-size N]] [--env-sampling]
 //
 // --backend cuda (default): HipPathTracer, the CudaPathTracer interface.  Without --mesh: the
 // reference kernel's built-in 4-sphere scene, one renderFrame per frame (the CUDA backend's
@@ -22,6 +22,8 @@
 // --background r,g,b (with --mesh): a constant environment of that radiance (hipptSetEnvironment, size 1) in place
 // of the sky gradient.  --env FILE.pfm (with --mesh): a lat-long colour PFM (little-endian, rows bottom to top)
 // resampled by hipptEnvFromEquirect to an octahedral map of --env-size texels a side (default 256).
+// --env-sampling: HIPPT_OPT_ENV_SAMPLING 1 (every Lambertian vertex connects to the environment map by its selection
+// table).  It needs --env or --background together with --light-sampling or --mis, and implies none of them.
 // --backend vulkan: HipVulkanPathTracer, one renderFrame(depth) per frame (the app's "vulkan"
 // branch, RayTracerFboItem.cpp:576-600).  --backend gl: HipGpuPathTracer, initialize + resize,
 // then renderFrame(N, depth) once (or per frame with --per-frame), as the GL branch calls it.
@@ -59,7 +61,8 @@ int usage() {
                  "                    [--height H] [--spp N] [--depth D] [--per-frame] [--present] [--out FILE]\n"
                  "                    [--ppm FILE.ppm] [--pick X,Y] [--update-mesh FILE] [--denoise PASSES]\n"
                  "                    [--radiance-in FILE|camera --radiance-out FILE] [--light-sampling] [--mis]\n"
-                 "                    [--light-select power|uniform] [--background r,g,b | --env FILE.pfm [--env-size N]]\n");
+                 "                    [--light-select power|uniform] [--background r,g,b | --env FILE.pfm [--env-size N]]\n"
+                 "                    [--env-sampling]\n");
     return 2;
 }
 
@@ -84,7 +87,7 @@ int main(int argc, char **argv) {
     std::string lightSelect = "uniform", background, envFile;
     int envSize = 256;
     int width = 320, height = 180, spp = 16, depth = 8, denoise = -1;
-    bool perFrame = false, present = false, lightSampling = false, mis = false;
+    bool perFrame = false, present = false, lightSampling = false, mis = false, envSampling = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char * { return i + 1 < argc ? argv[++i] : nullptr; };
@@ -93,6 +96,7 @@ int main(int argc, char **argv) {
         else if (a == "--present") present = true;
         else if (a == "--light-sampling") lightSampling = true;
         else if (a == "--mis") mis = true;
+        else if (a == "--env-sampling") envSampling = true;
         else if ((v = next()) == nullptr) return usage();
         else if (a == "--backend") backend = v;
         else if (a == "--mesh") mesh = v;
@@ -118,6 +122,10 @@ int main(int argc, char **argv) {
     if (backend != "cuda" && backend != "vulkan" && backend != "gl") return usage();
     if (lightSelect != "power" && lightSelect != "uniform") return usage();
     if (!background.empty() && !envFile.empty()) return usage();
+    if (envSampling && ((background.empty() && envFile.empty()) || !(lightSampling || mis))) {
+        std::fprintf(stderr, "hippt_render: --env-sampling needs --env or --background together with --light-sampling or --mis\n");
+        return 1;
+    }
     HipPathTracer tracer;
     if (!background.empty()) {
         const std::vector<float> c = parse_floats(background);
@@ -142,6 +150,7 @@ int main(int argc, char **argv) {
         }
     }
     hipptSetOption(HIPPT_OPT_LIGHT_SELECT, lightSelect == "power" ? HIPPT_LIGHT_SELECT_POWER : 0);
+    hipptSetOption(HIPPT_OPT_ENV_SAMPLING, envSampling ? 1 : 0);
     hipptSetOption(HIPPT_OPT_LIGHT_SAMPLING_MODE, mis ? HIPPT_LIGHT_SAMPLING_MIS : lightSampling ? 1 : 0);
     if (!mesh.empty()) {
         // the scene is the library's (shared by every interface)

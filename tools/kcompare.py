@@ -4,9 +4,9 @@ scratch bytes (the .amdhsa_ metadata, as tools/kregs.py) and the instruction cou
 
 usage: python tools/kcompare.py parent.s change.s [pairs.txt]
 
-A kernel of the change whose template arguments end in one more `false` than the parent's (a flag added with that
-default) is compared with the parent's kernel; one that ends in one more `true` is a new variant and is listed
-against the parent's kernel of the other arguments (its twin).  A renamed kernel is paired by pairs.txt: lines of
+A kernel of the change whose template arguments end in one or more `false` beyond the parent's (flags added with
+that default) is compared with the parent's kernel; one whose added arguments hold a `true` is a new variant and is
+listed against the parent's kernel of the other arguments (its twin).  A renamed kernel is paired by pairs.txt: lines of
 "parent-name change-name" (mangled); such pairs are listed with both figures whether or not they differ.
 """
 import re
@@ -57,9 +57,10 @@ def twin(name, parent, told):
     m = re.search(r"I((?:Lb[01]E)+)E", name)
     if m:
         args = m.group(1)
-        base = name.replace(args, args[:-4])
-        if base in parent:
-            return base, args.endswith("Lb1E")
+        for cut in range(4, len(args), 4):  # one flag added, or several
+            base = name.replace(args, args[:-cut])
+            if base in parent:
+                return base, "Lb1E" in args[-cut:]
     return None, True
 
 
