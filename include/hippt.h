@@ -549,6 +549,17 @@ enum {
                                        HIPPT_INFO_SKY_RECT_PIXELS: 0).  Same results either way;
                                        with HIPPT_OPT_COUNT_TRAVERSAL, nodeVisits counts only the traversals
                                        made */
+    , HIPPT_OPT_SKY_COMBINE = 41    /* -1 (default, automatic): a batch that has a sky rectangle (HIPPT_OPT_SKY_RECT)
+                                       and an item order table (HIPPT_OPT_ITEM_ORDER), is neither counted
+                                       (HIPPT_OPT_COUNT_TRAVERSAL) nor audited (HIPPT_OPT_CHAIN_AUDIT) and renders
+                                       under the built-in gradient sky leaves the 64-pixel runs that lie wholly
+                                       outside the rectangle out of its work queues; the combine of that batch
+                                       computes their samples' radiance (a function of pixel, frame and the
+                                       batch's camera) instead of reading it.  0: such runs are finished by the
+                                       tracing kernel, as before the option existed.  Same results and the same
+                                       hipptGetStats counts either way (HIPPT_INFO_SKY_COMBINE: the band pixels of
+                                       the last batch the combine finished, 0 when the mode did not apply).
+                                       Other values are rejected */
     , HIPPT_OPT_DENOISE_TIMING = 36 /* 1: hipptDenoise brackets each of its stages with timing events and keeps
                                        their device times (HIPPT_INFO_DENOISE_NS); 0 (default): no events.
                                        Same results either way (a measuring aid) */
@@ -758,6 +769,8 @@ enum { HIPPT_INFO_LDS_TOP_BYTES = 100, HIPPT_INFO_BLOCKS_PER_CU = 101, HIPPT_INF
                                           for a non-finite coordinate; reading it synchronises */,
        HIPPT_INFO_RENDER_PAD = 105,
        HIPPT_INFO_SKY_RECT_PIXELS = 106,
+       HIPPT_INFO_SKY_COMBINE = 112 /* HIPPT_OPT_SKY_COMBINE as applied: band pixels of the last batch, over all
+                                       devices, whose samples the combine finished (0: none) */,
        /* device time in nanoseconds of stage k of the last hipptDenoise made under
           HIPPT_OPT_DENOISE_TIMING, key HIPPT_INFO_DENOISE_NS + k: 0 the guide query, 1 prepare,
           2..9 passes 0..7, 10 finish (0: the stage did not run) */

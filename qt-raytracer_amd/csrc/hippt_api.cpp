@@ -198,8 +198,18 @@ struct Ctx {
     struct OrderTable {
         int frames;
         unsigned *dev;
+        // HIPPT_OPT_SKY_COMBINE: the table leaves out the skyRuns runs wholly outside skyRect (0: none left out)
+        unsigned skyRuns = 0;
+        hippt::SkyRect skyRect{};
     };
     std::vector<OrderTable> orderTables;  // most recently used first, at most kOrderTables
+    struct SkyFlags {  // item_order.h sky_runs of the last rectangle asked for (ensure_order)
+        bool valid = false;
+        int width = 0, rows = 0, y0 = 0, stride = 0;
+        unsigned tileShift = 6, count = 0;
+        hippt::SkyRect rect{};
+        std::vector<uint8_t> flags;
+    } skyFlags;
     struct RetiredTable {
         unsigned *dev;
         hipEvent_t done;  // recorded on the stream after the last launch that may read it
@@ -258,6 +268,8 @@ struct Ctx {
     unsigned long long *chainBoxDev = nullptr;  // its device address
     // pixel samples of chained batches (their kernels do not count them: every item is one sample)
     unsigned long long hostSamples = 0;
+    long long skyCombinePixels = 0;  // HIPPT_INFO_SKY_COMBINE: this context's share of the last batch
+    unsigned long long hostSegments = 0;  // segments of the samples a combine finishes (HIPPT_OPT_SKY_COMBINE)
     std::vector<EventPair> pool;                         // every timing event pair created
     std::vector<EventPair> freeEv;                       // pairs not in flight
     std::vector<std::pair<int, EventPair>> pending;      // (0 trace / 1 combine, events)
@@ -1054,8 +1066,12 @@ constexpr size_t kOrderTables = 4;
 
 int cost_threads() { return int(std::max(1u, std::min(16u, std::thread::hardware_concurrency()))); }
 
+// skyOmit (HIPPT_OPT_SKY_COMBINE): the batch's sky rectangle when its table is to leave out the runs
+// wholly outside it; *skyRuns: how many runs per frame the table left out (0: none, the mode is off).
 bool ensure_order(Ctx &c, const CameraF &cam, int frames, int maxDepth, bool forced, unsigned tileShift,
-                  const unsigned **table, const char **err) {
+                  const unsigned **table, const char **err, const hippt::SkyRect *skyOmit = nullptr,
+                  unsigned *skyRuns = nullptr) {
+    if (skyRuns) *skyRuns = 0;
     State &s = S();
     *table = nullptr;
     OrderKey key;
@@ -1129,15 +1145,40 @@ bool ensure_order(Ctx &c, const CameraF &cam, int frames, int maxDepth, bool for
         c.runCostsValid = true;
     }
     if (c.runCosts.empty()) return true;  // no estimate for this key (its job failed): image order
+    const hippt::RunLayout layout{unsigned(s.width), unsigned(c.rows), c.orderKey.tileShift};
+    // the runs' flags for this rectangle: kept with their key (the cost key's layout and rows, and the rectangle),
+    // so that a batch whose table is cached pays a comparison, not a pass over the runs
+    if (skyOmit) {
+        Ctx::SkyFlags &f = c.skyFlags;
+        const bool same = f.valid && f.width == s.width && f.rows == c.rows && f.y0 == c.y0 && f.stride == c.stride &&
+                          f.tileShift == layout.tileShift && f.rect.x0 == skyOmit->x0 && f.rect.y0 == skyOmit->y0 &&
+                          f.rect.x1 == skyOmit->x1 && f.rect.y1 == skyOmit->y1;
+        if (!same) {
+            f.count = unsigned(hippt::sky_runs(layout, c.y0, c.stride,
+                                               hippt::skyrect::Rect{skyOmit->x0, skyOmit->y0, skyOmit->x1, skyOmit->y1},
+                                               f.flags));
+            f.width = s.width, f.rows = c.rows, f.y0 = c.y0, f.stride = c.stride, f.tileShift = layout.tileShift;
+            f.rect = *skyOmit;
+            f.valid = true;
+        }
+    }
+    const std::vector<uint8_t> &sky = c.skyFlags.flags;
+    unsigned omitted = skyOmit ? c.skyFlags.count : 0u;
+    if (omitted >= c.runCosts.size()) omitted = 0;  // (nothing left to trace: the table keeps every run)
+    auto same_omit = [&](const Ctx::OrderTable &t) {
+        return t.skyRuns == omitted &&
+               (!omitted || (t.skyRect.x0 == skyOmit->x0 && t.skyRect.y0 == skyOmit->y0 && t.skyRect.x1 == skyOmit->x1 &&
+                             t.skyRect.y1 == skyOmit->y1));
+    };
+    if (skyRuns) *skyRuns = omitted;
     for (size_t k = 0; k < c.orderTables.size(); ++k)
-        if (c.orderTables[k].frames == frames) {
+        if (c.orderTables[k].frames == frames && same_omit(c.orderTables[k])) {
             std::rotate(c.orderTables.begin(), c.orderTables.begin() + k, c.orderTables.begin() + k + 1);
             *table = c.orderTables.front().dev;
             return true;
         }
     std::vector<uint32_t> order;
-    hippt::build_item_table(c.runCosts, hippt::RunLayout{unsigned(s.width), unsigned(c.rows), c.orderKey.tileShift},
-                            unsigned(frames), hippt::kMeshQueues, order);
+    hippt::build_item_table(c.runCosts, layout, unsigned(frames), hippt::kMeshQueues, order, omitted ? &sky : nullptr);
     unsigned *dev = nullptr;
     HIP_TRY(hipMalloc(&dev, std::max<size_t>(1, order.size()) * sizeof(unsigned)));
     // a fresh buffer: the copy need not wait for the launches queued on the context's stream
@@ -1151,7 +1192,8 @@ bool ensure_order(Ctx &c, const CameraF &cam, int frames, int maxDepth, bool for
         retire_table(c, c.orderTables.back().dev);
         c.orderTables.pop_back();
     }
-    c.orderTables.insert(c.orderTables.begin(), Ctx::OrderTable{frames, dev});
+    c.orderTables.insert(c.orderTables.begin(),
+                         Ctx::OrderTable{frames, dev, omitted, omitted ? *skyOmit : hippt::SkyRect{}});
     *table = dev;
     return true;
 }
@@ -1618,7 +1660,7 @@ bool chain_same(const hippt::MeshParams &a, const hippt::MeshParams &b) {
            a.runCount == b.runCount && a.runTileShift == b.runTileShift && a.rngTable == b.rngTable && a.poolOffset == b.poolOffset &&
            a.poolWords == b.poolWords && a.comb.format == b.comb.format && a.padWord == b.padWord &&
            a.trimScale == b.trimScale && a.skyRect.x0 == b.skyRect.x0 && a.skyRect.y0 == b.skyRect.y0 &&
-           a.skyRect.x1 == b.skyRect.x1 && a.skyRect.y1 == b.skyRect.y1;
+           a.skyRect.x1 == b.skyRect.x1 && a.skyRect.y1 == b.skyRect.y1 && a.orderRow == b.orderRow;
 }
 
 // Enqueues launch `l` of the run (chain::host_add, host_launch_held, host_close) with batch p's
@@ -1688,7 +1730,8 @@ bool chain_batch(Ctx &c, hippt::MeshParams &p, long long blocks, const plan::Rin
     namespace chain = hippt::chain;
     Ctx::Chain &ch = c.chain;
     chain::HostRun &run = ch.host;
-    p.comb = hippt::CombineParams{c.accum, c.out, nullptr, p.bandPixels, p.totalItems, 0, p.frames, p.comb.format};
+    p.comb = hippt::CombineParams{c.accum, c.out, nullptr, p.bandPixels, p.totalItems, 0, p.frames, p.comb.format,
+                                  p.comb.sky};
     const bool same = run.live && blocks == ch.blocks && ch.geomRev == S().scene.geomRev && chain_same(p, ch.key);
     if (!chain::host_continues(run, same, p.firstFrame, p.frames)) {
         if (!flush_deferred(c, err)) return false;  // the old run's (or an unchained batch's) combines
@@ -1741,7 +1784,7 @@ bool chain_batch(Ctx &c, hippt::MeshParams &p, long long blocks, const plan::Rin
     p.chainShift = ch.shift;
     p.chainCap = run.cap;
     p.chainStep = run.step;
-    c.hostSamples += p.totalItems;
+    c.hostSamples += (unsigned long long)p.bandPixels * unsigned(p.frames);  // (the combine's samples too)
     // What host_add reads of the run's last launch, and no more (chain::host_add_reads).  Groups are for
     // 64-item runs only: a group interleaves its batches' runs.
     const bool groupable = kChainGroups && p.totalItems % 64u == 0;
@@ -1815,6 +1858,7 @@ bool enqueue_sphere4(Ctx &c, int firstFrame, int count, int maxDepth, bool copy,
     State &s = S();
     // the legacy kernel writes accum/out itself: a mesh batch's pending combine goes first
     if (!flush_deferred(c, err)) return false;
+    c.skyCombinePixels = 0;
     s.activeEnv = 0;  // (the built-in scene keeps its gradient)
     hippt::Sphere4Params p{c.accum, c.out, c.stats, s.width, s.height, c.y0, c.rows, c.stride, firstFrame, count,
                            maxDepth, s.pixelFormat, nullptr};
@@ -2016,9 +2060,10 @@ void mesh_occupancy(Ctx &c, const plan::Facts &f, const plan::Layout &L) {
 // ensure_spill, enqueue_mesh).
 bool fill_mesh_params(Ctx &c, const plan::Facts &f, const plan::Layout &L, const plan::Batch &B, bool chained,
                       const CameraF &cam, int firstFrame, int frames, int maxDepth, float *scratch, hippt::MeshParams &p,
-                      const char **err) {
+                      hippt::SkyComb &sky, const char **err) {
     State &s = S();
     const unsigned bandPixels = unsigned(c.rows) * unsigned(s.width);
+    unsigned long long skyPixels = 0;  // band pixels whose samples the combine finishes (HIPPT_OPT_SKY_COMBINE)
     switch (L.fmt) {
     case hippt::kWideHybrid: p.nodes = c.nodes4h; break;
     case hippt::kWideQuant: p.nodes = c.nodes4q; break;
@@ -2092,13 +2137,47 @@ bool fill_mesh_params(Ctx &c, const plan::Facts &f, const plan::Layout &L, const
         // rows are `stride` image rows apart: the 1/8 shares neutral to -0.9%, r6f)
         const int tile = s.pixelTile >= 0 ? s.pixelTile : c.stride == 1 ? 8 : 0;
         const unsigned tileShift = tile == 8 ? 3u : tile == 16 ? 4u : tile == 32 ? 5u : 6u;
-        if (!ensure_order(c, cam, frames, maxDepth, s.itemOrder == 1, tileShift, &table, err)) return false;
+        // HIPPT_OPT_SKY_COMBINE: the runs wholly outside the rectangle are left out of the table and
+        // finished by the batch's combine.  Not for a counted or an audited batch (their
+        // counts are per traced item), and only with the built-in gradient sky (this function's callers).
+        const bool skyComb = B.skyCombine[chained ? 1 : 0] && skyOn && !s.chainAudit &&
+                             !hippt::skyrect::is_whole(sr, s.width, s.height);
+        unsigned skyRuns = 0;
+        if (!ensure_order(c, cam, frames, maxDepth, s.itemOrder == 1, tileShift, &table, err, skyComb ? &p.skyRect : nullptr,
+                          &skyRuns))
+            return false;
         if (table) {
             p.runOrder = table;
-            p.runCount = unsigned(c.runCosts.size());
+            p.runCount = unsigned(c.runCosts.size()) - skyRuns;
             p.runTileShift = c.orderKey.tileShift;
+            if (skyRuns) {
+                p.orderRow = hippt::skyrect::order_row_len(bandPixels, p.runCount);
+                p.rcpOrderRow = 1.0f / float(p.orderRow);
+                p.totalItems = p.orderRow * unsigned(frames);
+                skyPixels = 64ull * skyRuns;
+            }
         }
     }
+    // the batch's snapshot for its combine (enqueue_mesh, chain_batch)
+    sky = hippt::SkyComb{};
+    if (skyPixels) {
+        sky.on = 1;
+        sky.width = unsigned(s.width);
+        sky.rows = unsigned(c.rows);
+        sky.tileShift = p.runTileShift;
+        sky.y0 = c.y0;
+        sky.rowStride = c.stride;
+        sky.rect = p.skyRect;
+        sky.invW = p.invW;
+        sky.invH = p.invH;
+        for (int k = 0; k < 3; ++k) {
+            sky.origin[k] = cam.origin[k];
+            sky.llc[k] = cam.llc[k];
+            sky.horizontal[k] = cam.horizontal[k];
+            sky.vertical[k] = cam.vertical[k];
+        }
+    }
+    c.skyCombinePixels = (long long)skyPixels;
     p.poolOffset = L.poolOffset;
     if (s.rngTable && !rng_table(c, &p.rngTable, err)) return false;
     return true;
@@ -2111,6 +2190,7 @@ bool enqueue_mesh_lights(Ctx &c, const CameraF &cam, int firstFrame, int count, 
 
 bool enqueue_mesh(Ctx &c, const CameraF &cam, int firstFrame, int count, int maxDepth, bool copy, const char **err) {
     State &s = S();
+    c.skyCombinePixels = 0;
     if (!ensure_scene(c, err)) return false;
     s.activeLightSampling = 0;
     s.activeLightSelect = 0;
@@ -2147,12 +2227,20 @@ bool enqueue_mesh(Ctx &c, const CameraF &cam, int firstFrame, int count, int max
         if (!fuse && !flush_deferred(c, err)) return false;
         float *scratch = nullptr;
         if (!chained && !batch_scratch(c, size.need, &scratch, err)) return false;
+        hippt::SkyComb sky{};  // the batch's snapshot for its combine (HIPPT_OPT_SKY_COMBINE)
         if (maxDepth <= 0) {
             // ray_color with depth <= 0 returns black without tracing (RayTracer.h:582-583)
             HIP_TRY(hipMemsetAsync(scratch, 0, size_t(total) * 3 * sizeof(float), c.stream));
         } else {
             hippt::MeshParams p{};
-            if (!fill_mesh_params(c, facts, L, B, chained, cam, firstFrame + b, nf, maxDepth, scratch, p, err)) return false;
+            if (!fill_mesh_params(c, facts, L, B, chained, cam, firstFrame + b, nf, maxDepth, scratch, p, sky, err)) return false;
+            if (sky.on) {
+                // the left-out samples: one segment each, counted once per batch (the chained batches' pixel
+                // samples are the host's already, chain_batch)
+                const unsigned long long left = (unsigned long long)c.skyCombinePixels * unsigned(nf);
+                c.hostSegments += left;
+                if (!chained) c.hostSamples += left;
+            }
             if (s.knobs.pathMode == 1) {
                 if (!run_wavefront(c, p, cnt, L.spills, L.spillCap, err)) return false;
             } else {
@@ -2162,12 +2250,19 @@ bool enqueue_mesh(Ctx &c, const CameraF &cam, int firstFrame, int count, int max
                 s.activeChainCap = 0;
                 if (chained) {
                     p.comb.format = s.pixelFormat;
+                    p.comb.sky = sky;  // (one camera per run, chain_same: the run's snapshot)
                     if (!chain_batch(c, p, blocks, ring, err)) return false;
                     s.activeChainCap = int(c.chain.host.cap);
                     continue;  // launched or taken by the run's last launch; its combine
                                // belongs to the run (Ctx::chain)
                 } else {
                     HIP_TRY(hipMemsetAsync(c.queue, 0, kQueueBytes, c.stream));
+                    // (a pending sky-mode combine goes to combine_kernel when this launch's variant has no sky
+                    // branch, plan::sky_combine_kernel)
+                    if (c.hasDeferred && c.deferred.sky.on &&
+                        !plan::sky_combine_kernel(cnt, L.ldsScene, facts.full, L.spills, L.poolWords != 0, false) &&
+                        !flush_deferred(c, err))
+                        return false;
                     if (c.hasDeferred) {
                         p.comb = c.deferred;
                         c.hasDeferred = false;
@@ -2178,7 +2273,7 @@ bool enqueue_mesh(Ctx &c, const CameraF &cam, int firstFrame, int count, int max
             }
         }
         if (chained && maxDepth > 0) continue;  // its combine belongs to the run (Ctx::chain)
-        c.deferred = hippt::CombineParams{c.accum, c.out, scratch, bandPixels, total, firstFrame + b, nf, s.pixelFormat};
+        c.deferred = hippt::CombineParams{c.accum, c.out, scratch, bandPixels, total, firstFrame + b, nf, s.pixelFormat, sky};
         c.hasDeferred = true;
         if (!fuse && !flush_deferred(c, err)) return false;
     }
@@ -3618,7 +3713,7 @@ extern "C" bool hipptGetStats(hipptStats *out) {
         for (Ctx &c : s.ctxs) {
             unsigned long long v[kStatWords];
             if (!read_stats(c, v)) return false;
-            out->segments += v[0];
+            out->segments += v[0] + c.hostSegments;
             out->pixelSamples += v[1] + c.hostSamples;
             out->nodeVisits += v[2];
             out->triTests += v[3];
@@ -3646,6 +3741,7 @@ extern "C" int hipptGetCounters(unsigned long long *out, int n) {
         for (Ctx &c : s.ctxs) {
             unsigned long long v[kStatWords];
             if (!read_stats(c, v)) return 0;
+            v[0] += c.hostSegments;
             v[1] += c.hostSamples;
             for (int i = 0; i < n; ++i) out[i] += v[i];
         }
@@ -3662,6 +3758,7 @@ extern "C" void hipptResetStats(void) {
             (void)hipSetDevice(c.device);
             (void)hipMemset(c.stats, 0, kStatBytes);
             c.hostSamples = 0;
+            c.hostSegments = 0;
         }
         s.traceMs = s.combineMs = 0;
         s.traceLaunches = s.combineLaunches = 0;
@@ -3802,6 +3899,10 @@ bool set_option_locked(int key, long long value) {
         if (value != 0 && value != 1) return false;
         s.knobs.skyRect = value == 1;
         return true;
+    case HIPPT_OPT_SKY_COMBINE:
+        if (value != -1 && value != 0) return false;
+        s.knobs.skyCombine = int(value);
+        return true;
     case HIPPT_OPT_DENOISE_TIMING:
         if (value != 0 && value != 1) return false;
         s.denoiseTiming = value == 1;
@@ -3875,6 +3976,7 @@ long long get_option_locked(int key) {
     case HIPPT_OPT_QUERY_SLICE: return s.querySlice;
     case HIPPT_OPT_RENDER_PAD: return s.knobs.renderPad;
     case HIPPT_OPT_SKY_RECT: return s.knobs.skyRect ? 1 : 0;
+    case HIPPT_OPT_SKY_COMBINE: return s.knobs.skyCombine;
     case HIPPT_INFO_LDS_TOP_BYTES: return s.activeTopBytes;
     case HIPPT_INFO_BLOCKS_PER_CU: return s.activeBlocksPerCu;
     case HIPPT_INFO_CHUNK: return s.activeChunk;
@@ -3891,6 +3993,11 @@ long long get_option_locked(int key) {
     case HIPPT_OPT_ENV_SAMPLING: return s.envSampling;
     case HIPPT_INFO_ENV_SAMPLING: return s.activeEnvSampling;
     case HIPPT_INFO_SKY_RECT_PIXELS: return s.activeSkyPixels;
+    case HIPPT_INFO_SKY_COMBINE: {
+        long long n = 0;
+        for (const Ctx &c : s.ctxs) n += c.skyCombinePixels;
+        return n;
+    }
     case HIPPT_INFO_UPDATE_DROPPED:
         // the last update's count, from the first context that ran it (every context counts the same)
         for (Ctx &c : s.ctxs) {

@@ -30,6 +30,25 @@ struct Sphere4Params {
 // Pixel word formats of the output frame (HIPPT_OPT_PIXEL_FORMAT)
 enum { kPixelArgb = 0, kPixelRgba8 = 1 };
 
+// Image pixels [x0, x1) x [y0, y1) (skyrect::Rect, hippt_sky_rect.h)
+struct SkyRect {
+    int x0, y0, x1, y1;
+};
+
+// HIPPT_OPT_SKY_COMBINE (DESIGN.md §5 "Sky runs in the combine"): what the batch was traced with, for
+// the samples its item table left out (the 64-pixel runs wholly outside its sky rectangle,
+// skyrect::pixel_in_sky_run): the combine computes their radiance instead of loading it.  A snapshot:
+// the combine runs a launch later than its batch, after the camera, the scene or the image may have
+// changed.  on == 0: every sample was traced.
+struct SkyComb {
+    int on;
+    unsigned width, rows, tileShift;  // skyrect::RunShape
+    int y0, rowStride;
+    SkyRect rect;
+    float invW, invH;
+    float origin[3], llc[3], horizontal[3], vertical[3];  // the pinhole's CameraF fields
+};
+
 // Running average + tonemap over a batch of per-sample radiances
 // (CudaPathTracerKernel.cu:157-178).
 struct CombineParams {
@@ -39,6 +58,7 @@ struct CombineParams {
     unsigned bandPixels, totalItems;
     int firstFrame, frames;
     int format;  // kPixelArgb / kPixelRgba8
+    SkyComb sky;
 };
 
 // combine_kernel's output words also into the pinned full W*H host frame (device-mapped; a
@@ -46,11 +66,6 @@ struct CombineParams {
 struct HostFrame {
     uint32_t *host;
     int width, y0, stride;
-};
-
-// Image pixels [x0, x1) x [y0, y1) (skyrect::Rect, hippt_sky_rect.h)
-struct SkyRect {
-    int x0, y0, x1, y1;
 };
 
 // Mesh megakernel: one persistent grid drains `totalItems` (pixel, frame) samples of the band's
@@ -156,6 +171,12 @@ struct MeshParams {
     // the scene, and a pool refill whose 64 items all lie outside finishes them without a traversal.
     // The whole image: nothing is skipped.
     SkyRect skyRect;
+    // HIPPT_OPT_SKY_COMBINE: queue positions per frame of a table that leaves runs out
+    // (skyrect::order_row_len; totalItems = frames * orderRow) and its reciprocal; 0: the table, if
+    // any, holds every run and a frame has bandPixels positions.  The omitted runs' samples are the
+    // combine's (comb.sky of the launch that combines this batch).
+    unsigned orderRow;
+    float rcpOrderRow;
 };
 
 // Chained batches: the control block (unsigned words).  Ring slot k's block at k * kChainBlockWords:

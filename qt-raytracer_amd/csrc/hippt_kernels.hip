@@ -218,18 +218,79 @@ constexpr unsigned kSkyRunsPerTrip = HIPPT_SKY_RUNS;
 #endif
 // Running average in frame order, then the output word (CudaPathTracerKernel.cu:157-178), of band
 // pixel p over a batch of per-sample radiances.
-template <int UNROLL, bool HOST = false>
-__device__ __forceinline__ void combine_pixel(const CombineParams &P, unsigned p, const HostFrame &H = HostFrame{}) {
+//
+// HIPPT_OPT_SKY_COMBINE (CombineParams::sky): the batch's table left out the runs wholly
+// outside its sky rectangle, and for a pixel of such a run the frame loop computes the sample's
+// radiance instead of loading it: the refill path's own sequence (mesh_kernel, "Sky rectangle") from
+// the batch's snapshot: camera_pixel's seed and two draws, camera_dir_pinhole, sky_inv at throughput 1
+// (sky() is the same arithmetic), so the bits are the ones that path stored.
+//
+// Registers: the snapshot is read through a pointer into the kernel's argument block that is laundered into
+// vector registers (SkyArg), so its ~30 words are vector loads where the branch runs: in scalar registers
+// they spilled the timed megakernels (the SGPR cap, then a VGPR for the spill lanes; profiles/sky_combine/
+// regs.txt).  `on` alone is a scalar the caller loads.
+struct SkyArg {
+    int on;
+    const SkyComb *ptr;  // the kernel's own argument block at the snapshot's offset
+};
+__device__ __forceinline__ SkyArg sky_arg(int on, unsigned offset) {
+    return SkyArg{on, reinterpret_cast<const SkyComb *>((const char *)__builtin_amdgcn_kernarg_segment_ptr() + offset)};
+}
+__device__ __forceinline__ bool sky_comb_pixel(const SkyArg A, unsigned p, SkyComb &K, unsigned &x, unsigned &y) {
+    if (!A.on) return false;
+    const SkyComb *kp = A.ptr;
+    asm volatile("" : "+v"(kp));
+    // (field by field: a copy of the whole block leaves the kernels a stack slot)
+    K.width = kp->width, K.rows = kp->rows, K.tileShift = kp->tileShift, K.y0 = kp->y0, K.rowStride = kp->rowStride;
+    const skyrect::Rect R{kp->rect.x0, kp->rect.y0, kp->rect.x1, kp->rect.y1};
+    const skyrect::RunShape S{K.width, K.rows, K.tileShift, K.y0, K.rowStride};
+    if (!skyrect::pixel_in_sky_run(S, R, p)) return false;
+    K.invW = kp->invW, K.invH = kp->invH;
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        K.origin[k] = kp->origin[k], K.llc[k] = kp->llc[k], K.horizontal[k] = kp->horizontal[k], K.vertical[k] = kp->vertical[k];
+    const unsigned yb = p / K.width;
+    x = p - yb * K.width;
+    y = unsigned(K.y0) + yb * unsigned(K.rowStride);
+    return true;
+}
+__device__ __forceinline__ float3 sky_comb_sample(const SkyComb &K, unsigned x, unsigned y, unsigned frame) {
+    uint32_t rng = pixel_seed(x, y, K.width, frame);
+    const float s = (float(x) + rand01(rng)) * K.invW;
+    const float t = (float(y) + rand01(rng)) * K.invH;
+    Ray c{};
+    camera_dir_pinhole(K, s, t, c);
+    float3 L;
+    sky_inv(c, rsqrt_rn(fdot(c.dx, c.dy, c.dz, c.dx, c.dy, c.dz)), 1.0f, 1.0f, 1.0f, L.x, L.y, L.z);
+    return L;
+}
+
+template <int UNROLL, bool HOST = false, bool SKYC = true>
+__device__ __forceinline__ void combine_pixel(const CombineParams &P, const SkyArg A, unsigned p,
+                                              const HostFrame H = HostFrame{}) {
     float4 acc = P.accum[p];
+    unsigned sx = 0, sy = 0;
+    SkyComb K;
+    if (SKYC && sky_comb_pixel(A, p, K, sx, sy)) {
+        for (int fl = 0; fl < P.frames; ++fl) {
+            const int f = P.firstFrame + fl;
+            const float ff = float(f), fc = float(f + 1);
+            const float3 L = sky_comb_sample(K, sx, sy, unsigned(f));
+            acc.x = fmaf(acc.x, ff, L.x) / fc;
+            acc.y = fmaf(acc.y, ff, L.y) / fc;
+            acc.z = fmaf(acc.z, ff, L.z) / fc;
+        }
+    } else {
 #pragma unroll UNROLL
-    for (int fl = 0; fl < P.frames; ++fl) {
-        const size_t k = size_t(fl) * P.bandPixels + p;
-        const int f = P.firstFrame + fl;
-        const float ff = float(f), fc = float(f + 1);
-        const float3 L = *reinterpret_cast<const float3 *>(P.scratch + 3 * k);
-        acc.x = fmaf(acc.x, ff, L.x) / fc;
-        acc.y = fmaf(acc.y, ff, L.y) / fc;
-        acc.z = fmaf(acc.z, ff, L.z) / fc;
+        for (int fl = 0; fl < P.frames; ++fl) {
+            const size_t k = size_t(fl) * P.bandPixels + p;
+            const int f = P.firstFrame + fl;
+            const float ff = float(f), fc = float(f + 1);
+            const float3 L = *reinterpret_cast<const float3 *>(P.scratch + 3 * k);
+            acc.x = fmaf(acc.x, ff, L.x) / fc;
+            acc.y = fmaf(acc.y, ff, L.y) / fc;
+            acc.z = fmaf(acc.z, ff, L.z) / fc;
+        }
     }
     acc.w = 1.0f;
     P.accum[p] = acc;
@@ -245,47 +306,90 @@ __device__ __forceinline__ void combine_pixel(const CombineParams &P, unsigned p
 // once every chunk is claimed.  Wave-uniform.  The frame loop is not unrolled here: unrolled 8x
 // at the kernel's two call sites it cost blob70k 3% even with the combine off (r3g/r3h; none
 // without the unroll, r3i).
+template <bool SKYC>
 __device__ __forceinline__ bool combine_chunk(const MeshParams &P) {
     unsigned base = 0;
     if (__lane_id() == 0) base = atomicAdd(P.combCtr, 64u);
     base = __builtin_amdgcn_readfirstlane(base);
     if (base >= P.comb.bandPixels) return false;
     const unsigned p = base + __lane_id();
-    if (p < P.comb.bandPixels) combine_pixel<1>(P.comb, p);
+    if (p < P.comb.bandPixels)
+        combine_pixel<1, false, SKYC>(P.comb, sky_arg(SKYC ? late_field(comb.sky.on) : 0, unsigned(offsetof(MeshParams, comb.sky))), p);
     return true;
 }
 
 // Chained batches (hippt_trace.h): the running average of band pixel p over the run's batches
 // [c0, c1] in order (batch b: frames C.firstFrame + b*step + fl, its samples in ring slot b % slots).
-template <int UNROLL, bool HOST = false>
-__device__ __forceinline__ void combine_pixel_chain(const CombineParams &C, const float *scratch, unsigned p, int c0,
-                                                    int c1, unsigned slots, unsigned shift, int step,
-                                                    const HostFrame &H = HostFrame{}) {
-    float4 acc = C.accum[p];
-    for (int b = c0; b <= c1; ++b) {
-        const float *scr = scratch + 3 * ((size_t(unsigned(b) & (slots - 1u)) << shift) + p);
-        const int f0 = C.firstFrame + b * step;
+// S: where the combine's words come from, each read where it is used: the chained megakernels load them from
+// their argument block there (ChainCombLate: in scalar registers across both branches they cost the kernels
+// without the spilling stack a stack slot), chain_flush_kernel has them as arguments (ChainCombArgs).
+struct ChainCombLate {
+    __device__ __forceinline__ float4 *accum() const { return late_field(comb.accum); }
+    __device__ __forceinline__ uint32_t *out() const { return late_field(comb.out); }
+    __device__ __forceinline__ const float *scratch() const { return late_field(scratch); }
+    __device__ __forceinline__ unsigned bandPixels() const { return late_field(comb.bandPixels); }
+    __device__ __forceinline__ int firstFrame() const { return late_field(comb.firstFrame); }
+    __device__ __forceinline__ int frames() const { return late_field(comb.frames); }
+    __device__ __forceinline__ int format() const { return late_field(comb.format); }
+    __device__ __forceinline__ unsigned slots() const { return late_field(chainSlots); }
+    __device__ __forceinline__ unsigned shift() const { return late_field(chainShift); }
+    __device__ __forceinline__ int step() const { return max(0, late_field(chainStep)); }
+};
+struct ChainCombArgs {
+    const ChainFlushParams &P;
+    __device__ __forceinline__ float4 *accum() const { return P.comb.accum; }
+    __device__ __forceinline__ uint32_t *out() const { return P.comb.out; }
+    __device__ __forceinline__ const float *scratch() const { return P.scratch; }
+    __device__ __forceinline__ unsigned bandPixels() const { return P.comb.bandPixels; }
+    __device__ __forceinline__ int firstFrame() const { return P.comb.firstFrame; }
+    __device__ __forceinline__ int frames() const { return P.comb.frames; }
+    __device__ __forceinline__ int format() const { return P.comb.format; }
+    __device__ __forceinline__ unsigned slots() const { return P.slots; }
+    __device__ __forceinline__ unsigned shift() const { return P.shift; }
+    __device__ __forceinline__ int step() const { return P.step; }
+};
+template <int UNROLL, bool SKYC, typename Src>
+__device__ __forceinline__ void combine_pixel_chain(const Src &S, const SkyArg A, unsigned p, int c0, int c1) {
+    float4 acc = S.accum()[p];
+    unsigned sx = 0, sy = 0;
+    SkyComb K;
+    if (SKYC && sky_comb_pixel(A, p, K, sx, sy)) {  // (a run has one camera: every batch's samples of the pixel)
+        const int first = S.firstFrame(), frames = S.frames(), step = S.step();
+        for (int b = c0; b <= c1; ++b) {
+            const int f0 = first + b * step;
+            for (int fl = 0; fl < frames; ++fl) {
+                const float3 L = sky_comb_sample(K, sx, sy, unsigned(f0 + fl));
+                const float ff = float(f0 + fl), fc = float(f0 + fl + 1);
+                acc.x = fmaf(acc.x, ff, L.x) / fc;
+                acc.y = fmaf(acc.y, ff, L.y) / fc;
+                acc.z = fmaf(acc.z, ff, L.z) / fc;
+            }
+        }
+    } else {
+        const float *const scratch = S.scratch();
+        const unsigned slots = S.slots(), shift = S.shift(), bandPixels = S.bandPixels();
+        const int first = S.firstFrame(), frames = S.frames(), step = S.step();
+        for (int b = c0; b <= c1; ++b) {
+            const float *scr = scratch + 3 * ((size_t(unsigned(b) & (slots - 1u)) << shift) + p);
+            const int f0 = first + b * step;
 #pragma unroll UNROLL
-        for (int fl = 0; fl < C.frames; ++fl) {
-            const float3 L = *reinterpret_cast<const float3 *>(scr + 3 * size_t(fl) * C.bandPixels);
-            const float ff = float(f0 + fl), fc = float(f0 + fl + 1);
-            acc.x = fmaf(acc.x, ff, L.x) / fc;
-            acc.y = fmaf(acc.y, ff, L.y) / fc;
-            acc.z = fmaf(acc.z, ff, L.z) / fc;
+            for (int fl = 0; fl < frames; ++fl) {
+                const float3 L = *reinterpret_cast<const float3 *>(scr + 3 * size_t(fl) * bandPixels);
+                const float ff = float(f0 + fl), fc = float(f0 + fl + 1);
+                acc.x = fmaf(acc.x, ff, L.x) / fc;
+                acc.y = fmaf(acc.y, ff, L.y) / fc;
+                acc.z = fmaf(acc.z, ff, L.z) / fc;
+            }
         }
     }
     acc.w = 1.0f;
-    C.accum[p] = acc;
-    const uint32_t word = pack_pixel(acc.x, acc.y, acc.z, C.format);
-    C.out[p] = word;
-    if (HOST && H.host) {
-        const unsigned yb = p / unsigned(H.width), x = p - yb * unsigned(H.width);
-        H.host[size_t(unsigned(H.y0) + yb * unsigned(H.stride)) * unsigned(H.width) + x] = word;
-    }
+    S.accum()[p] = acc;
+    S.out()[p] = pack_pixel(acc.x, acc.y, acc.z, S.format());
 }
 
 // combine_chunk of a CHAIN launch: 64 pixels over its combine range (ChainWave::c0..c1), chunks from
 // the launch's epoch-parity counter; arguments loaded where they are used.
+template <bool SKYC>
 __device__ __forceinline__ bool combine_chunk_chain(const ChainWave *cw) {
     unsigned *const ctl = late_field(chainCtl);
     const unsigned e = late_field(chainEpoch);
@@ -297,8 +401,9 @@ __device__ __forceinline__ bool combine_chunk_chain(const ChainWave *cw) {
     const unsigned p = base + __lane_id();
     const int c0 = int(__builtin_amdgcn_readfirstlane(cw->c0)), c1 = int(__builtin_amdgcn_readfirstlane(cw->c1));
     if (p < bandPixels)
-        combine_pixel_chain<8>(late_field(comb), late_field(scratch), p, c0, c1, late_field(chainSlots),
-                               late_field(chainShift), max(0, late_field(chainStep)));
+        combine_pixel_chain<8, SKYC>(ChainCombLate{},
+                                     sky_arg(SKYC ? late_field(comb.sky.on) : 0, unsigned(offsetof(MeshParams, comb.sky))), p,
+                                     c0, c1);
     if (unsigned *const audit = late_field(chainAudit)) {
         const bool v = p < bandPixels;
         audit_combine(audit, c0, c1, unsigned(__popcll(__ballot(v))), wave_sum(v ? audit_hash(p) : 0ull), e,
@@ -509,7 +614,10 @@ __global__ __launch_bounds__(kMeshBlock, (FULL || WIDE) ? HIPPT_WIDE_WAVES_PER_E
     unsigned skyRuns = 0;  // (wave-uniform) sky runs finished since the last traversal round
     bool combLeft = CHAIN ? int(__builtin_amdgcn_readfirstlane(cw->c1)) >= int(__builtin_amdgcn_readfirstlane(cw->c0))
                           : P.comb.bandPixels != 0;
-    auto comb_step = [&]() { return CHAIN ? combine_chunk_chain(cw) : combine_chunk(P); };
+    // HIPPT_OPT_SKY_COMBINE: this variant's fused combine has the sky branch (the host gives the others no
+    // sky-mode combine: plan::sky_combine_kernel, checked in launch_mesh)
+    constexpr bool SKYCOMB = plan::sky_combine_kernel(STATS, LDS_SCENE, FULL, SPILL, POOL, CHAIN);
+    auto comb_step = [&]() { return CHAIN ? combine_chunk_chain<SKYCOMB>(cw) : combine_chunk<SKYCOMB>(P); };
     if (combLeft && (blockIdx.x & 1u) == 0 && threadIdx.x < 64u)
         while (combLeft) combLeft = comb_step();
     for (;;) {
@@ -583,7 +691,7 @@ __global__ __launch_bounds__(kMeshBlock, (FULL || WIDE) ? HIPPT_WIDE_WAVES_PER_E
                         }
                     } else {
                         it = HIPPT_LATE_CAM ? order_item_late(queue_fetch(true, Q, P.queue, P.totalItems, P.chunk, true, drained))
-                                            : order_item(P, queue_fetch(true, Q, P.queue, P.totalItems, P.chunk, true, drained));
+                                            : order_item<SKYCOMB>(P, queue_fetch(true, Q, P.queue, P.totalItems, P.chunk, true, drained));
                         if (it != kNone) {
                             unsigned px, py;
                             if (HIPPT_LATE_CAM)
@@ -660,7 +768,7 @@ __global__ __launch_bounds__(kMeshBlock, (FULL || WIDE) ? HIPPT_WIDE_WAVES_PER_E
             }
         } else if (__ballot(need)) {
             const unsigned it = HIPPT_LATE_CAM ? order_item_late(queue_fetch(need, Q, P.queue, P.totalItems, P.chunk))
-                                               : order_item(P, queue_fetch(need, Q, P.queue, P.totalItems, P.chunk));
+                                               : order_item<false>(P, queue_fetch(need, Q, P.queue, P.totalItems, P.chunk));
 #ifdef HIPPT_DEBUG_TIMELINE
             if (!tlDrained && __ballot(need && it == kNone)) tlDrained = __builtin_amdgcn_s_memrealtime();
             tlItems += __popcll(__ballot(it != kNone));
@@ -816,7 +924,8 @@ __global__ __launch_bounds__(kMeshBlock, (FULL || WIDE) ? HIPPT_WIDE_WAVES_PER_E
 // Running average in frame order, then ARGB (CudaPathTracerKernel.cu:157-178).
 __global__ __launch_bounds__(256) void combine_kernel(CombineParams P, HostFrame H) {
     const unsigned stride = gridDim.x * 256u;
-    for (unsigned p = blockIdx.x * 256u + threadIdx.x; p < P.bandPixels; p += stride) combine_pixel<8, true>(P, p, H);
+    const SkyArg A = sky_arg(P.sky.on, unsigned(offsetof(CombineParams, sky)));  // (P: the first argument)
+    for (unsigned p = blockIdx.x * 256u + threadIdx.x; p < P.bandPixels; p += stride) combine_pixel<8, true>(P, A, p, H);
 }
 
 // The chain's final combine (ChainFlushParams): every batch of the run no launch combined, in order.
@@ -829,7 +938,9 @@ __global__ __launch_bounds__(256) void chain_flush_kernel(ChainFlushParams P) {
     for (unsigned base = blockIdx.x * 256u + (threadIdx.x & ~63u); base < P.comb.bandPixels; base += stride) {
         const unsigned p = base + __lane_id();
         const bool v = p < P.comb.bandPixels;
-        if (v) combine_pixel_chain<8>(P.comb, P.scratch, p, c0, c1, P.slots, P.shift, P.step);
+        if (v)
+            combine_pixel_chain<8, true>(ChainCombArgs{P}, sky_arg(P.comb.sky.on, unsigned(offsetof(ChainFlushParams, comb.sky))),
+                                         p, c0, c1);
         if (P.audit)
             audit_combine(P.audit, c0, c1, unsigned(__popcll(__ballot(v))), wave_sum(v ? audit_hash(p) : 0ull), P.epoch,
                           P.comb.firstFrame, P.step);
@@ -986,6 +1097,10 @@ hipError_t launch_mesh(const MeshParams &p, int blocks, bool countTraversal, hip
     if (p.full < 0 || p.full > 2) return hipErrorInvalidValue;
     const MeshFn fn = mesh_fn(countTraversal, lds, p.full, p.wide, p.spill != nullptr, pool, chain);
     if (!fn) return hipErrorInvalidValue;
+    // a sky-mode combine, or a table that leaves runs out, only for a variant that has the code for it
+    if (((p.comb.bandPixels && p.comb.sky.on) || p.orderRow) &&
+        !plan::sky_combine_kernel(countTraversal, lds, p.full != 0, countTraversal || p.spill != nullptr, pool, chain))
+        return hipErrorInvalidValue;
     if (p.wide && (lds || p.topBytes || pool)) {
         const hipError_t e = check_lds_at_zero(reinterpret_cast<const void *>(fn));
         if (e != hipSuccess) return e;

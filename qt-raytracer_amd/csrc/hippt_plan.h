@@ -102,6 +102,7 @@ struct Knobs {
     int chainBatches = -1;  // batches a chained launch may trace (HIPPT_OPT_CHAIN; 0 off, -1 automatic)
     int renderPad = 0;      // HIPPT_OPT_RENDER_PAD (0: the builder's pad)
     bool skyRect = true;    // HIPPT_OPT_SKY_RECT
+    int skyCombine = -1;    // HIPPT_OPT_SKY_COMBINE (-1 automatic, 0 off)
 };
 
 // LDS limits of the kernels as built (hippt_kernels.hip mesh_lds_scene_limit, mesh_lds_block_budget:
@@ -301,6 +302,15 @@ inline Knobs query_knobs(Knobs k) {
 // rays per claim of a query launch of m rays
 inline unsigned query_chunk(unsigned m) { return m >= (1u << 20) ? 256u : 64u; }
 
+// HIPPT_OPT_SKY_COMBINE: the megakernel variants whose fused combine has the sky branch (hippt_kernels.hip
+// mesh_kernel SKYCOMB): the timed camera-pool kernels, less those that could take it only with new scratch
+// bytes (profiles/sky_combine/regs.txt): the unchained general kernels over an LDS scene, or with the
+// spilling stack.  A batch traced by another variant keeps the in-kernel path, and a launch of another
+// variant leaves a pending sky-mode combine to combine_kernel.
+constexpr bool sky_combine_kernel(bool count, bool lds, bool full, bool spill, bool pool, bool chain) {
+    return pool && !count && !(full && !chain && (lds || spill));
+}
+
 // What depends on the batch.  A batch that may chain is chained once its ring is there (ring_plan
 // below; hippt_api.cpp ensure_ring); the claim size and the sky rectangle depend on whether it was: [0] for a
 // batch launched on its own, [1] for a chained one.
@@ -310,6 +320,9 @@ struct Batch {
     bool trimWanted = false;
     unsigned chunk[2] = {0, 0};
     bool skyWanted[2] = {false, false};
+    // HIPPT_OPT_SKY_COMBINE's static part: the option, a rectangle wanted, not counted, a variant with the branch
+    // (the rectangle itself, the item table and the audit are the caller's)
+    bool skyCombine[2] = {false, false};
 };
 
 // copy: a blocking frame; total: the batch's work items
@@ -340,6 +353,8 @@ inline Batch batch(const Facts &f, const Knobs &k, const Layout &L, bool copy, i
         // unchained general LDS kernel with the spilling stack)
         b.skyWanted[chained] = k.pathMode == 0 && L.poolWords != 0 && k.skyRect &&
                                !(f.full && L.ldsScene && L.spills && !chained && !cnt);
+        b.skyCombine[chained] = k.skyCombine != 0 && b.skyWanted[chained] &&
+                                sky_combine_kernel(cnt, L.ldsScene, f.full, L.spills, L.poolWords != 0, chained != 0);
     }
     return b;
 }

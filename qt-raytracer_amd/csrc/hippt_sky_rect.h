@@ -145,5 +145,136 @@ inline Rect sky_rect(const Cam &cam, int width, int height, const float lo[3], c
     return r;
 }
 
+// ---- runs wholly outside the rectangle (HIPPT_OPT_SKY_COMBINE, DESIGN.md §5 "Sky runs in the combine") ----
+// Host and device both compile what follows.
+#if defined(__HIPCC__)
+#define HIPPT_SKY_HD __host__ __device__ __forceinline__
+#else
+#define HIPPT_SKY_HD inline
+#endif
+
+// The band's run geometry (item_order.h RunLayout and the band's rows): band row k is image row
+// y0 + k * rowStride; tileShift < 6: tiles of 2^tileShift columns x 2^(6 - tileShift) band rows over the
+// band's whole strips, runs of 64 consecutive band pixels over the rest; 6: consecutive runs only.
+struct RunShape {
+    unsigned width, rows, tileShift;
+    int y0, rowStride;
+};
+HIPPT_SKY_HD unsigned shape_band_pixels(const RunShape S) { return S.width * S.rows; }
+// band pixels the tiles cover (the whole strips), 0 without tiles
+HIPPT_SKY_HD unsigned shape_tile_pixels(const RunShape S) {
+    if (S.tileShift >= 6u) return 0u;
+    const unsigned th = 64u >> S.tileShift;
+    return (S.rows / th) * th * S.width;
+}
+template <typename R>
+HIPPT_SKY_HD bool pixel_outside(const R &r, unsigned x, unsigned y) {
+    return x - unsigned(r.x0) >= unsigned(r.x1 - r.x0) || y - unsigned(r.y0) >= unsigned(r.y1 - r.y0);
+}
+// (a rectangle that skips nothing: the mode has nothing to do)
+template <typename R>
+HIPPT_SKY_HD bool rect_valid(const R &r) {
+    return r.x0 >= 0 && r.y0 >= 0 && r.x1 >= r.x0 && r.y1 >= r.y0;
+}
+
+// "This 64-item run is wholly sky-certain": the run whose item 0 is band pixel `base` (a tile when
+// `tile`) has 64 valid pixels, all outside the rectangle.  It is the refill path's test,
+// __ballot(skyLane) == ~0ull (hippt_kernels.hip), as a function of the run: lane k has
+// skyLane = (item k valid) && pixel_outside(rect, x_k, y_k), with (x_k, y_k) from the same base + offset
+// arithmetic as run_pixel, and a ballot of all ones is the conjunction over the 64 lanes.  Where a refill's
+// 64 positions are one table slot (a band of a multiple of 64 pixels: every frame's row starts aligned)
+// the two tests are the same test.  Where they are not (a row length that is no multiple of 64: later
+// frames start unaligned and a claim straddles two slots) the ballot may differ, and nothing depends on
+// it: the host alone decides which runs the table leaves out, with this function, the combine asks the
+// same function through pixel_in_sky_run, and for a sample of a pixel outside the rectangle the refill
+// path and the combine compute the same bits, whichever of them finishes it.  A tile is a product of a
+// column range and a row set, so it is outside iff its columns miss [x0, x1) or every one of its rows
+// misses [y0, y1); a consecutive run is a row range with a column interval per row.
+template <typename R>
+HIPPT_SKY_HD bool run_sky_certain(const RunShape S, const R &rect, unsigned base, bool tile) {
+    if (!rect_valid(rect) || S.width == 0u) return false;
+    if (tile) {
+        const unsigned tw = 1u << S.tileShift, th = 64u >> S.tileShift;
+        const unsigned yb = base / S.width, x = base - yb * S.width;
+        if (x + tw > S.width || yb + th > S.rows) return false;
+        // columns [x, x + tw) against [x0, x1)
+        if (int(x + tw) <= rect.x0 || int(x) >= rect.x1) return true;
+        for (unsigned k = 0; k < th; ++k) {
+            const unsigned y = unsigned(S.y0) + (yb + k) * unsigned(S.rowStride);
+            if (y - unsigned(rect.y0) < unsigned(rect.y1 - rect.y0)) return false;
+        }
+        return true;
+    }
+    if (base + 64u > shape_band_pixels(S)) return false;
+    unsigned p = base;
+    while (p < base + 64u) {
+        const unsigned yb = p / S.width, x = p - yb * S.width;
+        const unsigned n = (S.width - x) < (base + 64u - p) ? S.width - x : base + 64u - p;  // this row's pixels
+        const unsigned y = unsigned(S.y0) + yb * unsigned(S.rowStride);
+        const bool rowIn = y - unsigned(rect.y0) < unsigned(rect.y1 - rect.y0);
+        if (rowIn && !(int(x + n) <= rect.x0 || int(x) >= rect.x1)) return false;
+        p += n;
+    }
+    return true;
+}
+
+// The inverse the combine needs: band pixel p's run (item_order.h run_base) -> base and shape; false
+// for a pixel in no whole run (the band's last bandPixels % 64 pixels).
+HIPPT_SKY_HD bool pixel_run(const RunShape S, unsigned p, unsigned &base, bool &tile) {
+    const unsigned tp = shape_tile_pixels(S), bp = shape_band_pixels(S);
+    if (p >= bp) return false;
+    if (p < tp) {
+        const unsigned tw = 1u << S.tileShift, th = 64u >> S.tileShift;
+        const unsigned yb = p / S.width, x = p - yb * S.width;
+        base = (yb / th) * th * S.width + (x & ~(tw - 1u));
+        tile = true;
+        return true;
+    }
+    base = tp + ((p - tp) & ~63u);
+    tile = false;
+    return base + 64u <= bp;
+}
+template <typename R>
+HIPPT_SKY_HD bool pixel_in_sky_run(const RunShape S, const R &rect, unsigned p) {
+    unsigned base = 0;
+    bool tile = false;
+    return pixel_run(S, p, base, tile) && run_sky_certain(S, rect, base, tile);
+}
+
+// A queue position of a batch whose table has `runCount` runs per frame out of the band's
+// bandPixels / 64 (the omitted ones are finished by the combine): frame fl = pos / rowLen and offset
+// q = pos % rowLen with rowLen = 64 * runCount + bandPixels % 64.  q < 64 * runCount is item q % 64 of
+// table entry fl * runCount + q / 64; the rest are the band's last pixels in image order,
+// fl * bandPixels + (bandPixels - rowLen) + q.  With every run in the table rowLen is bandPixels.
+HIPPT_SKY_HD unsigned order_row_len(unsigned bandPixels, unsigned runCount) { return 64u * runCount + (bandPixels & 63u); }
+HIPPT_SKY_HD unsigned order_tail_item(unsigned bandPixels, unsigned rowLen, unsigned fl, unsigned q) {
+    return fl * bandPixels + (bandPixels - rowLen) + q;
+}
+// n / d and n % d from d's float reciprocal, corrected by one (trace::divmod's arithmetic)
+HIPPT_SKY_HD void divmod_rcp(unsigned n, unsigned d, float rcp, unsigned &q, unsigned &r) {
+    q = unsigned(float(n) * rcp);
+    int rem = int(n - q * d);
+    if (rem < 0) {
+        --q;
+        rem += int(d);
+    } else if (rem >= int(d)) {
+        ++q;
+        rem -= int(d);
+    }
+    r = unsigned(rem);
+}
+// The item at queue position pos of such a table (trace::order_item calls this; the model test decodes
+// every position of its tables with it): a table entry's item k is its band pixel + k, or for a tile
+// (bit 31) column k mod 2^tileShift, band row k >> tileShift of the tile.
+HIPPT_SKY_HD unsigned order_position_item(unsigned pos, unsigned bandPixels, unsigned rowLen, float rcpRowLen,
+                                          unsigned runCount, const unsigned *table, unsigned width, unsigned tileShift) {
+    unsigned fl, q;
+    divmod_rcp(pos, rowLen, rcpRowLen, fl, q);
+    const unsigned run = q >> 6, k = q & 63u;
+    if (run >= runCount) return order_tail_item(bandPixels, rowLen, fl, q);
+    const unsigned v = table[fl * runCount + run];
+    return (v & 0x7fffffffu) + ((v >> 31) ? (k & ((1u << tileShift) - 1u)) + (k >> tileShift) * width : k);
+}
+
 }  // namespace skyrect
 }  // namespace hippt

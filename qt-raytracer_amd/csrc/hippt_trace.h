@@ -12,6 +12,7 @@
 #include "bvh_builder.h"
 #include "hippt_chain_logic.h"
 #include "hippt_device.h"
+#include "hippt_sky_rect.h"
 #include "hippt_slab.h"
 
 #pragma clang fp contract(off)
@@ -352,8 +353,18 @@ __device__ __forceinline__ unsigned run_item(unsigned v, unsigned k, unsigned wi
     return (v & 0x7fffffffu) + ((v >> 31) ? (k & ((1u << tileShift) - 1u)) + (k >> tileShift) * width : k);
 }
 
+// A table that leaves runs out (MeshParams::orderRow, HIPPT_OPT_SKY_COMBINE): the position splits by
+// the table's own row length, and a position past the row's runs is one of the band's last pixels
+// (skyrect::order_tail_item).  Item ids keep the band's frame stride.
+// ROWS: the kernel variant may get such a table (plan::sky_combine_kernel; launch_mesh refuses it otherwise)
+template <bool ROWS>
 __device__ __forceinline__ unsigned order_item(const MeshParams &P, unsigned it) {
     if (it == kNone || !P.runOrder) return it;
+    if (const unsigned row = !ROWS ? 0u : late_arg_at<unsigned>(unsigned(offsetof(MeshParams, orderRow)))) {
+        return skyrect::order_position_item(it, P.bandPixels, row,
+                                            late_arg_at<float>(unsigned(offsetof(MeshParams, rcpOrderRow))), P.runCount,
+                                            P.runOrder, unsigned(P.width), P.runTileShift);
+    }
     unsigned fl, q;
     divmod(it, P.bandPixels, P.rcpBandPixels, fl, q);
     const unsigned run = q >> 6;
@@ -368,6 +379,11 @@ __device__ __forceinline__ unsigned order_item_late(unsigned it) {
     if (!order) return it;
     const CamArgs A = cam_args_late();
     const unsigned runs = late_arg_at<unsigned>(unsigned(offsetof(MeshParams, runCount)));
+    if (const unsigned row = late_arg_at<unsigned>(unsigned(offsetof(MeshParams, orderRow))))
+        return skyrect::order_position_item(it, A.bandPixels, row,
+                                            late_arg_at<float>(unsigned(offsetof(MeshParams, rcpOrderRow))), runs, order,
+                                            unsigned(A.width),
+                                            late_arg_at<unsigned>(unsigned(offsetof(MeshParams, runTileShift))));
     unsigned fl, q;
     divmod(it, A.bandPixels, A.rcpBandPixels, fl, q);
     const unsigned run = q >> 6;
@@ -710,7 +726,9 @@ __device__ __forceinline__ void camera_ray(const CameraF &C, float s, float t, R
 // camera_ray's direction for a pinhole (lens_radius == 0, u and v finite) without the lens draw: the
 // lens offset is then +-0 whatever the draw gives, and x - (+-0) = x (a zero may differ in sign).  For
 // a sample that ends on this ray: the RNG state is not advanced.
-__device__ __forceinline__ void camera_dir_pinhole(const CameraF &C, float s, float t, Ray &r) {
+// (C: CameraF, or the combine's snapshot of its four vectors, SkyComb)
+template <typename Cam>
+__device__ __forceinline__ void camera_dir_pinhole(const Cam &C, float s, float t, Ray &r) {
     r.dx = fmaf(t, C.vertical[0], fmaf(s, C.horizontal[0], C.llc[0])) - C.origin[0];
     r.dy = fmaf(t, C.vertical[1], fmaf(s, C.horizontal[1], C.llc[1])) - C.origin[1];
     r.dz = fmaf(t, C.vertical[2], fmaf(s, C.horizontal[2], C.llc[2])) - C.origin[2];

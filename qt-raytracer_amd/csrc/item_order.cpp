@@ -199,16 +199,38 @@ void run_costs(const Bvh4 &bvh, const float *tris, const CameraF &cam, const Run
     for (auto &t : pool) t.join();
 }
 
-void build_item_table(const std::vector<float> &cost, const RunLayout &L, unsigned frames, unsigned queues,
-                      std::vector<uint32_t> &table) {
+size_t sky_runs(const RunLayout &L, int y0, int stride, const skyrect::Rect &rect, std::vector<uint8_t> &sky) {
+    const size_t n = run_count(L);
+    sky.assign(n, 0);
+    const skyrect::RunShape S{L.width, L.rows, L.tileShift, y0, stride};
+    size_t count = 0;
+    for (size_t r = 0; r < n; ++r) {
+        const uint32_t b = run_base(L, r);
+        sky[r] = skyrect::run_sky_certain(S, rect, b & ~kRunTile, (b & kRunTile) != 0) ? 1 : 0;
+        count += sky[r];
+    }
+    return count;
+}
+
+void build_item_table(const std::vector<float> &allCost, const RunLayout &L, unsigned frames, unsigned queues,
+                      std::vector<uint32_t> &table, const std::vector<uint8_t> *omit) {
+    // the runs the table holds (all of them without `omit`), in run order, and their costs
+    std::vector<uint32_t> kept;
+    std::vector<float> cost;
+    for (size_t r = 0; r < allCost.size(); ++r)
+        if (!omit || !(*omit)[r]) {
+            kept.push_back(uint32_t(r));
+            cost.push_back(allCost[r]);
+        }
     const size_t runs = cost.size(), slots = runs * frames;
     table.assign(slots, 0u);
     if (!slots) return;
     const unsigned bandPixels = L.width * L.rows;
-    const unsigned long long total = (unsigned long long)bandPixels * frames;
+    const unsigned rowLen = skyrect::order_row_len(bandPixels, unsigned(runs));
+    const unsigned long long total = (unsigned long long)rowLen * frames;
     // slot s: queue position pos(s) (which queue hands it out), items from item(s)
-    auto pos = [&](size_t s) { return (unsigned long long)(s / runs) * bandPixels + 64 * (s % runs); };
-    auto item = [&](size_t s) { return uint32_t((s / runs) * bandPixels) + run_base(L, s % runs); };
+    auto pos = [&](size_t s) { return (unsigned long long)(s / runs) * rowLen + 64 * (s % runs); };
+    auto item = [&](size_t s) { return uint32_t((s / runs) * bandPixels) + run_base(L, kept[s % runs]); };
     // A stable sort of each queue's slots (s = f*runs + r, ascending) by cost[r], longest first, in
     // O(slots): the runs by (cost descending, r ascending) once; a queue then takes each group of
     // equal-cost runs frame by frame (ascending slot order within a group is frame-major).

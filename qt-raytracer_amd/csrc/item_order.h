@@ -6,6 +6,7 @@
 
 #include "bvh_builder.h"
 #include "hippt_device.h"
+#include "hippt_sky_rect.h"
 
 namespace hippt {
 
@@ -42,7 +43,15 @@ void run_costs(const Bvh4 &bvh, const float *tris, const CameraF &cam, const Run
 // each of the `queues` contiguous queue ranges of positions (trace::queue_start) the slots come
 // longest estimate first (stable), so that waves hold samples of similar length and each queue ends
 // on the cheapest.  The order changes which lane traces a sample, never what it computes.
+// With `omit` (one flag per run; HIPPT_OPT_SKY_COMBINE) the table holds only the runs not flagged,
+// kept = runs - flagged per frame: slot s = f*kept + j (the j-th run not flagged) at queue position
+// f*rowLen + 64*j, rowLen = skyrect::order_row_len(bandPixels, kept); table[s] as above (item ids keep
+// the band's frame stride).  The queues split the smaller position space.
 void build_item_table(const std::vector<float> &cost, const RunLayout &L, unsigned frames, unsigned queues,
-                      std::vector<uint32_t> &table);
+                      std::vector<uint32_t> &table, const std::vector<uint8_t> *omit = nullptr);
+
+// sky[r] = 1 for each run of L (band rows y0 + k*stride) wholly outside the rectangle
+// (skyrect::run_sky_certain); returns how many.
+size_t sky_runs(const RunLayout &L, int y0, int stride, const skyrect::Rect &rect, std::vector<uint8_t> &sky);
 
 }  // namespace hippt

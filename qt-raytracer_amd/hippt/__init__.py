@@ -69,6 +69,7 @@ LIGHT_SAMPLING_MIS = 2  # light sampling with MIS (the power heuristic with the 
 OPT_LIGHT_SELECT = 39  # how a connection picks its light: 0 (default) uniformly, LIGHT_SELECT_POWER by area x emission
 LIGHT_SELECT_POWER = 1
 OPT_ENV_SAMPLING = 40  # connect every Lambertian vertex to the environment map by its selection table: 0 (default), 1
+OPT_SKY_COMBINE = 41  # sky-certain runs finished by the combine: -1 (default) automatic, 0 off (include/hippt.h)
 OPT_PIXEL_FORMAT = 25
 PIXEL_ARGB = 0
 PIXEL_RGBA8 = 1
@@ -84,6 +85,7 @@ INFO_LIGHT_SAMPLING = 108  # OPT_LIGHT_SAMPLING_MODE's value (1 or 2) if the las
 INFO_LIGHT_SELECT = 109  # OPT_LIGHT_SELECT's value if the last render took the light-sampling route and applied it
 INFO_ENVIRONMENT = 110  # the environment's size as the last render applied it (0: the gradient, or the built-in scene)
 INFO_ENV_SAMPLING = 111  # 1 if the last render applied OPT_ENV_SAMPLING
+INFO_SKY_COMBINE = 112  # band pixels of the last batch whose samples the combine finished (0: OPT_SKY_COMBINE off)
 INFO_DENOISE_NS = 200
 RAYS_DEVICE = 1
 HIT_SPHERE = 1 << 30
