@@ -265,31 +265,58 @@ __device__ __forceinline__ float3 sky_comb_sample(const SkyComb &K, unsigned x, 
     return L;
 }
 
-template <int UNROLL, bool HOST = false, bool SKYC = true>
+// One sample L of frame f into the running average: acc = (acc * ff + L) / fc, ff = float(f), fc = float(f + 1).
+// carry: float(f) on entry, float(f + 1) on return (ff of a frame is fc of the one before: one conversion).
+// FAST: one reciprocal of fc and three corrected quotients (hippt_trace.h avg_div) in place of three IEEE
+// divisions, which stay for the sample whose numerators leave avg_div's domain (avg_div_guard: a branch no real
+// radiance takes).  !FAST: the divisions alone, for the one megakernel variant the short form costs a stack slot
+// (mesh_kernel's FASTAVG).
+template <bool FAST>
+__device__ __forceinline__ void average_in(float &accx, float &accy, float &accz, float lx, float ly, float lz, int f,
+                                           float &carry) {
+    if (!FAST) {  // (the parent's code as it stood: the variant is that sensitive)
+        const float ff = float(f), fc = float(f + 1);
+        accx = fmaf(accx, ff, lx) / fc;
+        accy = fmaf(accy, ff, ly) / fc;
+        accz = fmaf(accz, ff, lz) / fc;
+        return;
+    }
+    const float ff = carry, fc = float(f + 1);
+    carry = fc;
+    const float ax = fmaf(accx, ff, lx), ay = fmaf(accy, ff, ly), az = fmaf(accz, ff, lz);
+    const float y = rcp_nr(fc);
+    float qx = avg_div(ax, fc, y), qy = avg_div(ay, fc, y), qz = avg_div(az, fc, y);
+    if (avg_div_guard(ax, ay, az, qx, qy, qz)) {
+        qx = ax / fc;
+        qy = ay / fc;
+        qz = az / fc;
+    }
+    accx = qx;
+    accy = qy;
+    accz = qz;
+}
+
+template <int UNROLL, bool HOST = false, bool SKYC = true, bool FASTAVG = true>
 __device__ __forceinline__ void combine_pixel(const CombineParams &P, const SkyArg A, unsigned p,
                                               const HostFrame H = HostFrame{}) {
     float4 acc = P.accum[p];
     unsigned sx = 0, sy = 0;
     SkyComb K;
     if (SKYC && sky_comb_pixel(A, p, K, sx, sy)) {
+        float fc = float(P.firstFrame);
         for (int fl = 0; fl < P.frames; ++fl) {
             const int f = P.firstFrame + fl;
-            const float ff = float(f), fc = float(f + 1);
             const float3 L = sky_comb_sample(K, sx, sy, unsigned(f));
-            acc.x = fmaf(acc.x, ff, L.x) / fc;
-            acc.y = fmaf(acc.y, ff, L.y) / fc;
-            acc.z = fmaf(acc.z, ff, L.z) / fc;
+            average_in<FASTAVG>(acc.x, acc.y, acc.z, L.x, L.y, L.z, f, fc);
         }
     } else {
+        float fc = float(P.firstFrame);
 #pragma unroll UNROLL
         for (int fl = 0; fl < P.frames; ++fl) {
             const size_t k = size_t(fl) * P.bandPixels + p;
             const int f = P.firstFrame + fl;
-            const float ff = float(f), fc = float(f + 1);
             const float3 L = *reinterpret_cast<const float3 *>(P.scratch + 3 * k);
-            acc.x = fmaf(acc.x, ff, L.x) / fc;
-            acc.y = fmaf(acc.y, ff, L.y) / fc;
-            acc.z = fmaf(acc.z, ff, L.z) / fc;
+            average_in<FASTAVG>(acc.x, acc.y, acc.z, L.x, L.y, L.z, f, fc);
         }
     }
     acc.w = 1.0f;
@@ -306,7 +333,7 @@ __device__ __forceinline__ void combine_pixel(const CombineParams &P, const SkyA
 // once every chunk is claimed.  Wave-uniform.  The frame loop is not unrolled here: unrolled 8x
 // at the kernel's two call sites it cost blob70k 3% even with the combine off (r3g/r3h; none
 // without the unroll, r3i).
-template <bool SKYC>
+template <bool SKYC, bool FASTAVG>
 __device__ __forceinline__ bool combine_chunk(const MeshParams &P) {
     unsigned base = 0;
     if (__lane_id() == 0) base = atomicAdd(P.combCtr, 64u);
@@ -314,7 +341,7 @@ __device__ __forceinline__ bool combine_chunk(const MeshParams &P) {
     if (base >= P.comb.bandPixels) return false;
     const unsigned p = base + __lane_id();
     if (p < P.comb.bandPixels)
-        combine_pixel<1, false, SKYC>(P.comb, sky_arg(SKYC ? late_field(comb.sky.on) : 0, unsigned(offsetof(MeshParams, comb.sky))), p);
+        combine_pixel<1, false, SKYC, FASTAVG>(P.comb, sky_arg(SKYC ? late_field(comb.sky.on) : 0, unsigned(offsetof(MeshParams, comb.sky))), p);
     return true;
 }
 
@@ -348,7 +375,7 @@ struct ChainCombArgs {
     __device__ __forceinline__ unsigned shift() const { return P.shift; }
     __device__ __forceinline__ int step() const { return P.step; }
 };
-template <int UNROLL, bool SKYC, typename Src>
+template <int UNROLL, bool SKYC, typename Src, bool FASTAVG = true>
 __device__ __forceinline__ void combine_pixel_chain(const Src &S, const SkyArg A, unsigned p, int c0, int c1) {
     float4 acc = S.accum()[p];
     unsigned sx = 0, sy = 0;
@@ -357,12 +384,10 @@ __device__ __forceinline__ void combine_pixel_chain(const Src &S, const SkyArg A
         const int first = S.firstFrame(), frames = S.frames(), step = S.step();
         for (int b = c0; b <= c1; ++b) {
             const int f0 = first + b * step;
+            float fc = float(f0);
             for (int fl = 0; fl < frames; ++fl) {
                 const float3 L = sky_comb_sample(K, sx, sy, unsigned(f0 + fl));
-                const float ff = float(f0 + fl), fc = float(f0 + fl + 1);
-                acc.x = fmaf(acc.x, ff, L.x) / fc;
-                acc.y = fmaf(acc.y, ff, L.y) / fc;
-                acc.z = fmaf(acc.z, ff, L.z) / fc;
+                average_in<FASTAVG>(acc.x, acc.y, acc.z, L.x, L.y, L.z, f0 + fl, fc);
             }
         }
     } else {
@@ -372,13 +397,11 @@ __device__ __forceinline__ void combine_pixel_chain(const Src &S, const SkyArg A
         for (int b = c0; b <= c1; ++b) {
             const float *scr = scratch + 3 * ((size_t(unsigned(b) & (slots - 1u)) << shift) + p);
             const int f0 = first + b * step;
+            float fc = float(f0);
 #pragma unroll UNROLL
             for (int fl = 0; fl < frames; ++fl) {
                 const float3 L = *reinterpret_cast<const float3 *>(scr + 3 * size_t(fl) * bandPixels);
-                const float ff = float(f0 + fl), fc = float(f0 + fl + 1);
-                acc.x = fmaf(acc.x, ff, L.x) / fc;
-                acc.y = fmaf(acc.y, ff, L.y) / fc;
-                acc.z = fmaf(acc.z, ff, L.z) / fc;
+                average_in<FASTAVG>(acc.x, acc.y, acc.z, L.x, L.y, L.z, f0 + fl, fc);
             }
         }
     }
@@ -617,7 +640,9 @@ __global__ __launch_bounds__(kMeshBlock, (FULL || WIDE) ? HIPPT_WIDE_WAVES_PER_E
     // HIPPT_OPT_SKY_COMBINE: this variant's fused combine has the sky branch (the host gives the others no
     // sky-mode combine: plan::sky_combine_kernel, checked in launch_mesh)
     constexpr bool SKYCOMB = plan::sky_combine_kernel(STATS, LDS_SCENE, FULL, SPILL, POOL, CHAIN);
-    auto comb_step = [&]() { return CHAIN ? combine_chunk_chain<SKYCOMB>(cw) : combine_chunk<SKYCOMB>(P); };
+    // (the short average costs this one variant a stack slot: profiles/exact_div/regs.txt)
+    constexpr bool FASTAVG = !(!STATS && LDS_SCENE && !FULL && SPILL && POOL && !CHAIN);
+    auto comb_step = [&]() { return CHAIN ? combine_chunk_chain<SKYCOMB>(cw) : combine_chunk<SKYCOMB, FASTAVG>(P); };
     if (combLeft && (blockIdx.x & 1u) == 0 && threadIdx.x < 64u)
         while (combLeft) combLeft = comb_step();
     for (;;) {

@@ -51,6 +51,12 @@ __device__ __forceinline__ float rand_pm1(uint32_t &s) {
 //   sqrt_fix(x) == sqrtf(x)                   for every x except the denormals (x >= 2^-104)
 //   rcp_nr(x)   == 1.0f / x                   for 2^-126 <= |x| < 2^126
 //   rcp_nr(sqrt_fix(x)) == 1.0f / sqrtf(x)    for 2^-105 <= x < +inf
+// and division itself, against hipcc's a / b (tests/native/div_selftest.hip, tests/test_gpu_division.py:
+// hashed pairs, every divisor mantissa, every exponent pair; the average's shape on every float a):
+//   div_core(a, b, rcp_nr(b)) == a / b        for 2^-126 <= |b| < 2^126, 2^-102 <= |a| < inf,
+//                                             2^-126 <= |a / b| < inf
+//   div_rn(a, b) == a / b                     for every a and b
+//   avg_div(a, fc, rcp_nr(fc)) == a / fc      for fc = float(n), 1 <= n <= 2^31, a = +-0 or 2^-94 <= |a| < inf
 // v_sqrt_f32 is within one ulp, so the correctly rounded root is s or a neighbour, picked by
 // the signs of the exact residuals x - s'*s (one fma each); v_rcp_f32 is within one ulp and one
 // Newton step rounds correctly.
@@ -67,6 +73,60 @@ __device__ __forceinline__ float sqrt_fix(float x) {
 __device__ __forceinline__ float rcp_nr(float x) {
     const float y = __builtin_amdgcn_rcpf(x);
     return fmaf(fmaf(-x, y, 1.0f), y, y);
+}
+
+// a / b as a short sequence (hipcc's IEEE expansion of a division is 11 instructions: two
+// v_div_scale, v_rcp, six FMA/multiply, v_div_fmas, v_div_fixup).  With y = rcp_nr(b) = RN(1/b),
+// q = RN(a*y) lies within one ulp of a/b, the residual r = a - b*q is then exactly representable
+// and one FMA computes it, and q' = RN(q + r*y) is the correctly rounded quotient (Markstein's
+// correction step after a correctly rounded reciprocal): three instructions after the reciprocal,
+// which one divisor shares among its numerators.  The argument needs
+//   y correctly rounded:   2^-126 <= |b| < 2^126 (rcp_nr's verified range);
+//   r exact:               r is a multiple of ulp(b)*ulp(q) >= 2^-47 |a|, so |a| >= 2^-102, a finite;
+//   q, q' normal:          2^-126 <= |a/b| < 2^128 (below, q' rounds on the denormal grid, where
+//                          a/b can be a tie that q + r*y with y != 1/b leaves on the wrong side).
+// div_core's claimed domain is exactly that (tests/native/div_selftest.hip counts it on its own).
+// Outside: a = +-0 gives +0 whenever the quotient is -0 (r = a - b*q is +0 for either zero, and
+// +0 + -0 = +0); a denormal b gives y = NaN; an infinite a gives r = NaN; a NaN a or b gives a NaN.
+// div_core has no caller in the kernels yet: the triangle hit's t = num / det measured slower with it
+// (DESIGN_LOG.md §A.X) and the sphere tests have not been tried.
+__device__ __forceinline__ float div_core(float a, float b, float y) {
+    const float q = a * y;
+    return fmaf(fmaf(-b, q, a), y, q);
+}
+
+// a / b, bit for bit, for any a and b: the short sequence where both magnitudes lie in
+// [2^-62, 2^62] (inside div_core's domain: the quotient is then in (2^-125, 2^125)), the IEEE
+// expansion outside, in a branch real operands of that size do not take.
+__device__ __forceinline__ float div_rn(float a, float b) {
+    const float aa = fabsf(a), ab = fabsf(b);
+    if (aa >= 0x1p-62f && aa <= 0x1p62f && ab >= 0x1p-62f && ab <= 0x1p62f) return div_core(a, b, rcp_nr(b));
+    return a / b;
+}
+
+// The running average's a / fc: fc = float(n) of a frame count 1 <= n <= 2^31, y = rcp_nr(fc)
+// shared by the three channels.  b is an integer-valued float, so b*q is a multiple of q's ulp
+// and r is exact for every finite a, denormals included; with the residual taken as r' = b*q - a
+// and multiplied by -y, a zero keeps its sign (q = a*y has it, r' is +0 for either zero, and
+// (+0)*(-y) = -0 adds to q without changing it), which div_core's form loses for -0.  What is
+// left outside is the denormal quotient (ties, as above) and the non-finite a: the domain is
+// a = +-0 or 2^-94 <= |a| < inf (2^-94 / 2^31 > 2^-126).  Outside it an infinite or NaN a makes the
+// result NaN (for a NaN a the division's NaN bit for bit on gfx950, which no caller relies on).
+__device__ __forceinline__ float avg_div(float a, float fc, float y) {
+    const float q = a * y;
+    return fmaf(fmaf(fc, q, -a), -y, q);
+}
+// avg_div's guard for the three channels of one sample, numerators a and quotients q: true where
+// a numerator is nonzero and below 2^-94 in magnitude, or a quotient is infinite or NaN; the caller
+// then divides.  (bits << 1) - 1 drops the sign and wraps +-0 to the top, so one unsigned minimum
+// finds a small nonzero magnitude (bits(2^-94) = 0x10800000); the sum of the magnitudes is not
+// finite where a quotient is not, and also where it merely overflows, where dividing is right too.
+// One comparison each: as six float comparisons the guard cost the flagship megakernel a stack
+// slot (DESIGN_LOG.md §A.X).
+__device__ __forceinline__ bool avg_div_guard(float ax, float ay, float az, float qx, float qy, float qz) {
+    const unsigned ux = (__float_as_uint(ax) << 1) - 1u, uy = (__float_as_uint(ay) << 1) - 1u,
+                   uz = (__float_as_uint(az) << 1) - 1u;
+    return min(ux, min(uy, uz)) < 2u * 0x10800000u - 1u || !(fabsf(qx) + fabsf(qy) + fabsf(qz) < INFINITY);
 }
 
 // 1.0f / sqrtf(x), bit for bit, for any x: the short sequence inside its verified range, the IEEE
